@@ -14,7 +14,12 @@ and ends with ONE exchange of the RGBW frame to rank 0 -- ImageBlock::put(ImageB
 across GPUs: `--merge reduce` (RCCL sum-reduce, either split) or `--merge gather` (RCCL gather of each rank's
 tile columns + halo, tile split only).  Total work is fixed as N grows -> "scaling": "strong".
 
-Rank 0 prints ONE JSON line: the contract fields plus
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times `--steps` render passes and prints the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step = wall-clock milliseconds of one timed pass, ...), the configuration,
+the pass split of the timed passes (HIP events per kernel class) and the tree.  `--dump-outputs DIR` writes what the last timed
+pass computed: DIR/rgbw.npy, the RGBW frame a caller of the path receives (rank 0: the merged frame; float32; a fixed, seeded
+sample of its pixels beside DIR/rgbw_pixel_index.npy when the frame exceeds 48 MB), and DIR/ray_counts.npy (float64: closest-hit
+and shadow rays of the pass, all ranks).  `--full` adds what takes passes or runs of its own:
   roofline      dominant kernel (the ray-query kernel, all its launches of one pass), timed live with HIP events on
                 the launch stream.  bound "valu": scenes whose BVH is cache-resident are VALU-issue bound
                 (profiles/*_counters.json: SQ_INSTS_VALU x the kernel's cycles per instruction vs elapsed cycles);
@@ -80,6 +85,10 @@ def parse_args(argv=None):
                     help="TEST ONLY (tests/test_distributed_cpu.py): run the same sharding / merge / reporting code on CPU "
                          "ranks (gloo) with the emulated device headers standing in for the GPU; never a fallback")
     ap.add_argument("--dump-frame", default=None, help="rank 0 saves the merged RGBW frame of the last step (.npy)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the instrumented pass and roofline, the CPU baseline and the parity verdict (off: only the timed steps)")
     return ap.parse_args(argv)
 
 
@@ -170,6 +179,25 @@ def bound_evidence(workload: str):
     return best
 
 
+DUMP_FRAME_BYTES = 48 << 20      # a larger frame is dumped as a fixed, seeded sample of its pixels (the dump stays below 64 MB)
+DUMP_SAMPLE_PIXELS = 1 << 20
+
+
+def dump_outputs(out_dir: str, frame, ray_counts) -> None:
+    """--dump-outputs: what the last timed step computed -- the RGBW frame a caller receives (float32) and its ray counts (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_FRAME_BYTES:
+        np.save(os.path.join(out_dir, "rgbw.npy"), frame)
+    else:
+        px = frame.reshape(-1, frame.shape[-1])
+        idx = np.sort(np.random.default_rng(12345).choice(px.shape[0], DUMP_SAMPLE_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "rgbw.npy"), px[idx])
+        np.save(os.path.join(out_dir, "rgbw_pixel_index.npy"), idx.astype(np.float64))      # row-major index into the (H, W) frame
+    np.save(os.path.join(out_dir, "ray_counts.npy"), np.asarray(ray_counts, dtype=np.float64))
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -236,12 +264,8 @@ def main():
                                         tiles_x=tiles_x, border=r.border, merge_ms=merge_ms, stream=stream, want_stats=want_stats,
                                         count_traversal=count, time_kernels=time_kernels)
 
-    # one instrumented pass: traversal counters for the roofline (untimed)
-    counted = step(want_stats=True, count=True)
-    if "engine" in counted:
-        engine = {0: "megakernel", 1: "wavefront", 2: "block-serial"}[int(counted["engine"])]
-    else:                      # --emulate: the CPU harness walks paths one by one, sized like the library's rule would
-        engine = args.engine if args.engine != "auto" else ("wavefront" if my_tiles * 256 * shard["spp_count"] >= (1 << (24 if sc.integrator.type == "normals" else 19)) else "megakernel")
+    # --full: one instrumented pass, traversal counters for the roofline (untimed)
+    counted = step(want_stats=True, count=True) if args.full else None
     for _ in range(args.warmup):
         step()
     barrier()
@@ -256,6 +280,18 @@ def main():
         film_ms.append(last.get("film_ms", 0.0)); trace_launches = last.get("n_trace_launches", 0)
     barrier()
     dt = time.perf_counter() - t0
+
+    src = counted if args.full else last
+    if "engine" in src:
+        engine = {0: "megakernel", 1: "wavefront", 2: "block-serial"}[int(src["engine"])]
+    else:                      # --emulate: the CPU harness walks paths one by one, sized like the library's rule would
+        engine = args.engine if args.engine != "auto" else ("wavefront" if my_tiles * 256 * shard["spp_count"] >= (1 << (24 if sc.integrator.type == "normals" else 19)) else "megakernel")
+    if args.dump_outputs:
+        counts = torch.tensor([float(last["n_closest_rays"]), float(last["n_shadow_rays"])], dtype=torch.float64, device=dev)
+        if world > 1:
+            dist.all_reduce(counts, op=dist.ReduceOp.SUM)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, frame.cpu().numpy(), counts.cpu().numpy())
 
     rays_local = float(last["n_closest_rays"] + last["n_shadow_rays"])
     t = torch.tensor([dt, rays_local], dtype=torch.float64, device=dev)
@@ -273,11 +309,9 @@ def main():
     else:
         rays_total = rays_local
 
-    if rank == 0:
-        if args.dump_frame:
-            np.save(args.dump_frame, frame.cpu().numpy())
-        ms_per_step = dt / args.steps * 1e3
-        mrays = rays_total / (ms_per_step * 1e-3) / 1e6
+    def roofline():
+        """--full: the dominant kernel's roofline from the instrumented pass's traversal counts and the timed passes' HIP-event
+        times, with the committed counter summary / bound evidence of this build where there is one.  Returns (roofline, counters)."""
         k_ms, t_ms = float(np.mean(kernel_ms)), float(np.mean(trace_ms))
         if t_ms <= 0.0:
             t_ms = k_ms
@@ -392,6 +426,15 @@ def main():
             for k in ("valu_cycles_per_instr", "valu_lanes_per_instr", "valu_useful_frac", "l2_hit_rate"):
                 if k in cd:
                     roof[k] = cd[k]
+        return roof, ctr
+
+    if rank == 0:
+        if args.dump_frame:
+            np.save(args.dump_frame, frame.cpu().numpy())
+        ms_per_step = dt / args.steps * 1e3
+        mrays = rays_total / (ms_per_step * 1e-3) / 1e6
+        k_ms = float(np.mean(kernel_ms))
+        roof, ctr = roofline() if args.full else (None, None)
         out = {
             "metric": "Mrays/sec (primary+secondary) at 1024x1024 256spp" if wl.name == "pa4-cbox-path_mis" else "Mrays/sec (primary+secondary)",
             "value": round(mrays, 2), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -414,12 +457,14 @@ def main():
                           # auto (nori_hip_build_accel): the device's builder (PLOC), the host's SAH builder as its fall-back
                           builder=args.builder if args.builder != "auto" else ("ploc" if info["built_on_device"] else "host"), builder_asked=args.builder),
         }
+        if not args.full:      # the roofline and the committed profile's bytes go with the instrumented pass
+            del out["roofline"], out["pass"]["hbm_measured_bytes"]
         if world > 1 or merge_ms:
             out["ranks"] = [{"rank": k, "ms_per_step": round(float(v[0]), 3), "kernel_ms": round(float(v[1]), 3), "merge_ms": round(float(v[2]), 3),
                              "rays_per_step": int(v[3])} for k, v in enumerate(per_rank)]
-    # the CPU leg runs on rank 0 (the other ranks wait); the parity render that follows is the distributed one -- every rank its
+    # --full: the CPU leg runs on rank 0 (the other ranks wait); the parity render that follows is the distributed one -- every rank its
     # share of the sample the CPU rendered, merged on rank 0 -- so the verdict is about the frame a multi-GPU run produces
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         sample = torch.zeros(3, dtype=torch.int64, device=dev)
         if rank == 0:
             cpu, A, mod, s_cpu = cpu_baseline(wl, args, whole_tiles=world > 1, min_spp=world if (world > 1 and split == "sample") else 1)

@@ -69,7 +69,7 @@ def test_bench_spawns_ranks_and_merges(tmp_path, whole, world, split, merge):
     """`python bench.py --gpus N` starts its own N ranks (no external launcher) and rank 0 holds the merged frame."""
     frame = tmp_path / "frame.npy"
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    cmd = [sys.executable, BENCH, "--gpus", str(world), "--emulate", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
+    cmd = [sys.executable, BENCH, "--gpus", str(world), "--emulate", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline",
            "--workload", "pa4-cbox-path_mis", "--width", str(SIZE["width"]), "--height", str(SIZE["height"]), "--spp", str(SIZE["spp"]),
            "--split", split, "--merge", merge, "--dump-frame", str(frame)]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
@@ -89,7 +89,7 @@ def test_bench_line_of_a_multi_rank_run_is_complete(world, split, merge):
     """A line for N > 1 carries what a line for N = 1 carries -- roofline, cpu_baseline (rank 0's host cores) and a parity block,
     here on the frame MERGED from all ranks -- plus what every rank saw (its wall clock, its kernels, its time in the merge)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    cmd = [sys.executable, BENCH, "--gpus", str(world), "--emulate", "--steps", "1", "--warmup", "0", "--cpu-seconds", "0.5",
+    cmd = [sys.executable, BENCH, "--gpus", str(world), "--emulate", "--steps", "1", "--warmup", "0", "--full", "--cpu-seconds", "0.5",
            "--workload", "pa4-cbox-path_mis", "--width", "64", "--height", "32", "--spp", "4", "--split", split, "--merge", merge]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
@@ -101,6 +101,49 @@ def test_bench_line_of_a_multi_rank_run_is_complete(world, split, merge):
     assert [r["rank"] for r in out["ranks"]] == list(range(world))
     assert all(r["ms_per_step"] > 0 and r["merge_ms"] >= 0 and r["rays_per_step"] > 0 for r in out["ranks"])
     assert sum(r["rays_per_step"] for r in out["ranks"]) == out["config"]["rays_per_step"]
+
+
+@pytest.mark.parametrize("world,split,merge", [(1, "tile", "reduce"), (2, "tile", "gather"), (3, "sample", "reduce")])
+def test_plain_bench_line_and_dumped_outputs(tmp_path, whole, world, split, merge):
+    """A plain run (no --full) times exactly --steps passes and prints the headline fields without the instrumented pass, the
+    CPU baseline or the parity render; --dump-outputs holds what the last timed pass computed: the merged RGBW frame and its
+    ray counts, the same whatever the number of steps."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    ref, st = whole
+    for steps in (1, 3):
+        out_dir = tmp_path / f"steps{steps}"
+        cmd = [sys.executable, BENCH, "--gpus", str(world), "--emulate", "--steps", str(steps), "--warmup", "1",
+               "--workload", "pa4-cbox-path_mis", "--width", str(SIZE["width"]), "--height", str(SIZE["height"]), "--spp", str(SIZE["spp"]),
+               "--split", split, "--merge", merge, "--dump-outputs", str(out_dir)]
+        p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == steps and out["warmup"] == 1 and out["n_gpus"] == world
+        assert out["unit"] == "Mrays/s" and out["higher_is_better"] is True and out["dtype"] == "f32" and out["ms_per_step"] > 0
+        assert abs(out["value"] - out["config"]["rays_per_step"] / out["ms_per_step"] / 1e3) <= 0.01 + 1e-3 * out["value"]
+        assert not {"roofline", "cpu_baseline", "parity"} & set(out)
+        assert sorted(os.listdir(out_dir)) == ["ray_counts.npy", "rgbw.npy"]
+        rgbw, counts = np.load(out_dir / "rgbw.npy"), np.load(out_dir / "ray_counts.npy")
+        assert rgbw.dtype == np.float32 and counts.dtype == np.float64
+        np.testing.assert_allclose(rgbw, ref, rtol=2e-5, atol=1e-6)
+        assert counts.tolist() == [st["n_closest_rays"], st["n_shadow_rays"]] and sum(counts) == out["config"]["rays_per_step"]
+
+
+def test_dumped_frame_beyond_the_limit_is_a_fixed_sample(tmp_path):
+    """A frame above the dump limit is written as the same seeded sample of its pixels every time, with their indices."""
+    import bench
+    frame = np.random.default_rng(1).random((1040, 3100, 4), dtype=np.float32)      # > 48 MB
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), frame, [1.0, 2.0])
+    idx = np.load(tmp_path / "a" / "rgbw_pixel_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == bench.DUMP_SAMPLE_PIXELS and np.all(np.diff(idx) > 0)
+    got = np.load(tmp_path / "a" / "rgbw.npy")
+    np.testing.assert_array_equal(got, frame.reshape(-1, 4)[idx.astype(np.int64)])
+    for n in ("rgbw.npy", "rgbw_pixel_index.npy", "ray_counts.npy"):
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in os.listdir(tmp_path / "a")) < 64 << 20
 
 
 def test_bench_without_gpu_fails_at_no_gpu():

@@ -11,8 +11,17 @@ import pytest
 from nori_amd import NoriError, _capi, host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/scenes"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
+SCENES = os.path.join(ROOT, "tests", "golden", "reference_scenes.tar.xz")      # the reference's shipped scenes: XML + the OBJ files they name
+
+
+@pytest.fixture(scope="module")
+def ref_scenes(tmp_path_factory):
+    """The reference's shipped scenes, unpacked; returns the directory that holds pa1 ... pa5."""
+    import tarfile
+    d = tmp_path_factory.mktemp("reference")
+    with tarfile.open(SCENES) as t:
+        t.extractall(d, filter="data")
+    return str(d / "scenes")
 
 
 def _declared(header):
@@ -177,12 +186,11 @@ def test_exr_png_roundtrip(tmp_path):
     assert np.abs(px.astype(int) - np.clip(255 * srgb, 0, 255).astype(int)).max() <= 1
 
 
-@needs_ref
-def test_shipped_scenes_load_unchanged():
+def test_shipped_scenes_load_unchanged(ref_scenes):
     import glob
     ok = 0
-    for f in sorted(glob.glob(REF + "/**/*.xml", recursive=True)):
-        if "ajax" in f:       # ajax.obj is not shipped with the reference
+    for f in sorted(glob.glob(ref_scenes + "/**/*.xml", recursive=True)):
+        if "ajax" in f:       # ajax.obj is not shipped with the reference (nor kept here)
             with pytest.raises(NoriError, match="Unable to open OBJ file"):
                 host.HostRoot(f)
             continue
@@ -194,11 +202,10 @@ def test_shipped_scenes_load_unchanged():
     assert ok >= 19
 
 
-@needs_ref
-def test_golden_fixtures_are_current():
-    """tests/golden/*.npz equal what the host produces from the reference files now."""
+def test_golden_fixtures_are_current(ref_scenes):
+    """tests/golden/*.npz equal what the host produces from the reference's scene files (tests/golden/reference_scenes.tar.xz) now."""
     from nori_amd.scene import Scene
-    sc = host.load_xml(REF + "/pa5/cbox/cbox_mis.xml")
+    sc = host.load_xml(ref_scenes + "/pa5/cbox/cbox_mis.xml")
     g = Scene.load_npz(os.path.join(ROOT, "tests", "golden", "pa5-cbox_mis.npz"))
     assert len(sc.meshes) == len(g.meshes) == 6
     for a, b in zip(sc.meshes, g.meshes):

@@ -15,7 +15,7 @@ ENG=${4:-wavefront}      # the engine the library picks for this workload (c1: m
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp
-B="python bench.py --steps 3 --warmup 1 --workload $WL"
+B="python bench.py --full --steps 3 --warmup 1 --workload $WL"      # --full: the line with its roofline, CPU baseline and parity block
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o s -- $B --no-cpu-baseline > $OUT/stats.log 2>&1
 find /tmp/prof_stats -name '*kernel_stats.csv' -exec cp {} $OUT/${TAG}_kernel_stats.csv \;
 rm -rf /tmp/prof_stats
