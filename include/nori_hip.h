@@ -38,7 +38,7 @@ extern "C" {
  * before its first call that passes such a struct, and refuses to go on if they differ (the host library and the Python
  * bindings of this repository do).  Bumped whenever a struct of this header changes size or layout, an enum value changes
  * meaning, or an entry point changes its signature. */
-#define NORI_HIP_ABI_VERSION 7      /* round 6: nori_render_stats as of round 5 (tail_ms, tail_cus); option "wavefront_samples"; nori_accel_info: built_on_device, n_references */
+#define NORI_HIP_ABI_VERSION 8      /* textures: nori_texture_desc, nori_scene_desc.{n_textures, textures}, nori_mesh_desc.albedo_texture, nori_hip_texture_eval */
 int nori_hip_abi_version(void);
 
 /* ------------------------------------------------------------------ enums */
@@ -128,6 +128,15 @@ typedef enum nori_accel_builder {
                                   10 M triangles +2.7 %; built in 19 / 28 / 33 / 144 ms against 30 / 56 / 90 / 2 400 */
 } nori_accel_builder;
 
+/* Albedo textures (no counterpart in the reference, which has no Texture class; src/accel.cpp:73 computes the texture
+ * coordinates "if provided by the mesh" and nothing reads them).  See nori_texture_desc. */
+typedef enum nori_texture_type {
+    NORI_TEXTURE_IMAGE = 0,
+    NORI_TEXTURE_CHECKERBOARD = 1
+} nori_texture_type;
+typedef enum nori_texture_filter { NORI_FILTER_NEAREST = 0, NORI_FILTER_BILINEAR = 1 } nori_texture_filter;
+typedef enum nori_texture_wrap { NORI_WRAP_REPEAT = 0, NORI_WRAP_CLAMP = 1 } nori_texture_wrap;
+
 /* ------------------------------------------------------ scene description */
 
 /* BSDF parameters; defaults as in the reference constructors
@@ -156,7 +165,33 @@ typedef struct nori_mesh_desc {
     nori_bsdf_desc bsdf;
     int32_t is_emitter;        /* <emitter type="area">                    */
     float radiance[3];
+    uint32_t albedo_texture;   /* 1-based index into nori_scene_desc::textures that replaces bsdf.albedo; 0 = none.
+                                  Diffuse BSDFs only */
 } nori_mesh_desc;
+
+/* A texture that gives a diffuse BSDF its albedo at the hit's uv (nori_intersection::uv: the mesh's interpolated texture
+ * coordinates, or the barycentric (u, v) where it has none -- src/accel.cpp:38,73-77).  The lookup, in float32 without FMA
+ * contraction, in this order:
+ *   s = u * uscale + uoffset, t = v * vscale + voffset; a non-finite s or t becomes 0.
+ *   CHECKERBOARD: ps = floor(s) - 2 floor(s / 2), pt likewise: color0 if ps == pt, else color1.
+ *   IMAGE:  wrap  -- REPEAT: s -= floor(s) (may round to 1); CLAMP: s = clamp(s, 0, 1); t the same; then t = 1 - t (v = 1 is
+ *                    the top row, row 0 of `texels`)
+ *           NEAREST  -- texel (min((int) (s W), W - 1), min((int) (t H), H - 1))
+ *           BILINEAR -- x = s W - 0.5, x0 = floor(x), fx = x - x0; columns (int) x0 and (int) x0 + 1, reduced modulo W into
+ *                       [0, W) for REPEAT, clamped to [0, W - 1] for CLAMP; rows from y = t H - 0.5 the same way; blended
+ *                       with lerp(a, b, f) = a + f (b - a) along x in both rows, then along y (a constant image returns its
+ *                       texel's value exactly).
+ * No mip-mapping: one lookup per shaded hit. */
+typedef struct nori_texture_desc {
+    int32_t type;              /* nori_texture_type */
+    uint32_t width, height;    /* IMAGE: 1 .. 16384 each; ignored for CHECKERBOARD */
+    const float *texels;       /* IMAGE: 3 * width * height floats, linear RGB, row-major, row 0 = the top row of the image */
+    int32_t filter;            /* nori_texture_filter */
+    int32_t wrap;              /* nori_texture_wrap */
+    float uscale, vscale;      /* 1 for an unscaled texture */
+    float uoffset, voffset;
+    float color0[3], color1[3];/* CHECKERBOARD */
+} nori_texture_desc;
 
 /* src/perspective.cpp:22-39; to_world is row-major 4x4 (camera -> world). */
 typedef struct nori_camera_desc {
@@ -187,6 +222,8 @@ typedef struct nori_scene_desc {
     nori_rfilter_desc rfilter;
     nori_integrator_desc integrator;
     int32_t sample_count;      /* Independent::m_sampleCount               */
+    uint32_t n_textures;       /* referenced by nori_mesh_desc::albedo_texture */
+    const nori_texture_desc *textures;
 } nori_scene_desc;
 
 /* ------------------------------------------------------- per-query records */
@@ -299,11 +336,17 @@ void nori_hip_destroy(nori_hip_ctx *ctx);
 const char *nori_hip_last_error(const nori_hip_ctx *ctx);
 
 /* Copy the scene into HBM (SoA vertex/index buffers, material and emitter
- * tables, camera, filter table).  Replaces the load-time half of
+ * tables, textures, camera, filter table).  NORI_ERR_INVALID_ARGUMENT (with a message) for a texture index out of range, a
+ * texture on a mesh whose BSDF is not diffuse, an image of zero or more than 16384 texels in a dimension, or an image
+ * without texels.  Replaces the load-time half of
  * Scene::addChild / Accel::addMesh (src/scene.cpp:48-52, src/accel.cpp:12-17),
  * the ImageBlock filter tabulation (src/block.cpp:18-27) and
  * PerspectiveCamera::activate (src/perspective.cpp:41-74). */
 int nori_hip_upload_scene(nori_hip_ctx *ctx, const nori_scene_desc *scene);
+
+/* Evaluate texture `texture` (1-based, as nori_mesh_desc::albedo_texture) of the uploaded scene at n points uv (2n floats,
+ * HOST memory) on the device, with the lookup the shading uses; rgb: 3n floats. */
+int nori_hip_texture_eval(nori_hip_ctx *ctx, uint32_t texture, const float *uv, size_t n, float *rgb);
 
 /* Accel::build (src/accel.cpp:19-21 -- a no-op in the reference, a BVH here) */
 int nori_hip_build_accel(nori_hip_ctx *ctx, int builder /* nori_accel_builder */);

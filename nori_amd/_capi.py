@@ -21,6 +21,9 @@ INTEGRATOR_NAMES = {"normals": 0, "ao": 1, "simple": 2, "whitted": 3,
 RFILTER_NAMES = {"gaussian": 0, "mitchell": 1, "tent": 2, "box": 3}
 WARP_NAMES = {"square": 0, "tent": 1, "disk": 2, "uniform_sphere": 3,
               "uniform_hemisphere": 4, "cosine_hemisphere": 5, "beckmann": 6}
+TEXTURE_NAMES = {"image": 0, "checkerboard": 1}
+TEXTURE_FILTER_NAMES = {"nearest": 0, "bilinear": 1}
+TEXTURE_WRAP_NAMES = {"repeat": 0, "clamp": 1}
 SEED_PER_SAMPLE, SEED_NORI_BLOCK = 0, 1
 MEASURE_UNKNOWN, MEASURE_SOLID_ANGLE, MEASURE_DISCRETE = 0, 1, 2
 NO_HIT = 0xFFFFFFFF
@@ -45,7 +48,14 @@ class MeshDesc(C.Structure):
     _fields_ = [("n_vertices", C.c_uint32), ("n_triangles", C.c_uint32),
                 ("positions", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)),
                 ("texcoords", C.POINTER(C.c_float)), ("indices", C.POINTER(C.c_uint32)),
-                ("bsdf", BsdfDesc), ("is_emitter", C.c_int32), ("radiance", C.c_float * 3)]
+                ("bsdf", BsdfDesc), ("is_emitter", C.c_int32), ("radiance", C.c_float * 3),
+                ("albedo_texture", C.c_uint32)]
+
+
+class TextureDesc(C.Structure):
+    _fields_ = [("type", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32), ("texels", C.POINTER(C.c_float)),
+                ("filter", C.c_int32), ("wrap", C.c_int32), ("uscale", C.c_float), ("vscale", C.c_float),
+                ("uoffset", C.c_float), ("voffset", C.c_float), ("color0", C.c_float * 3), ("color1", C.c_float * 3)]
 
 
 class CameraDesc(C.Structure):
@@ -65,7 +75,8 @@ class IntegratorDesc(C.Structure):
 class SceneDesc(C.Structure):
     _fields_ = [("n_meshes", C.c_uint32), ("meshes", C.POINTER(MeshDesc)),
                 ("camera", CameraDesc), ("rfilter", RFilterDesc),
-                ("integrator", IntegratorDesc), ("sample_count", C.c_int32)]
+                ("integrator", IntegratorDesc), ("sample_count", C.c_int32),
+                ("n_textures", C.c_uint32), ("textures", C.POINTER(TextureDesc))]
 
 
 class RenderParams(C.Structure):
@@ -111,7 +122,7 @@ assert RAY_DTYPE.itemsize == 32 and ITS_DTYPE.itemsize == 104
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
 
-HIP_ABI_VERSION = 7      # NORI_HIP_ABI_VERSION of the include/nori_hip.h these ctypes structs mirror
+HIP_ABI_VERSION = 8      # NORI_HIP_ABI_VERSION of the include/nori_hip.h these ctypes structs mirror
 
 #: every symbol include/nori_hip.h declares -> (restype, argtypes)
 HIP_PROTOTYPES = {
@@ -120,6 +131,7 @@ HIP_PROTOTYPES = {
     "nori_hip_destroy": (None, [_P]),
     "nori_hip_last_error": (C.c_char_p, [_P]),
     "nori_hip_upload_scene": (C.c_int, [_P, C.POINTER(SceneDesc)]),
+    "nori_hip_texture_eval": (C.c_int, [_P, C.c_uint32, _P, C.c_size_t, _P]),
     "nori_hip_build_accel": (C.c_int, [_P, C.c_int]),
     "nori_hip_accel_info": (C.c_int, [_P, C.POINTER(AccelInfo)]),
     "nori_hip_debug_excursions": (C.c_int, [_P, _P, C.c_int]),

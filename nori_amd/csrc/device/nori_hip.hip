@@ -80,7 +80,8 @@ struct RenderArgs {
     uint32_t th_shade, th_inner, th_leaf;   /* lanes of a wave that must want a kind of work for it to run */
 };
 
-template <int INTEG, int STACK, bool COUNT>
+/* MATSET = kAnyBsdf | kTextured (rt_path.h): the kernel of scenes with textured albedos; kAnyBsdf: every other scene */
+template <int INTEG, int STACK, bool COUNT, int MATSET = kAnyBsdf>
 __global__ __launch_bounds__(kBlock, NORI_RENDER_MIN_WAVES) void render_kernel(DevScene sc, RenderArgs args, FilmStore film,
                                                         unsigned long long *stats) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -150,7 +151,7 @@ __global__ __launch_bounds__(kBlock, NORI_RENDER_MIN_WAVES) void render_kernel(D
             if (!gen) {
                 bool done;
                 if (st.phase == PH_SHADOW) done = path_on_shadow(st, tv.hit.tri != kNoHit, tv.o);
-                else done = path_on_closest<INTEG>(sc, st, tv.hit, tv.hit.tri != kNoHit, tv.d);
+                else done = path_on_closest<INTEG, MATSET>(sc, st, tv.hit, tv.hit.tri != kNoHit, tv.d);
                 if (done) {
                     /* block.put(pixelSample, value), src/main.cpp:52: the sample goes to the film's
                        store (20 B); film_gather applies the reconstruction filter afterwards */
@@ -228,7 +229,7 @@ __global__ __launch_bounds__(kBlock) void intersect_kernel(DevScene sc, const no
     }
 }
 
-template <int INTEG, int STACK>
+template <int INTEG, int STACK, int MATSET = kAnyBsdf>
 __global__ __launch_bounds__(kBlock) void li_kernel(DevScene sc, const nori_ray *rays, size_t n,
                                                     const uint64_t *seed_state, const uint64_t *seed_seq, float *rgb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -247,7 +248,7 @@ __global__ __launch_bounds__(kBlock) void li_kernel(DevScene sc, const nori_ray 
             Hit hit;
             const f3 qo = st.ray.o, qd = st.ray.d;
             const bool found = traverse<false>(sc, st.ray, any, stack, hit, tc);
-            const bool done = any ? path_on_shadow(st, found, qo) : path_on_closest<INTEG>(sc, st, hit, found, qd);
+            const bool done = any ? path_on_shadow(st, found, qo) : path_on_closest<INTEG, MATSET>(sc, st, hit, found, qd);
             if (done) break;
         }
         rgb[3 * i] = st.L.x; rgb[3 * i + 1] = st.L.y; rgb[3 * i + 2] = st.L.z;
@@ -263,7 +264,7 @@ __global__ __launch_bounds__(kBlock) void li_kernel(DevScene sc, const nori_ray 
    oracle in its native seeding, not for throughput.  Samples go to the film's store like everywhere else. */
 constexpr int kNoriBlock = 32;        /* NORI_BLOCK_SIZE, include/nori/block.h:17 */
 
-template <int INTEG, int STACK>
+template <int INTEG, int STACK, int MATSET = kAnyBsdf>
 __global__ __launch_bounds__(64) void render_block_serial_kernel(DevScene sc, uint32_t blocks_x, uint32_t n_blocks, uint32_t spp,
                                                                  uint32_t tiles_x, FilmStore film, unsigned long long *stats) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -295,7 +296,7 @@ __global__ __launch_bounds__(64) void render_block_serial_kernel(DevScene sc, ui
                         const f3 qo = st.ray.o, qd = st.ray.d;
                         if (any) ++nShadow; else ++nClosest;
                         const bool found = traverse<false>(sc, st.ray, any, stack, hit, tc);
-                        const bool done = any ? path_on_shadow(st, found, qo) : path_on_closest<INTEG>(sc, st, hit, found, qd);
+                        const bool done = any ? path_on_shadow(st, found, qo) : path_on_closest<INTEG, MATSET>(sc, st, hit, found, qd);
                         if (done) break;
                     }
                     rng = st.rng;                                  /* the stream goes on where Li left it */
@@ -338,6 +339,13 @@ __global__ void bsdf_kernel(Bsdf b, int op, const float *wi, const float *wo_in,
         if (op == 1) { const f3 v = bsdf_eval(b, a, o); value[3 * i] = v.x; value[3 * i + 1] = v.y; value[3 * i + 2] = v.z; }
         else value[i] = bsdf_pdf(b, a, o);
     }
+}
+
+__global__ void texture_eval_kernel(const TexRec *textures, const f4 *texels, uint32_t k, const float *uv, size_t n, float *rgb) {
+    const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f3 c = texture_lookup(textures[k], texels, mk2(uv[2 * i], uv[2 * i + 1]));
+    rgb[3 * i] = c.x; rgb[3 * i + 1] = c.y; rgb[3 * i + 2] = c.z;
 }
 
 __global__ void warp_kernel(int warp, float param, int pdf, const float *in, size_t n, float *out) {
@@ -570,6 +578,12 @@ int nori_hip_upload_scene(nori_hip_ctx *ctx, const nori_scene_desc *scene) {
     d.n_triangles = (uint32_t) h.tri_mesh.size();
     d.n_cdf = (uint32_t) h.emitter_cdf.size();
     d.camera = h.camera; d.filter = h.filter; d.integrator = h.integrator;
+    if (!h.textures.empty()) {      /* (scenes without textures allocate nothing and keep null pointers) */
+        if ((rc = upload(ctx, ctx->allocs_scene, h.textures, &d.textures))) return rc;
+        if ((rc = upload(ctx, ctx->allocs_scene, h.texels, &d.texels))) return rc;
+        d.n_textures = (uint32_t) h.textures.size();
+        d.textured = h.textured ? 1u : 0u;
+    }
     ctx->have_scene = true;
     return NORI_OK;
 }
@@ -841,7 +855,10 @@ static void launch_li(nori_hip_ctx *ctx, const nori_ray *r, size_t n, const uint
     const size_t lds = STACK * kBlock * sizeof(int);
     switch (ctx->dev.integrator.type) {
 #define LI_CASE(I) case I: hipLaunchKernelGGL((li_kernel<I, STACK>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); break;
-        LI_CASE(0) LI_CASE(1) LI_CASE(2) LI_CASE(3) LI_CASE(4) LI_CASE(5) LI_CASE(6)
+#define LI_TEX(I) case I: if (ctx->dev.textured) { hipLaunchKernelGGL((li_kernel<I, STACK, kAnyBsdf | kTextured>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } \
+                          else { hipLaunchKernelGGL((li_kernel<I, STACK>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } break;
+        LI_CASE(0) LI_CASE(1) LI_CASE(2) LI_TEX(3) LI_TEX(4) LI_TEX(5) LI_TEX(6)
+#undef LI_TEX
 #undef LI_CASE
     }
 }
@@ -911,6 +928,26 @@ int nori_hip_bsdf_eval(nori_hip_ctx *ctx, const nori_bsdf_desc *bsdf, const floa
 int nori_hip_bsdf_pdf(nori_hip_ctx *ctx, const nori_bsdf_desc *bsdf, const float *wi, const float *wo, size_t n, float *pdf) {
     if (!wo || !pdf) return NORI_ERR_INVALID_ARGUMENT;
     return bsdf_call(ctx, bsdf, 2, wi, wo, nullptr, n, nullptr, pdf, nullptr, nullptr);
+}
+
+int nori_hip_texture_eval(nori_hip_ctx *ctx, uint32_t texture, const float *uv, size_t n, float *rgb) {
+    if (!ctx) return NORI_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_scene) { ctx->error = "texture_eval: no scene uploaded"; return NORI_ERR_NOT_READY; }
+    if (texture == 0 || texture > ctx->dev.n_textures) {
+        ctx->error = "texture_eval: texture " + std::to_string(texture) + " is out of range (the scene has " + std::to_string(ctx->dev.n_textures) +
+                     " textures, numbered from 1)";
+        return NORI_ERR_INVALID_ARGUMENT;
+    }
+    if (n == 0) return NORI_OK;
+    if (!uv || !rgb) return NORI_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    SCRATCH_IN(ctx, din, uv, n * 2 * sizeof(float));
+    SCRATCH_OUT(ctx, dout, n * 3 * sizeof(float));
+    hipLaunchKernelGGL(texture_eval_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, ctx->dev.textures, ctx->dev.texels, texture - 1u,
+                       (const float *) din.p, n, (float *) dout.p);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpy(rgb, dout.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return NORI_OK;
 }
 
 int nori_hip_warp(nori_hip_ctx *ctx, int warp, float param, const float *sample, size_t n, float *out) {
@@ -987,6 +1024,10 @@ template <int INTEG, int STACK, bool COUNT>
 static hipError_t launch_render_one(nori_hip_ctx *ctx, const RenderArgs &a, const FilmStore &film, hipStream_t s) {
     const size_t lds = render_lds_bytes<STACK>(a);
     auto kern = render_kernel<INTEG, STACK, COUNT>;
+    /* integrators that ask a BSDF have a kernel for scenes with textured albedos (rt_path.h, kTextured) */
+    if constexpr (INTEG >= INT_WHITTED) {
+        if (ctx->dev.textured) kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured>;
+    }
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         if (e != hipSuccess) return e;
@@ -1102,10 +1143,14 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
         const uint32_t need = ctx->bvh.max_depth + 1;
         timer.begin(KC_TRACE, s);
         switch (ctx->dev.integrator.type) {
-#define SB(I) case I: if (need <= 32) hipLaunchKernelGGL((render_block_serial_kernel<I, 32>), dim3((n_blocks + 63) / 64), dim3(64), 32 * 64 * sizeof(int), s, ctx->dev, bx, n_blocks, a.spp_count, a.tiles_x, film, ctx->d_stats); \
-                      else hipLaunchKernelGGL((render_block_serial_kernel<I, 64>), dim3((n_blocks + 63) / 64), dim3(64), 64 * 64 * sizeof(int), s, ctx->dev, bx, n_blocks, a.spp_count, a.tiles_x, film, ctx->d_stats); break;
-            SB(0) SB(1) SB(2) SB(3) SB(4) SB(5) SB(6)
+#define SB2(I, M) if (need <= 32) hipLaunchKernelGGL((render_block_serial_kernel<I, 32, M>), dim3((n_blocks + 63) / 64), dim3(64), 32 * 64 * sizeof(int), s, ctx->dev, bx, n_blocks, a.spp_count, a.tiles_x, film, ctx->d_stats); \
+                          else hipLaunchKernelGGL((render_block_serial_kernel<I, 64, M>), dim3((n_blocks + 63) / 64), dim3(64), 64 * 64 * sizeof(int), s, ctx->dev, bx, n_blocks, a.spp_count, a.tiles_x, film, ctx->d_stats);
+#define SB(I) case I: SB2(I, kAnyBsdf) break;
+#define SBT(I) case I: if (ctx->dev.textured) { SB2(I, kAnyBsdf | kTextured) } else { SB2(I, kAnyBsdf) } break;
+            SB(0) SB(1) SB(2) SBT(3) SBT(4) SBT(5) SBT(6)
+#undef SBT
 #undef SB
+#undef SB2
         }
         timer.end(s);
         HIP_TRY(ctx, hipGetLastError());

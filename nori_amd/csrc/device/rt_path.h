@@ -17,6 +17,7 @@
  */
 #pragma once
 #include "rt_sampling.h"
+#include "rt_texture.h"
 #include "rt_trace.h"
 
 namespace nrt {
@@ -152,8 +153,11 @@ NORI_HD void surface_from_record(bool has_normals, float u, float v, f3 p0, f3 p
 
 /* MATSET: the BSDF types the scene contains, bit t = nori_bsdf_type t (DevScene::bsdf_mask).  A kernel instantiated for a
    subset never compiles the other BSDFs' sample / eval / pdf (include/nori/bsdf.h:59-87): wf_shade of an all-diffuse scene
-   (src/diffuse.cpp:23-71) is a smaller kernel with more waves per SIMD.  kAnyBsdf: every type. */
+   (src/diffuse.cpp:23-71) is a smaller kernel with more waves per SIMD.  kAnyBsdf: every type.
+   kTextured (bit 4): the kernel reads the albedo of a textured diffuse mesh from its texture (rt_texture.h) at the hit's uv;
+   without the bit no texture code is compiled -- the kernels of scenes without textures are the kernels of before. */
 constexpr int kAnyBsdf = 0xf;
+constexpr int kTextured = 0x10;
 template <int MATSET> NORI_HD int32_t bsdf_type_in_set(int32_t type) {
     if (MATSET == 1) return 0;                                      /* diffuse only: a constant */
     if (MATSET == 8) return 3;
@@ -204,6 +208,8 @@ NORI_HD bool path_on_closest(const DevScene &sc, const Tab &tab, PathState &st, 
     const f3 rad = mk3(m.radiance[0], m.radiance[1], m.radiance[2]);
     Bsdf bsdf = bsdf_from_mesh(m);
     bsdf.type = bsdf_type_in_set<MATSET>(bsdf.type);
+    if ((MATSET & kTextured) && (m.flags & kMeshTextured))      /* the albedo of bsdf_eval / pdf / sample and sample_direct alike */
+        bsdf.albedo = texture_lookup(sc.textures[m.pad[0] - 1u], sc.texels, hit_uv(sc, m.flags, hit));
     const f3 wi = to_local(fr, -d);
 
     if (INTEG == INT_WHITTED) {
@@ -288,10 +294,10 @@ NORI_HD bool path_on_closest(const DevScene &sc, const Tab &tab, PathState &st, 
 }
 
 /* (every engine but wf_shade: the tables behind DevScene's pointers) */
-template <int INTEG>
+template <int INTEG, int MATSET = kAnyBsdf>
 NORI_HD bool path_on_closest(const DevScene &sc, PathState &st, const Hit &hit, bool found, const f3 d) {
     const SceneTables tab = {&sc};
-    return path_on_closest<INTEG>(sc, tab, st, hit, found, d);
+    return path_on_closest<INTEG, SceneTables, MATSET>(sc, tab, st, hit, found, d);
 }
 
 /* Consume the result of a shadow query (`o` = origin of the shadow ray, which

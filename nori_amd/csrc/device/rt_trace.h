@@ -440,6 +440,18 @@ struct Surface {
     f3 ns;       /* its.shFrame.n, accel.cpp:82-95 */
 };
 
+/* its.uv: the mesh's texture coordinates interpolated with the barycentrics (src/accel.cpp:73-77), or the barycentric (u, v)
+ * where the mesh has none (:38).  One formula for nori_hip_intersect (surface_fill) and the texture lookup of the shading. */
+NORI_HD f2 hit_uv(const DevScene &sc, uint32_t mesh_flags, const Hit &h) {
+    if (mesh_flags & kMeshHasUV) {
+        const float b0 = 1.0f - (h.u + h.v), b1 = h.u, b2 = h.v;
+        const uint32_t *idx = sc.indices + 3 * (size_t) h.tri;
+        const f2 a = sc.texcoords[idx[0]], b = sc.texcoords[idx[1]], c = sc.texcoords[idx[2]];
+        return mk2((b0 * a.x + b1 * b.x) + b2 * c.x, (b0 * a.y + b1 * b.y) + b2 * c.y);
+    }
+    return mk2(h.u, h.v);
+}
+
 /* src/accel.cpp:45-96 -- barycentric position and shading normal, from the triangle's
  * pre-gathered shading record (rt_types.h) */
 NORI_HD void surface_fill(const DevScene &sc, const Hit &h, Surface &s, f3 *geo_n, f2 *uv_out) {
@@ -458,15 +470,7 @@ NORI_HD void surface_fill(const DevScene &sc, const Hit &h, Surface &s, f3 *geo_
     } else {
         s.ns = ng;
     }
-    if (uv_out) {
-        if (m.flags & kMeshHasUV) {
-            const uint32_t *idx = sc.indices + 3 * (size_t) h.tri;
-            const f2 a = sc.texcoords[idx[0]], b = sc.texcoords[idx[1]], c = sc.texcoords[idx[2]];
-            *uv_out = mk2((b0 * a.x + b1 * b.x) + b2 * c.x, (b0 * a.y + b1 * b.y) + b2 * c.y);
-        } else {
-            *uv_out = mk2(h.u, h.v);
-        }
-    }
+    if (uv_out) *uv_out = hit_uv(sc, m.flags, h);
 }
 
 /* PerspectiveCamera::sampleRay, src/perspective.cpp:76-97 */

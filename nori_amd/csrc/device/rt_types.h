@@ -299,16 +299,19 @@ struct MeshRec {
     uint32_t tri_offset;      /* first global triangle                */
     uint32_t vtx_offset;      /* first global vertex                  */
     uint32_t n_triangles;
-    uint32_t flags;           /* bit0 normals, bit1 uv, bit2 emitter  */
+    uint32_t flags;           /* bit0 normals, bit1 uv, bit2 emitter, bit3 textured albedo */
     int32_t bsdf_type;
     float albedo[3];          /* diffuse albedo / microfacet kd       */
     float alpha, int_ior, ext_ior, ks;
     float radiance[3];
     float inv_area;           /* DiscretePDF::getNormalization()      */
     uint32_t cdf_offset;      /* into emitter_cdf (n_triangles+1)     */
-    uint32_t pad[3];
+    uint32_t pad[3];          /* pad[0]: 1-based texture of a textured mesh (rt_texture.h), else 0 */
 };
-constexpr uint32_t kMeshHasNormals = 1u, kMeshHasUV = 2u, kMeshEmitter = 4u;
+constexpr uint32_t kMeshHasNormals = 1u, kMeshHasUV = 2u, kMeshEmitter = 4u, kMeshTextured = 8u;
+static_assert(sizeof(MeshRec) == 80, "the LDS shade tables (shade_tables.h) hold 80-B mesh records");
+
+struct TexRec;
 
 struct CameraRec {
     float sample_to_camera[16];   /* row-major */
@@ -362,6 +365,11 @@ struct DevScene {
     CameraRec camera;
     FilterRec filter;
     IntegratorRec integrator;
+    /* albedo textures (rt_texture.h); null / 0 in scenes without them, which never read these */
+    const TexRec *textures;
+    const f4 *texels;
+    uint32_t n_textures;
+    uint32_t textured;          /* some mesh has a textured albedo: the kernels compiled with kTextured run (rt_path.h) */
 };
 
 struct Hit {

@@ -80,6 +80,35 @@ std::string prepare_scene(const nori_scene_desc &desc, HostScene &out) {
     if (desc.sample_count < 0) return "negative sample count";
     out.sample_count = desc.sample_count;
 
+    if (desc.n_textures > 0 && !desc.textures) return "scene has textures == NULL";
+    for (uint32_t k = 0; k < desc.n_textures; ++k) {
+        const nori_texture_desc &t = desc.textures[k];
+        const std::string name = "texture " + std::to_string(k + 1) + ": ";
+        if (t.type != NORI_TEXTURE_IMAGE && t.type != NORI_TEXTURE_CHECKERBOARD) return name + "unknown type " + std::to_string(t.type);
+        if (t.filter != NORI_FILTER_NEAREST && t.filter != NORI_FILTER_BILINEAR) return name + "unknown filter " + std::to_string(t.filter);
+        if (t.wrap != NORI_WRAP_REPEAT && t.wrap != NORI_WRAP_CLAMP) return name + "unknown wrap mode " + std::to_string(t.wrap);
+        TexRec r; std::memset(&r, 0, sizeof(r));
+        r.type = (uint32_t) t.type;
+        r.uscale = t.uscale; r.vscale = t.vscale; r.uoffset = t.uoffset; r.voffset = t.voffset;
+        for (int c = 0; c < 3; ++c) { r.color0[c] = t.color0[c]; r.color1[c] = t.color1[c]; }
+        r.bilinear = t.filter == NORI_FILTER_BILINEAR ? 1u : 0u;
+        r.clamp = t.wrap == NORI_WRAP_CLAMP ? 1u : 0u;
+        if (t.type == NORI_TEXTURE_IMAGE) {
+            if (!t.texels) return name + "image texture with texels == NULL";
+            if (t.width == 0 || t.height == 0 || t.width > kTexMaxDim || t.height > kTexMaxDim)
+                return name + "image of " + std::to_string(t.width) + " x " + std::to_string(t.height) + " texels (each dimension must be 1 .. " +
+                       std::to_string(kTexMaxDim) + ")";
+            const size_t n = (size_t) t.width * t.height;
+            if (out.texels.size() + n >= (1ull << 32)) return name + "too many texels in the scene (limit 2^32)";
+            r.width = t.width; r.height = t.height;
+            r.texel_offset = (uint32_t) out.texels.size();
+            out.texels.resize(out.texels.size() + n);
+            f4 *dst = &out.texels[r.texel_offset];
+            for (size_t i = 0; i < n; ++i) { dst[i].x = t.texels[3 * i]; dst[i].y = t.texels[3 * i + 1]; dst[i].z = t.texels[3 * i + 2]; dst[i].w = 0.0f; }
+        }
+        out.textures.push_back(r);
+    }
+
     uint64_t nV = 0, nT = 0;
     for (uint32_t i = 0; i < desc.n_meshes; ++i) { nV += desc.meshes[i].n_vertices; nT += desc.meshes[i].n_triangles; }
     if (nT >= (1ull << 28)) return "too many triangles (limit 2^28)";
@@ -98,6 +127,15 @@ std::string prepare_scene(const nori_scene_desc &desc, HostScene &out) {
         if (rec.bsdf_type < 0 || rec.bsdf_type > 3) return "unknown BSDF type";
         for (int k = 0; k < 3; ++k) { rec.albedo[k] = m.bsdf.albedo[k]; rec.radiance[k] = m.radiance[k]; }
         rec.alpha = m.bsdf.alpha; rec.int_ior = m.bsdf.int_ior; rec.ext_ior = m.bsdf.ext_ior; rec.ks = m.bsdf.ks;
+        if (m.albedo_texture != 0u) {
+            if (m.albedo_texture > desc.n_textures)
+                return "mesh " + std::to_string(mi) + ": albedo_texture " + std::to_string(m.albedo_texture) + " is out of range (the scene has " +
+                       std::to_string(desc.n_textures) + " textures, numbered from 1)";
+            if (m.bsdf.type != NORI_BSDF_DIFFUSE) return "mesh " + std::to_string(mi) + ": a texture on a BSDF that is not diffuse (only a diffuse albedo can be textured)";
+            rec.flags |= kMeshTextured;
+            rec.pad[0] = m.albedo_texture;
+            out.textured = true;
+        }
         for (uint32_t v = 0; v < m.n_vertices; ++v) {
             f4 p; p.x = m.positions[3 * v]; p.y = m.positions[3 * v + 1]; p.z = m.positions[3 * v + 2]; p.w = 0.0f;
             out.positions[vOff + v] = p;

@@ -9,6 +9,7 @@
 
 #include "../../../include/nori_hip.h"
 #include "rt_types.h"
+#include "rt_texture.h"
 
 namespace nrt {
 
@@ -26,6 +27,9 @@ struct HostScene {
     IntegratorRec integrator;
     int32_t sample_count = 1;
     bool has_uv = false;
+    std::vector<TexRec> textures;       /* nori_texture_desc, one record each (rt_texture.h) */
+    std::vector<f4> texels;             /* every image texture's texels, RGBA (A = 0) */
+    bool textured = false;              /* some mesh's albedo is a texture */
 };
 
 struct HostBvh {

@@ -858,7 +858,7 @@ __global__ __launch_bounds__(kSB, NORI_SHADE_WGS) void wf_shade(DevScene sc, WfB
    scene 22 -> 19 ms per tail on all CUs, 223 -> 80 ms on 16 CUs, where the tail of a batch runs when the NEXT batch runs beside it:
    what it costs there is CU time, not the length of the longest path.  profiles/r5_06_tail_probe_c4.txt.)  Same arithmetic per
    path, hence the same radiance; which lane walks a path is not observable. */
-template <int INTEG>
+template <int INTEG, int MATSET = kAnyBsdf>      /* kAnyBsdf | kTextured: scenes with textured albedos (rt_path.h) */
 __global__ __launch_bounds__(kB) void wf_finish(DevScene sc, WfBuf b, int cur, WfBatch bt, int count) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     LdsStackW<16, true> stack;
@@ -914,7 +914,7 @@ __global__ __launch_bounds__(kB) void wf_finish(DevScene sc, WfBuf b, int cur, W
                 if (found) hit.mesh = f2u(sc.shade_tris[(size_t) hit.tri * kShadeQuads].w);
                 PathState st;
                 vertex_unpack(st, fl, L, T, rng_state, ((uint64_t) (bt.s_first + ((sidx % per_tile) >> 8)) << 1u) | 1u);
-                fin = path_on_closest<INTEG>(sc, st, hit, found, ray.d);
+                fin = path_on_closest<INTEG, MATSET>(sc, st, hit, found, ray.d);
                 L.x = st.L.x; L.y = st.L.y; L.z = st.L.z;
                 if (!fin) { vertex_pack(st, o, dA, dB, T, L, Ld, fl); rng_state = st.rng.state; }
             }
@@ -1070,10 +1070,12 @@ void launch_shade(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt
        microfacet BSDF, any scene; integrators that never ask a BSDF (normals, ao, simple) have one kernel */
     int matset = sc.integrator.type < INT_WHITTED ? kAnyBsdf : sc.bsdf_mask == 1u ? 1 : (sc.bsdf_mask & 8u) == 0u ? 7 : kAnyBsdf;
     if (getenv("NORI_HIP_SHADE_ANY_BSDF")) matset = kAnyBsdf;      /* A/B: the general kernel whatever the scene holds */
+    if (sc.integrator.type >= INT_WHITTED && sc.textured) matset = kAnyBsdf | kTextured;      /* textured albedos: one set, every BSDF */
     switch (sc.integrator.type) {
 #define SH3(I, F, M) if (lds_tables) hipLaunchKernelGGL((wf_shade<I, F, true, M>), grid, block, 0, s, sc, b, cur, bt); \
                      else hipLaunchKernelGGL((wf_shade<I, F, false, M>), grid, block, 0, s, sc, b, cur, bt)
-#define SH2(I, F) if (matset == 1) { SH3(I, F, 1); } else if (matset == 7) { SH3(I, F, 7); } else { SH3(I, F, kAnyBsdf); }
+#define SH2(I, F) if (matset == 1) { SH3(I, F, 1); } else if (matset == 7) { SH3(I, F, 7); } else if (matset == kAnyBsdf) { SH3(I, F, kAnyBsdf); } \
+                  else { SH3(I, F, kAnyBsdf | kTextured); }
 #define SH1(I, F) SH3(I, F, kAnyBsdf)
 #define SH(I, W) case I: if (mode == kFreshOnly) { W(I, kFreshOnly); } else if (mode == kMixed) { W(I, kMixed); } else { W(I, kStoredOnly); } break;
         SH(0, SH1) SH(1, SH1) SH(2, SH1) SH(3, SH2) SH(4, SH2) SH(5, SH2) SH(6, SH2)
@@ -1089,7 +1091,10 @@ void launch_finish(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &b
     const size_t lds = (size_t) LdsStackW<16, true>::kLdsEntries * kB * sizeof(int);
     switch (sc.integrator.type) {
 #define FN(I) case I: hipLaunchKernelGGL((wf_finish<I>), grid, block, lds, s, sc, b, cur, bt, (int) count); break;
-        FN(0) FN(1) FN(2) FN(3) FN(4) FN(5) FN(6)
+#define FNT(I) case I: if (sc.textured) { hipLaunchKernelGGL((wf_finish<I, kAnyBsdf | kTextured>), grid, block, lds, s, sc, b, cur, bt, (int) count); } \
+                       else { hipLaunchKernelGGL((wf_finish<I>), grid, block, lds, s, sc, b, cur, bt, (int) count); } break;
+        FN(0) FN(1) FN(2) FNT(3) FNT(4) FNT(5) FNT(6)
+#undef FNT
 #undef FN
     }
 }

@@ -16,7 +16,9 @@ class NoriObject {
 public:
     enum EClassType {
         EScene = 0, EMesh, EBSDF, EPhaseFunction, EEmitter, EMedium, ECamera,
-        EIntegrator, ESampler, ETest, EReconstructionFilter, EClassTypeCount
+        EIntegrator, ESampler, ETest, EReconstructionFilter,
+        ETexture,      /* (appended: the values above keep their numbers) */
+        EClassTypeCount
     };
     virtual ~NoriObject() {}
     virtual EClassType getClassType() const = 0;
@@ -38,6 +40,7 @@ public:
         case EIntegrator: return "integrator";
         case ESampler: return "sampler";
         case ETest: return "test";
+        case ETexture: return "texture";
         default: return "<unknown>";
         }
     }

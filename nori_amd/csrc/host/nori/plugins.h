@@ -56,9 +56,22 @@ struct BSDFQueryRecord {
     BSDFQueryRecord(const Vector3f &wi_, const Vector3f &wo_, EMeasure m) : wi(wi_), wo(wo_), eta(1.f), measure(m) {}
 };
 
+/* ---------------------------------------------------------------- Texture */
+/* An albedo texture (no counterpart in the reference; texture.cpp): `image` (PNG or OpenEXR file) or `checkerboard`,
+   flattened into nori_texture_desc.  The object owns its texels. */
+class Texture : public NoriObject {
+public:
+    EClassType getClassType() const { return ETexture; }
+    virtual void fill(nori_texture_desc &d) const = 0;
+};
+
 /* include/nori/bsdf.h:43-101 */
 class BSDF : public NoriObject {
 public:
+    /* a <texture> child: only Diffuse takes one (as its albedo) */
+    virtual void addChild(NoriObject *child);
+    /* the texture that gives the albedo, or null */
+    virtual const Texture *albedoTexture() const { return nullptr; }
     virtual Color3f sample(BSDFQueryRecord &bRec, const Point2f &sample) const;
     virtual Color3f eval(const BSDFQueryRecord &bRec) const;
     virtual float pdf(const BSDFQueryRecord &bRec) const;
@@ -242,6 +255,7 @@ private:
     Accel *m_accel = nullptr;
     mutable nori_scene_desc m_desc;
     mutable std::vector<nori_mesh_desc> m_meshDescs;
+    mutable std::vector<nori_texture_desc> m_textureDescs;
     mutable bool m_descValid = false;
     mutable std::unique_ptr<Device> m_device;
     mutable std::unique_ptr<DeviceGroup> m_group;

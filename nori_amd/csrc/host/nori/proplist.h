@@ -27,6 +27,7 @@ public:
 #undef NORI_PROP
     /* Vector3f and Point3f are one C++ type here but distinct property kinds,
        as <vector> and <point> are in the scene format (parser.cpp:93-94) */
+    bool has(const std::string &name) const { return m_properties.count(name) != 0; }
     void setVector(const std::string &name, const Vector3f &value);
     Vector3f getVector(const std::string &name) const;
     Vector3f getVector(const std::string &name, const Vector3f &defaultValue) const;

@@ -1,7 +1,7 @@
 /*
  * parser.cpp -- loadFromXML: builds the NoriObject graph from a scene file.
  * Grammar and checks of the reference's src/parser.cpp:16-305: the 11 object
- * tags and 13 property / transform tags (parser.cpp:79-102), exact attribute
+ * tags (plus <texture>, an extension: the albedo of a diffuse BSDF, texture.cpp) and 13 property / transform tags (parser.cpp:79-102), exact attribute
  * sets per tag (:105-116), structural rules (:140-157), children constructed
  * before their parent, then addChild + setParent in document order, then
  * activate() (:166-199); transform operations LEFT-multiply the running
@@ -28,6 +28,7 @@ const std::map<std::string, int> &tagTable() {
         {"emitter", NoriObject::EEmitter}, {"camera", NoriObject::ECamera}, {"medium", NoriObject::EMedium},
         {"phase", NoriObject::EPhaseFunction}, {"integrator", NoriObject::EIntegrator},
         {"sampler", NoriObject::ESampler}, {"rfilter", NoriObject::EReconstructionFilter}, {"test", NoriObject::ETest},
+        {"texture", NoriObject::ETexture},
         {"boolean", EBoolean}, {"integer", EInteger}, {"float", EFloat}, {"string", EString}, {"point", EPoint},
         {"vector", EVector}, {"color", EColor}, {"transform", ETransform}, {"translate", ETranslate},
         {"matrix", EMatrix}, {"rotate", ERotate}, {"scale", EScale}, {"lookat", ELookAt}};
@@ -99,7 +100,14 @@ struct Parser {
         NoriObject *result = nullptr;
         try {
             if (currentIsObject) {
-                checkAttributes(node, {"type"});
+                if (tag == NoriObject::ETexture && node.attribute("name")) {
+                    /* <texture name="albedo">: the slot it fills (the only one there is) */
+                    checkAttributes(node, {"type", "name"});
+                    if (attr(node, "name") != "albedo")
+                        throw NoriException("a <texture> can only be named \"albedo\" (got \"%s\")", attr(node, "name"));
+                } else {
+                    checkAttributes(node, {"type"});
+                }
                 result = NoriObjectFactory::createInstance(attr(node, "type"), propList);
                 if (result->getClassType() != (int) tag)
                     throw NoriException("Unexpectedly constructed an object of type <%s> (expected type <%s>): %s",

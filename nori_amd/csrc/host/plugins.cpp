@@ -91,14 +91,36 @@ float BSDF::pdf(const BSDFQueryRecord &bRec) const {
 
 static void clearDesc(nori_bsdf_desc &d, int type) { std::memset(&d, 0, sizeof(d)); d.type = type; }
 
+void BSDF::addChild(NoriObject *child) {
+    if (child->getClassType() == ETexture) {
+        const std::string s = toString();
+        throw NoriException("a <texture> can only be the albedo of a diffuse BSDF, not of %s", s.substr(0, s.find('[')));
+    }
+    NoriObject::addChild(child);
+}
+
 class Diffuse : public BSDF {
 public:
-    Diffuse(const PropertyList &propList) { m_albedo = propList.getColor("albedo", Color3f(0.5f)); }
+    Diffuse(const PropertyList &propList) {
+        m_albedo = propList.getColor("albedo", Color3f(0.5f));
+        m_hasAlbedo = propList.has("albedo");
+    }
+    ~Diffuse() { delete m_texture; }
     bool isDiffuse() const { return true; }
+    /* <texture name="albedo"> in place of <color name="albedo"> */
+    void addChild(NoriObject *child) {
+        if (child->getClassType() != ETexture) { BSDF::addChild(child); return; }
+        if (m_hasAlbedo) throw NoriException("a diffuse BSDF cannot have both an albedo color and an albedo texture");
+        if (m_texture) throw NoriException("a diffuse BSDF can only have one albedo texture");
+        m_texture = static_cast<Texture *>(child);
+    }
+    const Texture *albedoTexture() const { return m_texture; }
     void fill(nori_bsdf_desc &d) const { clearDesc(d, NORI_BSDF_DIFFUSE); for (int i = 0; i < 3; ++i) d.albedo[i] = m_albedo[i]; }
-    std::string toString() const { return format("Diffuse[\n  albedo = %s\n]", m_albedo.toString()); }
+    std::string toString() const { return format("Diffuse[\n  albedo = %s\n]", m_texture ? indent(m_texture->toString()) : m_albedo.toString()); }
 private:
     Color3f m_albedo;
+    bool m_hasAlbedo = false;
+    Texture *m_texture = nullptr;
 };
 
 class Mirror : public BSDF {
@@ -538,6 +560,18 @@ const nori_scene_desc &Scene::getDesc() const {
         m_camera->getReconstructionFilter()->fill(m_desc.rfilter);
         m_integrator->fill(m_desc.integrator);
         m_desc.sample_count = (int32_t) m_sampler->getSampleCount();
+        /* albedo textures: one record per texture object, referenced 1-based by the meshes (the objects own the texels) */
+        std::vector<const Texture *> textures;
+        m_textureDescs.clear();
+        for (size_t i = 0; i < m_meshes.size(); ++i) {
+            const Texture *t = m_meshes[i]->getBSDF()->albedoTexture();
+            if (!t) continue;
+            size_t k = std::find(textures.begin(), textures.end(), t) - textures.begin();
+            if (k == textures.size()) { textures.push_back(t); m_textureDescs.emplace_back(); t->fill(m_textureDescs.back()); }
+            m_meshDescs[i].albedo_texture = (uint32_t) k + 1u;
+        }
+        m_desc.n_textures = (uint32_t) m_textureDescs.size();
+        m_desc.textures = m_textureDescs.empty() ? nullptr : m_textureDescs.data();
         m_descValid = true;
     }
     return m_desc;

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _capi as capi
 from ._capi import NoriError
-from .scene import Bsdf, Camera, Integrator, Mesh, RFilter, Scene
+from .scene import Bsdf, Camera, Integrator, Mesh, RFilter, Scene, Texture
 
 DEFER_TESTS, QUIET = 1, 2
 _P = C.c_void_p
@@ -59,6 +59,9 @@ def load_host():
 _BSDF_TYPES = {v: k for k, v in capi.BSDF_NAMES.items()}
 _INTEGRATORS = {v: k for k, v in capi.INTEGRATOR_NAMES.items()}
 _RFILTERS = {v: k for k, v in capi.RFILTER_NAMES.items()}
+_TEXTURES = {v: k for k, v in capi.TEXTURE_NAMES.items()}
+_TEXTURE_FILTERS = {v: k for k, v in capi.TEXTURE_FILTER_NAMES.items()}
+_TEXTURE_WRAPS = {v: k for k, v in capi.TEXTURE_WRAP_NAMES.items()}
 
 
 def bsdf_from_desc(d: capi.BsdfDesc) -> Bsdf:
@@ -81,12 +84,20 @@ def scene_from_desc(d: capi.SceneDesc) -> Scene:
             b = Bsdf(b.type, b.albedo if b.type == "diffuse" else (0.5, 0.5, 0.5),
                      0.1, m.bsdf.int_ior if b.type == "dielectric" else 1.5046,
                      m.bsdf.ext_ior if b.type == "dielectric" else 1.000277)
-        meshes.append(Mesh(pos, idx, nrm, uv, b, tuple(m.radiance) if m.is_emitter else None, f"mesh{i}"))
+        meshes.append(Mesh(pos, idx, nrm, uv, b, tuple(m.radiance) if m.is_emitter else None, f"mesh{i}",
+                           m.albedo_texture - 1 if m.albedo_texture else None))
     c = d.camera
     cam = Camera(c.width, c.height, c.fov, c.near_clip, c.far_clip, np.array(list(c.to_world), np.float32).reshape(4, 4))
     rf = RFilter(_RFILTERS[d.rfilter.type], d.rfilter.radius, d.rfilter.stddev, d.rfilter.B, d.rfilter.C)
     it = Integrator(_INTEGRATORS[d.integrator.type], tuple(d.integrator.position), tuple(d.integrator.energy))
-    return Scene(meshes, cam, rf, it, d.sample_count)
+    textures = []
+    for k in range(d.n_textures):
+        t = d.textures[k]
+        kind = _TEXTURES[t.type]
+        texels = np.ctypeslib.as_array(t.texels, (t.height, t.width, 3)).copy() if kind == "image" else None
+        textures.append(Texture(kind, texels, _TEXTURE_FILTERS[t.filter], _TEXTURE_WRAPS[t.wrap], t.uscale, t.vscale, t.uoffset, t.voffset,
+                                tuple(t.color0), tuple(t.color1)))
+    return Scene(meshes, cam, rf, it, d.sample_count, textures)
 
 
 @dataclass

@@ -113,6 +113,14 @@ class Renderer:
         self._check(self._lib.nori_hip_intersect(self._h, ptr(rays), ptr(its), rays.shape[0], int(shadow)), "intersect")
         return its
 
+    def texture_eval(self, index: int, uv) -> np.ndarray:
+        """(n, 3) float32: Scene.textures[index] (0-based) of the uploaded scene at the (n, 2) texture coordinates uv, evaluated on
+        the device by the lookup the shading uses."""
+        uv = _f32(uv, 2)
+        out = np.zeros((uv.shape[0], 3), dtype=np.float32)
+        self._check(self._lib.nori_hip_texture_eval(self._h, int(index) + 1, ptr(uv), uv.shape[0], ptr(out)), "texture_eval")
+        return out
+
     def sample_rays(self, pixel_samples) -> np.ndarray:
         ps = _f32(pixel_samples, 2)
         rays = np.zeros(ps.shape[0], dtype=capi.RAY_DTYPE)

@@ -40,6 +40,44 @@ class Bsdf:
 
 
 @dataclass
+class Texture:
+    """An albedo texture of a diffuse BSDF (nori_texture_desc in include/nori_hip.h, which states the lookup)."""
+    kind: str = "image"                     # "image" | "checkerboard"
+    texels: Optional[np.ndarray] = None     # image: (H, W, 3) float32 linear RGB, row 0 = the top row
+    filter: str = "bilinear"                # "nearest" | "bilinear"
+    wrap: str = "repeat"                    # "repeat" | "clamp"
+    uscale: float = 1.0
+    vscale: float = 1.0
+    uoffset: float = 0.0
+    voffset: float = 0.0
+    color0: tuple = (0.4, 0.4, 0.4)         # checkerboard
+    color1: tuple = (0.2, 0.2, 0.2)
+
+    def __post_init__(self):
+        if self.texels is not None:
+            self.texels = np.ascontiguousarray(self.texels, dtype=np.float32)
+            assert self.texels.ndim == 3 and self.texels.shape[2] == 3, "texels: (H, W, 3)"
+
+    def params(self) -> dict:
+        return {"kind": self.kind, "filter": self.filter, "wrap": self.wrap, "uscale": float(self.uscale), "vscale": float(self.vscale),
+                "uoffset": float(self.uoffset), "voffset": float(self.voffset), "color0": list(map(float, self.color0)),
+                "color1": list(map(float, self.color1))}
+
+    def desc(self) -> capi.TextureDesc:
+        d = capi.TextureDesc()
+        d.type = capi.TEXTURE_NAMES[self.kind]
+        if self.texels is not None:
+            d.height, d.width = int(self.texels.shape[0]), int(self.texels.shape[1])
+            d.texels = self.texels.ctypes.data_as(C.POINTER(C.c_float))
+        d.filter = capi.TEXTURE_FILTER_NAMES[self.filter]
+        d.wrap = capi.TEXTURE_WRAP_NAMES[self.wrap]
+        d.uscale, d.vscale, d.uoffset, d.voffset = self.uscale, self.vscale, self.uoffset, self.voffset
+        d.color0[:] = [float(x) for x in self.color0]
+        d.color1[:] = [float(x) for x in self.color1]
+        return d
+
+
+@dataclass
 class Mesh:
     positions: np.ndarray                   # (nV, 3) float32, world space
     indices: np.ndarray                     # (nF, 3) uint32
@@ -48,6 +86,7 @@ class Mesh:
     bsdf: Bsdf = field(default_factory=Bsdf)
     radiance: Optional[tuple] = None        # area emitter if not None
     name: str = ""
+    albedo_texture: Optional[int] = None    # index into Scene.textures (0-based here, 1-based in nori_mesh_desc); diffuse only
 
     def __post_init__(self):
         self.positions = np.ascontiguousarray(self.positions, dtype=np.float32).reshape(-1, 3)
@@ -91,6 +130,7 @@ class Scene:
     rfilter: RFilter = field(default_factory=RFilter)
     integrator: Integrator = field(default_factory=Integrator)
     sample_count: int = 1
+    textures: List[Texture] = field(default_factory=list)
 
     # ------------------------------------------------------------ C view
     def c_desc(self):
@@ -109,6 +149,7 @@ class Scene:
             d.bsdf = m.bsdf.desc()
             d.is_emitter = 1 if m.radiance is not None else 0
             d.radiance[:] = [float(x) for x in (m.radiance or (0, 0, 0))]
+            d.albedo_texture = 0 if m.albedo_texture is None else int(m.albedo_texture) + 1
             keep.append(m)
         s = capi.SceneDesc()
         s.n_meshes = n
@@ -125,6 +166,11 @@ class Scene:
         s.integrator.position[:] = [float(x) for x in it.position]
         s.integrator.energy[:] = [float(x) for x in it.energy]
         s.sample_count = int(self.sample_count)
+        if self.textures:
+            tarr = (capi.TextureDesc * len(self.textures))(*[t.desc() for t in self.textures])
+            keep += [tarr] + list(self.textures)
+            s.n_textures = len(self.textures)
+            s.textures = C.cast(tarr, C.POINTER(capi.TextureDesc))
         return s, keep
 
     @property
@@ -150,6 +196,10 @@ class Scene:
         for m in self.meshes:
             for a in (m.positions, m.indices, m.normals, m.texcoords):
                 h.update(b"-" if a is None else np.ascontiguousarray(a).tobytes())
+        if self.textures:      # (scenes without textures: the digest of before, which profiles and fixtures are keyed by)
+            for t in self.textures:
+                h.update(b"t-" if t.texels is None else b"t" + np.asarray(t.texels.shape, dtype=np.int64).tobytes() + t.texels.tobytes())
+            h.update(np.asarray([-1 if m.albedo_texture is None else m.albedo_texture for m in self.meshes], dtype=np.int64).tobytes())
         return h.hexdigest()
 
     def save_npz(self, path: str, base: Optional[str] = None) -> None:
@@ -166,10 +216,14 @@ class Scene:
                                                  "alpha": m.bsdf.alpha, "int_ior": m.bsdf.int_ior,
                                                  "ext_ior": m.bsdf.ext_ior},
                         "radiance": list(map(float, m.radiance)) if m.radiance is not None else None,
-                        "normals": m.normals is not None, "texcoords": m.texcoords is not None}
+                        "normals": m.normals is not None, "texcoords": m.texcoords is not None,
+                        **({"albedo_texture": m.albedo_texture} if m.albedo_texture is not None else {})}
                        for m in self.meshes],
         }
+        if self.textures:
+            meta["textures"] = [dict(t.params(), texels=t.texels is not None) for t in self.textures]
         if base is not None:
+            assert not self.textures, "a variant fixture (base=...) stores no arrays: save a textured scene whole"
             meta["base"], meta["geometry_digest"] = base, self.geometry_digest()
             np.savez_compressed(path, meta=np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8))
             return
@@ -181,6 +235,9 @@ class Scene:
                 arrays[f"m{i}_N"] = m.normals
             if m.texcoords is not None:
                 arrays[f"m{i}_UV"] = m.texcoords
+        for k, t in enumerate(self.textures):
+            if t.texels is not None:
+                arrays[f"t{k}_texels"] = t.texels
         arrays["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
         np.savez_compressed(path, **arrays)
 
@@ -217,5 +274,11 @@ class Scene:
                                   z[f"m{i}_N"] if mm["normals"] else None,
                                   z[f"m{i}_UV"] if mm["texcoords"] else None,
                                   Bsdf(b["type"], tuple(b["albedo"]), b["alpha"], b["int_ior"], b["ext_ior"]),
-                                  tuple(mm["radiance"]) if mm["radiance"] is not None else None, mm["name"]))
+                                  tuple(mm["radiance"]) if mm["radiance"] is not None else None, mm["name"],
+                                  mm.get("albedo_texture")))
+        for k, tm in enumerate(meta.get("textures", [])):
+            p = dict(tm)
+            has_texels = p.pop("texels")
+            p["color0"], p["color1"] = tuple(p["color0"]), tuple(p["color1"])
+            sc.textures.append(Texture(texels=z[f"t{k}_texels"] if has_texels else None, **p))
         return sc
