@@ -317,28 +317,45 @@ NORI_HD uint32_t split_inside(const uint32_t *sat, f3 mn, f3 mx, f3 smin, f3 sin
                 fz = fminf(1.0f, (mx.z - mn.z) * sinv.z * (float) kSplitGrid / (float) (z1 - z0));
     return (uint32_t) ((float) cells * (fx * (fy * fz)));
 }
-/* box of the triangle's part inside the cell [cmn, cmx] (binary64 clipping, rounded outwards); false: nothing there */
-NORI_HD bool split_part_box(const double tri[3][3], f3 cmn, f3 cmx, f3 &mn, f3 &mx) {
-    double a[10][3], b[10][3];
+/* the triangle clipped to the cell [lo, hi], plane by plane, in binary64: the polygon's vertices in a[0 .. n), n returned (0: nothing
+   there).  a and b hold `cap` vertices each.  An exactly convex polygon gains at most one vertex per plane (3 + 6 = 9); rounded
+   intersection points carry no such proof, so every store is guarded: -1 when a vertex beyond `cap` would have to be stored, and nothing
+   was written past a[cap - 1] / b[cap - 1].  *peak (if given): the most vertices the polygon had after any plane. */
+constexpr int kSplitClipVertices = 10;
+NORI_HD int split_clip(const double tri[3][3], const double lo[3], const double hi[3], double (*a)[3], double (*b)[3], int cap, int *peak) {
     int n = 3;
+    if (cap < n) return -1;
     for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) a[i][k] = tri[i][k];
-    const double lo[3] = {cmn.x, cmn.y, cmn.z}, hi[3] = {cmx.x, cmx.y, cmx.z};
+    if (peak) *peak = n;
     for (int plane = 0; plane < 6 && n > 0; ++plane) {
         const int axis = plane >> 1; const bool above = (plane & 1) == 0; const double where = above ? lo[axis] : hi[axis];
         int m = 0;
         for (int i = 0; i < n; ++i) {
             const double *p = a[i], *q = a[(i + 1) % n];
             const double dp = above ? p[axis] - where : where - p[axis], dq = above ? q[axis] - where : where - q[axis];
-            if (dp >= 0.0) { for (int k = 0; k < 3; ++k) b[m][k] = p[k]; ++m; }
+            if (dp >= 0.0) {
+                if (m >= cap) return -1;
+                for (int k = 0; k < 3; ++k) b[m][k] = p[k]; ++m;
+            }
             if ((dp > 0.0 && dq < 0.0) || (dp < 0.0 && dq > 0.0)) {
+                if (m >= cap) return -1;
                 const double t = dp / (dp - dq);
                 for (int k = 0; k < 3; ++k) b[m][k] = p[k] + t * (q[k] - p[k]);
                 b[m][axis] = where; ++m;
             }
         }
-        n = m < 10 ? m : 10;
+        n = m;
+        if (peak && n > *peak) *peak = n;
         for (int i = 0; i < n; ++i) for (int k = 0; k < 3; ++k) a[i][k] = b[i][k];
     }
+    return n;
+}
+/* box of the triangle's part inside the cell [cmn, cmx] (binary64 clipping, rounded outwards); false: nothing there, or the clipped
+   polygon does not fit its buffers -- the caller does not cut then, and the uncut part is a valid reference */
+NORI_HD bool split_part_box(const double tri[3][3], f3 cmn, f3 cmx, f3 &mn, f3 &mx, int *peak = nullptr) {
+    double a[kSplitClipVertices][3], b[kSplitClipVertices][3];
+    const double lo[3] = {cmn.x, cmn.y, cmn.z}, hi[3] = {cmx.x, cmx.y, cmx.z};
+    const int n = split_clip(tri, lo, hi, a, b, kSplitClipVertices, peak);
     if (n <= 0) return false;
     double dmn[3] = {a[0][0], a[0][1], a[0][2]}, dmx[3] = {a[0][0], a[0][1], a[0][2]};
     for (int i = 1; i < n; ++i) for (int k = 0; k < 3; ++k) { dmn[k] = a[i][k] < dmn[k] ? a[i][k] : dmn[k]; dmx[k] = a[i][k] > dmx[k] ? a[i][k] : dmx[k]; }
@@ -352,7 +369,7 @@ NORI_HD bool split_part_box(const double tri[3][3], f3 cmn, f3 cmx, f3 &mn, f3 &
 }
 /* the references of triangle t, at most 1 + cuts (a part no grid plane crosses keeps its cuts unused): counted (write = false: the
    builder's scan places every triangle's run) or written at out[first ...]; returns how many */
-NORI_HD uint32_t split_emit(const f4 *pos, const uint32_t *idx, uint32_t t, uint32_t cuts, float pad0, f3 smin, f3 sinv, bool write, const RefOut &out, uint32_t first) {
+NORI_HD uint32_t split_emit(const f4 *pos, const uint32_t *idx, uint32_t t, uint32_t cuts, float pad0, f3 smin, f3 sinv, bool write, const RefOut &out, uint32_t first, int *peak = nullptr) {
     f3 tmn, tmx; tri_box(pos, idx, t, tmn, tmx);
     const f3 p0 = xyz(pos[idx[3 * (size_t) t]]), p1 = xyz(pos[idx[3 * (size_t) t + 1]]), p2 = xyz(pos[idx[3 * (size_t) t + 2]]);
     bool unbounded;
@@ -379,7 +396,9 @@ NORI_HD uint32_t split_emit(const f4 *pos, const uint32_t *idx, uint32_t t, uint
         if (cut) {
             f3 lo_cmx = pt.mx, hi_cmn = pt.mn;
             if (axis == 0) { lo_cmx.x = where; hi_cmn.x = where; } else if (axis == 1) { lo_cmx.y = where; hi_cmn.y = where; } else { lo_cmx.z = where; hi_cmn.z = where; }
-            cut = split_part_box(tri, pt.mn, lo_cmx, lo.mn, lo.mx) && split_part_box(tri, hi_cmn, pt.mx, hi.mn, hi.mx);
+            int pk_lo = 0, pk_hi = 0;      /* (most vertices the two clips held: for the CPU harness, tests/test_device_logic_cpu.py) */
+            cut = split_part_box(tri, pt.mn, lo_cmx, lo.mn, lo.mx, &pk_lo) && split_part_box(tri, hi_cmn, pt.mx, hi.mn, hi.mx, &pk_hi);
+            if (peak) { if (pk_lo > *peak) *peak = pk_lo; if (pk_hi > *peak) *peak = pk_hi; }
         }
         if (!cut) {
             if (write) {

@@ -72,9 +72,12 @@ class Renderer:
 
     # ------------------------------------------------------------ load time
     def upload(self, scene: Scene, build: bool = True, builder: int = 0):
-        """builder: nori_accel_builder.  The default here is 0, the host's SAH builder, whose trees the suite's fixed expectations (depths,
-        costs, which traversal-stack variant runs) were written for; the library's own default -- NORI_ACCEL_AUTO = 2, what the C++ host,
-        bench.py, smoke() and the tools pass -- is the device's builder (lbvh.hip)."""
+        """builder: nori_accel_builder (include/nori_hip.h).  The default HERE is 0, NORI_ACCEL_HOST_SAH: the host's SAH builder, whose trees
+        the suite's pinned expectations (depths, node counts, costs, which traversal-stack variant runs) were written for.  It is not
+        what the library builds by default: that is 2, NORI_ACCEL_AUTO -- the device's builder (lbvh.hip; the host's only if the
+        device's fails, silently: accel_info()["built_on_device"] tells) -- which the C++ host, bench.py, smoke() and the tools pass.
+        The tests that carry the parity claims at full size run on both (tests/test_gpu_parity.py: BUILDERS); pass builder=2 to
+        render through the tree a user of the library gets."""
         desc, keep = scene.c_desc()
         self._check(self._lib.nori_hip_upload_scene(self._h, C.byref(desc)), "upload_scene")
         del keep

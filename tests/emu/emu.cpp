@@ -326,7 +326,13 @@ int emu_border_size(const emu_ctx *c) { return c->host.filter.border; }
 
 /* the references split_emit (lbvh_steps.h) makes of ONE triangle cut `cuts` times, in a scene box [smin, smax]: their padded boxes as
    (mn.xyz, mx.xyz) rows and Morton keys; returns how many (tests/test_device_logic_cpu.py: every point of the triangle lies in one of them) */
+int emu_split_parts_peak(const float *tri9, uint32_t cuts, float pad0, const float *smin3, const float *smax3, float *boxes6, unsigned long long *keys, int cap, int *peak);
 int emu_split_parts(const float *tri9, uint32_t cuts, float pad0, const float *smin3, const float *smax3, float *boxes6, unsigned long long *keys, int cap) {
+    return emu_split_parts_peak(tri9, cuts, pad0, smin3, smax3, boxes6, keys, cap, nullptr);
+}
+/* the same, and *peak = the most vertices any of the clips behind these parts held in its buffers (split_clip; 0: nothing was clipped) */
+int emu_split_parts_peak(const float *tri9, uint32_t cuts, float pad0, const float *smin3, const float *smax3, float *boxes6, unsigned long long *keys, int cap, int *peak) {
+    if (peak) *peak = 0;
     f4 pos[3]; uint32_t idx[3] = {0u, 1u, 2u};
     for (int k = 0; k < 3; ++k) { pos[k].x = tri9[3 * k]; pos[k].y = tri9[3 * k + 1]; pos[k].z = tri9[3 * k + 2]; pos[k].w = 0.0f; }
     const f3 smin = mk3(smin3[0], smin3[1], smin3[2]);
@@ -337,13 +343,35 @@ int emu_split_parts(const float *tri9, uint32_t cuts, float pad0, const float *s
     if ((int) n > cap) return -1;
     std::vector<uint32_t> tri(n); std::vector<f4> mn(n), mx(n); std::vector<unsigned long long> key(n);
     const RefOut out{tri.data(), mn.data(), mx.data(), key.data()};
-    if (split_emit(pos, idx, 0u, cuts, pad0, smin, sinv, true, out, 0u) != n) return -2;
+    if (split_emit(pos, idx, 0u, cuts, pad0, smin, sinv, true, out, 0u, peak) != n) return -2;
     for (uint32_t k = 0; k < n; ++k) {
         boxes6[6 * k] = mn[k].x; boxes6[6 * k + 1] = mn[k].y; boxes6[6 * k + 2] = mn[k].z;
         boxes6[6 * k + 3] = mx[k].x; boxes6[6 * k + 4] = mx[k].y; boxes6[6 * k + 5] = mx[k].z;
         keys[k] = key[k];
     }
     return (int) n;
+}
+
+/* split_clip (lbvh_steps.h) on ONE triangle and ONE cell with buffers of `cap` vertices that the harness owns: each buffer is followed by
+   kGuard vertices of a canary value.  Returns split_clip's answer (vertices left, 0: nothing there, -1: the polygon does not fit `cap`);
+   *peak = the most vertices the polygon had; *canaries_intact = 1 iff no guard word behind either buffer changed;
+   verts (cap x 3 doubles, may be null): the clipped polygon. */
+int emu_split_clip(const float *tri9, const float *cmn3, const float *cmx3, int cap, int *peak, int *canaries_intact, double *verts) {
+    constexpr int kGuard = 16;
+    if (cap < 0 || cap > 64) return -2;
+    const double canary = -7.25e77;
+    std::vector<double> store((size_t) 2 * (cap + kGuard) * 3, canary);
+    double (*a)[3] = reinterpret_cast<double (*)[3]>(store.data());
+    double (*b)[3] = reinterpret_cast<double (*)[3]>(store.data() + (size_t) (cap + kGuard) * 3);
+    double tri[3][3];
+    for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) tri[i][k] = tri9[3 * i + k];
+    const double lo[3] = {cmn3[0], cmn3[1], cmn3[2]}, hi[3] = {cmx3[0], cmx3[1], cmx3[2]};
+    const int n = split_clip(tri, lo, hi, a, b, cap, peak);
+    bool ok = true;
+    for (int g = 0; g < kGuard * 3; ++g) ok = ok && (&a[cap][0])[g] == canary && (&b[cap][0])[g] == canary;
+    *canaries_intact = ok ? 1 : 0;
+    if (verts) for (int i = 0; i < n && i < cap; ++i) for (int k = 0; k < 3; ++k) verts[3 * i + k] = a[i][k];
+    return n;
 }
 
 /* raw records for an independent look at the 32-B form (tests/test_device_logic_cpu.py): copies up to `cap` nodes as 16 floats

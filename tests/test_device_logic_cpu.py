@@ -590,7 +590,8 @@ def test_split_parts_cover_the_triangle():
     """split_emit (lbvh_steps.h) on single triangles: whatever the shape -- slivers, axis-parallel, tiny in a huge scene box, far from the origin --
     and however many cuts, every point of the triangle lies in the box of at least one part (the parts are the triangle clipped to cells
     that tile its box; boxes evaluated in binary64, rounded outwards, padded as the whole triangle is -- a sliver's parts keep the sliver's
-    wide pad) and no part reaches beyond the triangle's own padded box."""
+    wide pad) and no part reaches beyond the triangle's own padded box.  And no clip behind these parts ever held more than the 9
+    vertices an exactly convex polygon can have (3 + one per plane): the buffers hold 10."""
     from tests.backends import emu_lib, ptr
     lib = emu_lib()
     rng = np.random.default_rng(5)
@@ -609,9 +610,10 @@ def test_split_parts_cover_the_triangle():
         smin, smax = (lo - grow * rng.uniform(0, 1, 3)).astype(np.float32), (hi + grow * rng.uniform(0, 1, 3)).astype(np.float32)
         pad = np.float32(2e-6 * np.linalg.norm(smax - smin) + 1e-30)
         cuts = int(rng.choice([1, 2, 3, 7, 15, 63]))
-        boxes = np.zeros((64, 6), np.float32); keys = np.zeros(64, np.uint64)
-        n = lib.emu_split_parts(ptr(np.ascontiguousarray(tri)), cuts, pad, ptr(smin), ptr(smax), ptr(boxes), ptr(keys), 64)
+        boxes = np.zeros((64, 6), np.float32); keys = np.zeros(64, np.uint64); peak = np.zeros(1, np.int32)
+        n = lib.emu_split_parts_peak(ptr(np.ascontiguousarray(tri)), cuts, pad, ptr(smin), ptr(smax), ptr(boxes), ptr(keys), 64, ptr(peak))
         assert 1 <= n <= cuts + 1, (trial, n, cuts)
+        assert peak[0] <= 9, (trial, int(peak[0]), tri)
         b = boxes[:n].astype(np.float64)
         pts = w @ tri.astype(np.float64)
         eps = 1e-12 * (1.0 + np.abs(pts))[:, None, :]      # (the points are binary64 combinations of the vertices: their own rounding, 1e-16 relative)
@@ -622,6 +624,170 @@ def test_split_parts_cover_the_triangle():
         assert (b[:, :3] >= whole[0, :3].astype(np.float64) - 1e-6 * scale).all() and (b[:, 3:] <= whole[0, 3:].astype(np.float64) + 1e-6 * scale).all(), trial
         n_cut += 1 if n > 1 else 0
     assert n_cut > 200
+    # inputs aimed at the clip's vertex bound (_clip_edge_cases: vertices on the grid's planes, slivers of a few ulps, coordinates near
+    # 1e30, 1e-30 and denormal, contacts in a point or an edge, planes through a cell edge, hexagons), in a scene box of four cells
+    # per axis whose grid planes are the planes of the case's cell: the same properties, the same bound
+    n_cut, tags = 0, {}
+    for trial, (tag, tri, cmn, cmx) in enumerate(_clip_edge_cases(np.random.default_rng(6), 300)):
+        e = cmx - cmn
+        smin, smax = np.minimum(cmn - e, tri.min(0)).astype(np.float32), np.maximum(cmn + 3 * e, tri.max(0)).astype(np.float32)
+        if rng.random() < 0.5:
+            smin, smax = (cmn - e).astype(np.float32), (cmn + 3 * e).astype(np.float32)      # the triangle may reach out of the scene box: keys clamp, boxes do not
+        pad = np.float32(2e-6 * np.linalg.norm((smax - smin).astype(np.float64)) + 1e-30)
+        cuts = int(rng.choice([1, 3, 7, 63]))
+        boxes = np.zeros((64, 6), np.float32); keys = np.zeros(64, np.uint64); peak = np.zeros(1, np.int32)
+        n = lib.emu_split_parts_peak(ptr(np.ascontiguousarray(tri)), cuts, pad, ptr(smin), ptr(smax), ptr(boxes), ptr(keys), 64, ptr(peak))
+        assert 1 <= n <= cuts + 1, (tag, trial, n, cuts)
+        assert peak[0] <= 9, (tag, trial, int(peak[0]), tri)
+        b = boxes[:n].astype(np.float64)
+        top = float(np.abs(tri).max())
+        pts = w[:1000] @ tri.astype(np.float64)
+        eps = 1e-12 * top                            # binary64 rounding of the points: 1e-16 of the largest coordinate
+        inside = ((pts[:, None, :] >= b[None, :, :3] - eps) & (pts[:, None, :] <= b[None, :, 3:] + eps)).all(2).any(1)
+        assert inside.all(), (tag, trial, cuts, n, tri, pts[~inside][:3])
+        whole = np.zeros((1, 6), np.float32); k1 = np.zeros(1, np.uint64)
+        assert lib.emu_split_parts(ptr(np.ascontiguousarray(tri)), 0, pad, ptr(smin), ptr(smax), ptr(whole), ptr(k1), 1) == 1
+        # a part's box is the clipped polygon's, whose vertices lie in the triangle's box up to binary64 rounding, moved outwards to the
+        # next binary32 value at most, and padded as the whole: two units in the last place of the largest coordinate (or of the smallest denormal)
+        tol = 2.0 * max(top * 2.0 ** -23, 2.0 ** -149)
+        assert (b[:, :3] >= whole[0, :3].astype(np.float64) - tol).all() and (b[:, 3:] <= whole[0, 3:].astype(np.float64) + tol).all(), (tag, trial)
+        n_cut += 1 if n > 1 else 0
+        tags[tag] = tags.get(tag, 0) + (1 if n > 1 else 0)
+    print(f"[split] edge cases cut: {tags}")
+    assert n_cut > 300
+
+
+def _ulps(x, k):
+    """binary32 x moved by k units in its last place (k an integer array; across zero the pattern of the sign-magnitude encoding is kept monotone)"""
+    i = np.asarray(x, np.float32).view(np.int32).astype(np.int64)
+    i = np.where(i < 0, -(i & 0x7fffffff), i) + k
+    return np.where(i < 0, (-i) | 0x80000000, i).astype(np.uint32).view(np.float32)
+
+
+def _clip_edge_cases(rng, n_each):
+    """(tag, triangle (3, 3) binary32, cell min (3,), cell max (3,)) aimed at the vertex bound of split_clip: inputs on which the exact
+    clip has the most vertices it can have, or on which rounding decides which side of a plane a point lies."""
+    pow2 = [1.0, 2.0 ** 100, 2.0 ** -100, 2.0 ** -140]      # ~1e30, ~1e-30, and binary32 denormals (small integers x 2^-140 are exact)
+    for k in range(n_each):
+        # vertices exactly on grid planes: an integer lattice, the cell one of its cubes -- contacts in corners, along edges, in faces
+        sc = np.float32(pow2[k % 4])
+        tri = rng.integers(-2, 4, (3, 3)).astype(np.float32)
+        c = rng.integers(-1, 2, 3).astype(np.float32)
+        yield "lattice", tri * sc, c * sc, (c + 1) * sc
+        # slivers: extents of a few units in the last place along one, two or three axes, the cell's planes among the same few values
+        base = (rng.uniform(-1, 1, 3) * float(rng.choice([1.0, 1e3]))).astype(np.float32)
+        thin = rng.random(3) < 0.6
+        tri = np.where(thin, _ulps(np.broadcast_to(base, (3, 3)), rng.integers(-3, 4, (3, 3))), base + rng.uniform(-1, 1, (3, 3)).astype(np.float32))
+        lo = np.where(thin, _ulps(base, rng.integers(-3, 1, 3)), base - rng.uniform(0, 1, 3).astype(np.float32))
+        hi = np.where(thin, _ulps(base, rng.integers(0, 4, 3)), base + rng.uniform(0, 1, 3).astype(np.float32))
+        yield "sliver", tri.astype(np.float32) * sc, lo.astype(np.float32) * sc, hi.astype(np.float32) * sc
+        # the cell touches the triangle in one point (a vertex in a cell corner) or along one edge (an edge in a cell edge), exactly or within ulps
+        c = rng.uniform(-1, 1, 3).astype(np.float32); e = rng.uniform(0.1, 1, 3).astype(np.float32)
+        corner = np.where(rng.random(3) < 0.5, c, c + e)
+        away = np.where(corner == c, -1.0, 1.0) * rng.uniform(0.0, 2.0, (3, 3))
+        tri = (corner + away).astype(np.float32)
+        tri[0] = _ulps(corner, rng.integers(-1, 2, 3) * int(rng.integers(0, 2)))
+        if k % 2:                                              # a second vertex on the cell edge through that corner
+            ax = int(rng.integers(0, 3)); tri[1] = tri[0]; tri[1, ax] = np.float32(c[ax] + e[ax] * rng.uniform(-1, 2))
+        yield "touch", tri * sc, c * sc, (c + e) * sc
+        # the triangle's plane (nearly) contains a cell edge: two vertices on the line of the edge, beyond its ends, moved by ulps
+        ax = int(rng.integers(0, 3))
+        p0 = np.where(rng.random(3) < 0.5, c, c + e).astype(np.float32); p1 = p0.copy()
+        p0[ax] = np.float32(c[ax] - e[ax] * rng.uniform(0, 3)); p1[ax] = np.float32(c[ax] + e[ax] * rng.uniform(1, 4))
+        tri = np.stack([_ulps(p0, rng.integers(-2, 3, 3)), _ulps(p1, rng.integers(-2, 3, 3)), (c + 0.5 * e + rng.uniform(-2, 2, 3) * e).astype(np.float32)])
+        yield "edge-in-plane", tri.astype(np.float32) * sc, c * sc, (c + e) * sc
+        # a plane that cuts all three axes of the cell: the exact clip is a hexagon, the polygon of most vertices a box makes of a plane
+        s = rng.uniform(1.2, 1.8)
+        far = rng.uniform(3, 6)
+        tri = np.float32([[s + 2 * far, -far, -far], [-far, s + 2 * far, -far], [-far, -far, s + 2 * far]]) * e + c
+        yield "hexagon", _ulps(tri, rng.integers(-1, 2, (3, 3))) * sc, c * sc, (c + e) * sc
+
+
+def _emu_clip(lib, tri, cmn, cmx, cap):
+    from tests.backends import ptr
+    tri, cmn, cmx = (np.ascontiguousarray(x, np.float32) for x in (tri, cmn, cmx))
+    peak = np.zeros(1, np.int32); intact = np.zeros(1, np.int32); verts = np.zeros((max(cap, 1), 3), np.float64)
+    n = lib.emu_split_clip(ptr(tri), ptr(cmn), ptr(cmx), cap, ptr(peak), ptr(intact), ptr(verts))
+    return n, int(peak[0]), int(intact[0]), verts[:max(n, 0)]
+
+
+# kept by name: (triangle, cell min, cell max) as binary32 bit patterns.  Three million inputs of _clip_edge_cases (311 seeds) gave no polygon of
+# more than 9 vertices; this one reaches the 9 of the exact bound (every plane of the cell cuts a corner off), at coordinates near 1e33
+CLIP_NAMED_CASES = {
+    "nine-vertices": ([4134531696, 4132298155, 1981822994, 4134533956, 4132290749, 1981801299, 4134514667, 4132272194, 1981804615],
+                      [4134533447, 4132295154, 1981802604], [4134516821, 4132274437, 1981815590]),
+}
+
+
+def test_split_clip_never_needs_more_than_nine_vertices():
+    """split_clip (lbvh_steps.h: the triangle against the six planes of a cell, in binary64) holds its polygon in buffers of 10 vertices.
+    An exactly convex polygon has at most 3 + 6 = 9; the intersection points are rounded, so that is no proof.  Inputs aimed at the bound
+    -- vertices on the planes, slivers of a few ulps, coordinates near 1e30, near 1e-30 and denormal, contacts in one point or edge,
+    planes that nearly contain a cell edge, hexagons -- and plain random ones: the polygon never has more than 9 vertices, the call never
+    gives up, nothing behind the buffers changes, every vertex of the result lies in the cell, and every point of the triangle that lies
+    in the cell lies in the box of the result (what split_part_box returns, before its rounding outwards)."""
+    from tests.backends import emu_lib
+    lib = emu_lib()
+    rng = np.random.default_rng(77)
+    w = rng.uniform(0, 1, (300, 3)); w /= w.sum(1, keepdims=True)
+    w[:3] = np.eye(3); w[3:6] = [[0.5, 0.5, 0], [0, 0.5, 0.5], [0.5, 0, 0.5]]
+
+    def plain(n):
+        for _ in range(n):
+            c = rng.uniform(-1, 1, 3).astype(np.float32); e = (rng.uniform(0.01, 1, 3) * rng.choice([1.0, 1e-3], 3)).astype(np.float32)
+            yield "random", (c + 0.5 * e + rng.uniform(-2, 2, (3, 3)) * e).astype(np.float32), c, c + e
+
+    def named():
+        for name, (t, lo, hi) in CLIP_NAMED_CASES.items():
+            yield name, np.uint32(t).view(np.float32).reshape(3, 3), np.uint32(lo).view(np.float32), np.uint32(hi).view(np.float32)
+    seen, peaks = {}, {}
+    for tag, tri, cmn, cmx in list(named()) + list(_clip_edge_cases(rng, 1500)) + list(plain(3000)):
+        assert np.isfinite(tri).all() and (cmx >= cmn).all(), tag
+        n, peak, intact, verts = _emu_clip(lib, tri, cmn, cmx, 10)
+        what = (tag, tri.view(np.uint32).tolist(), cmn.view(np.uint32).tolist(), cmx.view(np.uint32).tolist())
+        assert intact == 1, what
+        assert n >= 0, what                       # -1: more vertices than the buffers hold
+        assert 3 <= peak <= 9, (peak,) + what
+        seen[tag] = seen.get(tag, 0) + 1; peaks[tag] = max(peaks.get(tag, 0), peak)
+        lo, hi = cmn.astype(np.float64), cmx.astype(np.float64)
+        pts = w @ tri.astype(np.float64)
+        # (binary64 roundings of the points and of the intersection points: 1e-16 relative to the largest coordinate; 1e-12 leaves room)
+        eps = 1e-12 * max(float(np.abs(tri).max()), float(np.abs(lo).max()), float(np.abs(hi).max()))
+        in_cell = ((pts >= lo + eps) & (pts <= hi - eps)).all(1)      # strictly inside, whatever the roundings
+        if n == 0:
+            assert not in_cell.any(), what
+            continue
+        assert ((verts >= lo - eps) & (verts <= hi + eps)).all(), what
+        vmn, vmx = verts.min(0), verts.max(0)
+        assert ((pts[in_cell] >= vmn - eps) & (pts[in_cell] <= vmx + eps)).all(), what
+    print(f"[split_clip] cases {seen}, most vertices {peaks}")
+    assert peaks["nine-vertices"] == 9 and peaks["hexagon"] >= 6 and all(seen[t] == 1500 for t in ("lattice", "sliver", "touch", "edge-in-plane", "hexagon")) and seen["random"] == 3000
+
+
+def test_split_clip_stops_at_its_capacity_instead_of_writing_past_it():
+    """The guard itself, whether or not any input ever needs more than 9 vertices: a plane through all three axes of a cell clips a
+    triangle to a hexagon.  With buffers one vertex short of what that clip needs -- and with buffers of 4 -- split_clip reports "does
+    not fit" (-1: split_part_box returns false, split_emit does not cut and emits the uncut part) and the canary words behind both
+    buffers are what they were.  With the count clamped only AFTER the loop that stores the vertices (the code before the guard) the
+    canaries behind the buffers are overwritten and this test fails."""
+    from tests.backends import emu_lib
+    lib = emu_lib()
+    tri = np.float32([[4.5, -1.5, -1.5], [-1.5, 4.5, -1.5], [-1.5, -1.5, 4.5]])      # the plane x + y + z = 1.5
+    cmn, cmx = np.float32([0, 0, 0]), np.float32([1, 1, 1])
+    n, peak, intact, verts = _emu_clip(lib, tri, cmn, cmx, 10)
+    assert (n, intact) == (6, 1) and 6 <= peak <= 9, (n, peak, intact)
+    assert np.allclose(verts.sum(1), 1.5, rtol=0, atol=1e-12) and len({tuple(np.round(v, 9)) for v in verts}) == 6      # six distinct points of the plane
+    n_fit, _, intact_fit, _ = _emu_clip(lib, tri, cmn, cmx, peak)
+    assert (n_fit, intact_fit) == (6, 1)                                             # exactly enough: no false alarm
+    for cap in (peak - 1, 4, 3, 2, 0):
+        n_short, _, intact_short, _ = _emu_clip(lib, tri, cmn, cmx, cap)
+        assert intact_short == 1, f"split_clip wrote behind buffers of {cap} vertices (the clip needs {peak})"
+        assert n_short == -1, f"split_clip did not report that {peak} vertices do not fit {cap}: returned {n_short}"
+    # the same through split_emit: the parts of this triangle are what they are with room to spare -- the guard does not fire at 10
+    from tests.backends import ptr
+    boxes = np.zeros((64, 6), np.float32); keys = np.zeros(64, np.uint64); pk = np.zeros(1, np.int32)
+    n_parts = lib.emu_split_parts_peak(ptr(tri), 7, np.float32(1e-5), ptr(np.float32([-2, -2, -2])), ptr(np.float32([5, 5, 5])), ptr(boxes), ptr(keys), 64, ptr(pk))
+    assert n_parts == 8 and 3 <= pk[0] <= 9, (n_parts, int(pk[0]))
 
 
 def test_triangle_splitting_in_front_of_the_device_builder():

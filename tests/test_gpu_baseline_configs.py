@@ -1,7 +1,8 @@
 """The BASELINE.json configurations THEMSELVES in the driver-run GPU suite -- `workloads.load("c2" | "c4" | "c5")` at their full
 geometry (327,680 / 10,004,450 triangles, 2048 x 2048 frame), a few samples per pixel so that the CPU oracle finishes in seconds --
 not smaller stand-ins: wavefront engine with the production node loop (32-B records + hand-written loop for the BVH2 trees, wide
-nodes for the terrain) against Oracle(use_bvh=True).  Bar: ray counts EQUAL (bit-identical paths), frame within the SURVEY 8(d)
+nodes for the terrain) against Oracle(use_bvh=True), on the tree of the host's SAH builder and on the one the library
+builds by default (on the device).  Bar: ray counts EQUAL (bit-identical paths), frame within the SURVEY 8(d)
 image contract.  Semantics held: Accel::rayIntersect (src/accel.cpp:23-43), renderBlock / render (src/main.cpp:27-56)."""
 import json
 import os
@@ -16,6 +17,7 @@ from tests.test_gpu_parity import assert_image_parity
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ORACLE_THREADS = min(16, os.cpu_count() or 1)      # the oracle starts as many threads as it is told; a run may not have the whole machine
 
 
 @pytest.mark.parametrize("name,spp,triangles,size,layout", [
@@ -29,23 +31,30 @@ def test_baseline_config_at_full_geometry_matches_the_oracle(name, spp, triangle
     wl = workloads.load(name, spp=spp)
     sc = wl.scene
     assert (sc.camera.width, sc.camera.height) == (size, size)
-    r = Renderer(0).upload(sc)                         # the builder bench.py uses
-    r.set_option("engine", "wavefront")
-    info = r.accel_info()
-    if triangles is not None:
-        assert info["n_triangles"] == triangles
-    assert info["node_children"] == layout
-    if layout == 2:
-        assert info["node_records_32b"] == 1           # the hand-written loop's tree form
-    B, sb = r.render_host()
-    assert sb["engine"] == 1 and sb["n_invalid"] == 0
     o = Oracle(sc, use_bvh=True)
-    A, sa = o.render_host(threads=os.cpu_count() or 1)
-    assert sb["n_camera_samples"] == sa["n_camera_samples"] == size * size * spp
-    for k in ("n_closest_rays", "n_shadow_rays"):
-        assert int(sa[k]) == int(sb[k]), (name, k, sa[k], sb[k])
-    assert_image_parity(A, B, r.border, f"{name} {size}x{size}x{spp}, {info['n_triangles']} triangles")
-    r.close(); o.close()
+    A, sa = o.render_host(threads=ORACLE_THREADS)      # once per scene: hits -- hence paths, counts and frame -- do not depend on the tree
+    o.close()
+    # 2 = NORI_ACCEL_AUTO, the library's default and what bench.py, smoke() and the C++ host pass: the tree is built on the device
+    # (lbvh.hip); 0 = the host's SAH builder, whose trees the rest of the suite pins.  The same bar for both.
+    for builder in (0, 2):
+        r = Renderer(0).upload(sc, builder=builder)
+        r.set_option("engine", "wavefront")
+        info = r.accel_info()
+        assert info["built_on_device"] == (1 if builder == 2 else 0), (name, builder, info)      # AUTO falls back to the host's builder without a word
+        if triangles is not None:
+            assert info["n_triangles"] == triangles
+        if name == "c4-table-mis" and builder == 2:
+            assert info["n_references"] > info["n_triangles"], info      # the tree under test is the one cut into references
+        assert info["node_children"] == layout
+        if layout == 2:
+            assert info["node_records_32b"] == 1           # the hand-written loop's tree form
+        B, sb = r.render_host()
+        assert sb["engine"] == 1 and sb["n_invalid"] == 0
+        assert sb["n_camera_samples"] == sa["n_camera_samples"] == size * size * spp
+        for k in ("n_closest_rays", "n_shadow_rays"):
+            assert int(sa[k]) == int(sb[k]), (name, builder, k, sa[k], sb[k])
+        assert_image_parity(A, B, r.border, f"{name} {size}x{size}x{spp}, {info['n_triangles']} triangles, builder {builder}")
+        r.close()
 
 
 def test_device_builder_at_ten_million_triangles_gives_the_host_trees_hits():

@@ -24,6 +24,19 @@ pytestmark = pytest.mark.gpu
 
 ITS_FIELDS = ["p", "t", "uv", "sh_s", "sh_t", "sh_n", "geo_s", "geo_t", "geo_n", "mesh", "tri"]
 
+# 0 = NORI_ACCEL_HOST_SAH: the host's builder, Renderer.upload's default, whose trees the suite's pinned numbers belong to;
+# 2 = NORI_ACCEL_AUTO: the library's default and what bench.py, smoke() and the C++ host pass -- the tree is built on the device (lbvh.hip)
+BUILDERS = (0, 2)
+ORACLE_THREADS = min(16, os.cpu_count() or 1)      # the oracle starts as many threads as it is told (0: as many as the machine has)
+
+
+def assert_built_where_asked(r, builder):
+    """AUTO falls back to the host's builder on any error of the device's and drops the message: only this field tells."""
+    info = r.accel_info()
+    assert info["built_on_device"] == (1 if builder == 2 else 0), (builder, info)
+    return info
+
+
 # SURVEY.md 8(d), per-sample seeding: the image contract every oracle comparison is held to
 PIXEL_REL_TOL, PIXEL_FRACTION, MEAN_REL_TOL = 1e-3, 0.999, 1e-4
 
@@ -461,6 +474,41 @@ def test_treelet_wave_builds_the_tree_of_the_serial_form():
         assert np.array_equal(got[0][5], got[1][5])
 
 
+def test_two_device_builds_of_one_scene_give_one_tree():
+    """The device builder decides in integer sums and settles conflicts by 64-bit maxima (lbvh.hip): which thread comes first is a
+    matter of timing, what is built is not.  Two contexts, builder = auto, one scene: the same tree -- by what a tree determines: node,
+    reference and level counts, SAH cost, the node and triangle tests of a render in either engine -- and the same frame, bit for bit.
+    (test_reference_scenes_both_engines_and_oracle compares the counters of two contexts' trees and rests on this.)  The pa5 table
+    (triangles cut into references, re-insertion), the headline Cornell box at a reduced frame, a 30,000-triangle soup."""
+    from nori_amd.render import Renderer
+    from nori_amd.scene import Mesh, Scene
+    golden = os.path.join(os.path.dirname(__file__), "golden")
+    table = Scene.load_npz(os.path.join(golden, "pa5-table_mis.npz"))
+    table.camera.width, table.camera.height, table.sample_count = 160, 120, 2
+    cbox = Scene.load_npz(os.path.join(golden, "pa4-cbox-path_mis.npz"))
+    cbox.camera.width, cbox.camera.height, cbox.sample_count = 256, 256, 2
+    soup = scenes.soup_scene(30000, seed=3, width=80, height=56, integrator="path_mis")
+    soup.sample_count = 4
+    v, f = scenes.quad((-3, 3, -3), (3, 3, -3), (3, 3, 3), (-3, 3, 3))
+    soup.meshes.append(Mesh(v, f, bsdf=Bsdf("diffuse", (0, 0, 0)), radiance=(5.0, 5.0, 5.0), name="light"))
+    for name, sc in (("table", table), ("cbox", cbox), ("soup", soup)):
+        a, b = Renderer(0).upload(sc, builder=2), Renderer(0).upload(sc, builder=2)
+        ia, ib = assert_built_where_asked(a, 2), assert_built_where_asked(b, 2)
+        if name == "table":
+            assert ia["n_references"] > ia["n_triangles"]
+        for k in ("n_triangles", "n_nodes", "n_leaves", "n_references", "max_depth", "sah_cost", "node_children", "node_records_32b", "total_bytes"):
+            assert ia[k] == ib[k], (name, k, ia[k], ib[k])
+        for engine in ("megakernel", "wavefront"):
+            a.set_option("engine", engine); b.set_option("engine", engine)
+            A, sa = a.render_host(count_traversal=True)
+            B, sb = b.render_host(count_traversal=True)
+            for k in ("n_camera_samples", "n_closest_rays", "n_shadow_rays", "n_node_tests", "n_tri_tests", "n_invalid"):
+                assert sa[k] == sb[k], (name, engine, k, sa[k], sb[k])
+            assert sa["n_node_tests"] > 0 and sa["n_tri_tests"] > 0
+            assert np.array_equal(A, B), (name, engine)
+        a.close(); b.close()
+
+
 def test_gpu_lbvh_render_equals_sah_render(renderer_factory):
     from tests import stat_harness  # noqa: F401
     from nori_amd.scene import Scene
@@ -540,20 +588,24 @@ def test_fuzz_intersect_short():
 def test_headline_workload_matches_oracle(renderer_factory):
     """BASELINE config 3 -- the bench workload: pa4 Cornell box geometry, path_mis, full 1024 x 1024 frame, at
     a sample count the CPU oracle finishes in seconds -- wavefront engine against the oracle, per-sample
-    seeding, held to the SURVEY 8(d) image contract; ray counts agree to the flipped decisions."""
+    seeding, held to the SURVEY 8(d) image contract; ray counts equal.  On the host builder's tree and on the tree the
+    benchmark itself renders through (builder = auto: built on the device)."""
     import os
     from nori_amd.scene import Scene
     sc = Scene.load_npz(os.path.join(os.path.dirname(__file__), "golden", "pa4-cbox-path_mis.npz"))
     assert (sc.camera.width, sc.camera.height, sc.integrator.type) == (1024, 1024, "path_mis")
     sc.sample_count = 8
-    r, o = renderer_factory(sc), Oracle(sc, use_bvh=True)
-    r.set_option("engine", "wavefront")
-    B, sb = r.render_host()
-    A, sa = o.render_host()
-    assert sb["n_camera_samples"] == sa["n_camera_samples"] == 1024 * 1024 * 8 and sb["n_invalid"] == 0
-    for k in ("n_closest_rays", "n_shadow_rays"):
-        assert int(sa[k]) == int(sb[k]), (k, sa[k], sb[k])
-    assert_image_parity(A, B, r.border, "pa4-cbox-path_mis 1024x1024x8")
+    A, sa = Oracle(sc, use_bvh=True).render_host(threads=ORACLE_THREADS)      # once: the oracle's frame does not depend on the device's tree
+    for builder in BUILDERS:
+        r = renderer_factory(sc, builder=builder)
+        assert_built_where_asked(r, builder)
+        r.set_option("engine", "wavefront")
+        B, sb = r.render_host()
+        assert sb["n_camera_samples"] == sa["n_camera_samples"] == 1024 * 1024 * 8 and sb["n_invalid"] == 0
+        for k in ("n_closest_rays", "n_shadow_rays"):
+            assert int(sa[k]) == int(sb[k]), (builder, k, sa[k], sb[k])
+        assert_image_parity(A, B, r.border, f"pa4-cbox-path_mis 1024x1024x8, builder {builder}")
+        r.close()
 
 
 def test_nori_block_seeding_zscore(renderer_factory):
@@ -651,22 +703,24 @@ def test_reference_film_order_gives_bit_identical_frames(renderer_factory, engin
     """film_order = reference: the device adds the samples of a frame in the order of renderBlock / ImageBlock::put /
     BlockGenerator (src/main.cpp:33-53, src/block.cpp:62-152).  With bit-identical radiance per camera sample the whole
     RGBW frame -- every bit of every pixel, the W channel included -- equals a single-threaded render of the oracle;
-    frame sizes that are no multiple of the 32-pixel block or the 16-pixel tile included."""
+    frame sizes that are no multiple of the 32-pixel block or the 16-pixel tile included.  Whichever builder made the tree."""
     from nori_amd import NoriError
     sb = [Bsdf("mirror"), Bsdf("dielectric")] if integ in ("whitted", "path_mis") else [Bsdf("microfacet", (0.2, 0.3, 0.1), 0.2), Bsdf("diffuse")]
     sc = scenes.cornell_box(size[0], size[1], spp, integ, sphere_bsdfs=sb, rfilter=RFilter(rf))
-    r, o = renderer_factory(sc), Oracle(sc, use_bvh=True)
-    r.set_option("engine", engine)
-    r.set_option("film_order", "reference")
-    A, sa = o.render_host(threads=1)
-    B, sb_ = r.render_host()
-    assert sa["n_closest_rays"] == sb_["n_closest_rays"] and sa["n_shadow_rays"] == sb_["n_shadow_rays"]
-    assert np.array_equal(A, B), f"{int((A != B).sum())} of {A.size} floats differ, max {np.abs(A - B).max():.3e}"
-    with pytest.raises(NoriError, match="UNSUPPORTED|whole frames"):
-        r.render_host(tile_mod=2)
-    r.set_option("film_order", "fast")
-    C_, _ = r.render_host()
-    np.testing.assert_allclose(C_, B, rtol=1e-4, atol=1e-5)            # same samples, the fast film's summation order
+    A, sa = Oracle(sc, use_bvh=True).render_host(threads=1)
+    for builder in BUILDERS:
+        r = renderer_factory(sc, builder=builder)
+        assert_built_where_asked(r, builder)
+        r.set_option("engine", engine)
+        r.set_option("film_order", "reference")
+        B, sb_ = r.render_host()
+        assert sa["n_closest_rays"] == sb_["n_closest_rays"] and sa["n_shadow_rays"] == sb_["n_shadow_rays"], builder
+        assert np.array_equal(A, B), f"builder {builder}: {int((A != B).sum())} of {A.size} floats differ, max {np.abs(A - B).max():.3e}"
+        with pytest.raises(NoriError, match="UNSUPPORTED|whole frames"):
+            r.render_host(tile_mod=2)
+        r.set_option("film_order", "fast")
+        C_, _ = r.render_host()
+        np.testing.assert_allclose(C_, B, rtol=1e-4, atol=1e-5)            # same samples, the fast film's summation order
 
 
 def test_reference_film_order_with_the_reference_sampler(renderer_factory):
@@ -684,15 +738,18 @@ def test_reference_film_order_with_the_reference_sampler(renderer_factory):
 def test_headline_geometry_frame_is_bit_identical_in_reference_order(renderer_factory):
     """The headline workload's scene and full 1024 x 1024 frame (1,024 blocks of 32 x 32, 4,096 tiles), 2 samples per
     pixel so that the single-threaded oracle finishes in seconds: wavefront engine + film_order = reference -> the RGBW
-    frame equals the oracle's bit for bit."""
+    frame equals the oracle's bit for bit, through the host builder's tree and through the device-built one."""
     import os
     from nori_amd.scene import Scene
     sc = Scene.load_npz(os.path.join(os.path.dirname(__file__), "golden", "pa4-cbox-path_mis.npz"))
     sc.sample_count = 2
-    r, o = renderer_factory(sc), Oracle(sc, use_bvh=True)
-    r.set_option("engine", "wavefront")
-    r.set_option("film_order", "reference")
-    B, sb = r.render_host()
-    A, sa = o.render_host(threads=1)
-    assert sa["n_closest_rays"] == sb["n_closest_rays"] and sa["n_shadow_rays"] == sb["n_shadow_rays"]
-    assert np.array_equal(A, B), f"{int((A != B).sum())} of {A.size} floats differ"
+    A, sa = Oracle(sc, use_bvh=True).render_host(threads=1)      # once: single-threaded, the expensive half
+    for builder in BUILDERS:
+        r = renderer_factory(sc, builder=builder)
+        assert_built_where_asked(r, builder)
+        r.set_option("engine", "wavefront")
+        r.set_option("film_order", "reference")
+        B, sb = r.render_host()
+        assert sa["n_closest_rays"] == sb["n_closest_rays"] and sa["n_shadow_rays"] == sb["n_shadow_rays"], builder
+        assert np.array_equal(A, B), f"builder {builder}: {int((A != B).sum())} of {A.size} floats differ"
+        r.close()

@@ -23,10 +23,14 @@ def _budget(wf, n):
     wf.set_option("wavefront_samples", n)
 
 
-def _pair(renderer_factory, sc):
-    mk = renderer_factory(sc)
-    wf = renderer_factory(sc)
+def _pair(renderer_factory, sc, builder=0):
+    """A megakernel and a wavefront context on the same scene, each with a tree of its own from `builder` (0: the host's SAH builder;
+    2: auto, the library's default -- built on the device, which the contexts' accel_info must confirm: auto falls back silently)."""
+    mk = renderer_factory(sc, builder=builder)
+    wf = renderer_factory(sc, builder=builder)
     wf.set_option("engine", "wavefront")
+    for r in (mk, wf):
+        assert r.accel_info()["built_on_device"] == (1 if builder == 2 else 0), (builder, r.accel_info())
     return mk, wf
 
 
@@ -259,23 +263,30 @@ def test_regeneration_gives_the_bits_of_the_shrinking_schedule(renderer_factory)
 
 
 def test_regeneration_on_wide_and_deep_trees(renderer_factory):
-    """The same through the other traversal kernels: wide (BVH4) nodes, and a tree deeper than the LDS stack (spill columns)."""
-    sc = scenes.soup_scene(30000, seed=3, width=80, height=56, integrator="path_mis")
-    sc.sample_count = 6
+    """The same through the other traversal kernels and trees: wide (BVH4) nodes, a tree deeper than the LDS stack (spill columns), and
+    the library's default tree -- built on the device, with triangles that hang in several leaves."""
+    soup = scenes.soup_scene(30000, seed=3, width=80, height=56, integrator="path_mis")
+    soup.sample_count = 6
     from nori_amd.scene import Mesh
     v, f = scenes.quad((-3, 3, -3), (3, 3, -3), (3, 3, 3), (-3, 3, 3))
-    sc.meshes.append(Mesh(v, f, bsdf=Bsdf("diffuse", (0, 0, 0)), radiance=(5.0, 5.0, 5.0), name="light"))
-    for layout, builder in (("bvh4q", 0), ("bvh2", 1)):
+    soup.meshes.append(Mesh(v, f, bsdf=Bsdf("diffuse", (0, 0, 0)), radiance=(5.0, 5.0, 5.0), name="light"))
+    # and the default tree (builder = auto: built on the device) of a scene whose triangles it cuts into references
+    table = Scene.load_npz(os.path.join(GOLDEN, "pa5-table_mis.npz"))
+    table.camera.width, table.camera.height, table.sample_count = 80, 56, 6
+    for layout, builder, sc in (("bvh4q", 0, soup), ("bvh2", 1, soup), ("bvh2", 2, table)):
         from nori_amd.render import Renderer
         wf = Renderer(0); wf.set_option("accel_layout", layout); wf.upload(sc, builder=builder); wf.set_option("engine", "wavefront")
-        assert wf.accel_info()["max_depth"] + 1 > 16 or layout == "bvh4q"
+        info = wf.accel_info()
+        assert info["max_depth"] + 1 > 16 or layout == "bvh4q"
+        if builder == 2:
+            assert info["built_on_device"] == 1 and info["n_references"] > info["n_triangles"], info
         ref, sr = wf.render_host()
         wf.set_option("wavefront_samples", 1 << 30)
         for pool in (256 * 3, 80 * 56 * 2):
             wf.set_option("wavefront_paths", pool)
             b, sb = wf.render_host()
-            assert np.array_equal(b, ref), (layout, pool)
-            assert sr["n_closest_rays"] == sb["n_closest_rays"] and sr["n_shadow_rays"] == sb["n_shadow_rays"], (layout, pool)
+            assert np.array_equal(b, ref), (layout, builder, pool)
+            assert sr["n_closest_rays"] == sb["n_closest_rays"] and sr["n_shadow_rays"] == sb["n_shadow_rays"], (layout, builder, pool)
         wf.close()
 
 
@@ -374,18 +385,22 @@ def test_reference_scenes_both_engines_and_oracle(renderer_factory, name):
     sc = Scene.load_npz(os.path.join(GOLDEN, name + ".npz"))
     sc.camera.width, sc.camera.height = sc.camera.width // 4, sc.camera.height // 4
     sc.sample_count = 4
-    mk, wf = _pair(renderer_factory, sc)
-    a, sa = mk.render_host(count_traversal=True)
-    b, sb = _with_env(WALK_64B, lambda: wf.render_host(count_traversal=True))
-    for k in ("n_camera_samples", "n_closest_rays", "n_shadow_rays", "n_node_tests", "n_tri_tests", "n_invalid"):
-        assert sa[k] == sb[k], (k, sa[k], sb[k])
-    np.testing.assert_allclose(b, a, rtol=1e-4, atol=1e-5)
+    from tests.test_gpu_parity import BUILDERS, ORACLE_THREADS, assert_image_parity
     o = Oracle(sc, use_bvh=True)
-    ref, so = o.render_host()
-    for k in ("n_closest_rays", "n_shadow_rays"):
-        assert int(so[k]) == int(sb[k]), k              # bit-identical paths (tests/test_gpu_parity.py): equal counts
-    from tests.test_gpu_parity import assert_image_parity
-    assert_image_parity(ref, b, wf.border, name)
+    ref, so = o.render_host(threads=ORACLE_THREADS)      # once per scene, whatever tree the device walks
+    for builder in BUILDERS:                             # the host's SAH tree; the tree the library builds by default (on the device)
+        # (each engine builds its own tree: equal node / triangle tests below also say that two builds gave one tree --
+        # tests/test_gpu_parity.py::test_two_device_builds_of_one_scene_give_one_tree states that on its own)
+        mk, wf = _pair(renderer_factory, sc, builder)
+        a, sa = mk.render_host(count_traversal=True)
+        b, sb = _with_env(WALK_64B, lambda: wf.render_host(count_traversal=True))
+        for k in ("n_camera_samples", "n_closest_rays", "n_shadow_rays", "n_node_tests", "n_tri_tests", "n_invalid"):
+            assert sa[k] == sb[k], (builder, k, sa[k], sb[k])
+        np.testing.assert_allclose(b, a, rtol=1e-4, atol=1e-5)
+        for k in ("n_closest_rays", "n_shadow_rays"):
+            assert int(so[k]) == int(sb[k]), (builder, k)              # bit-identical paths (tests/test_gpu_parity.py): equal counts
+        assert_image_parity(ref, b, wf.border, f"{name}, builder {builder}")
+        mk.close(); wf.close()
 
 
 def test_fuzz_engines_short():
@@ -424,17 +439,25 @@ def test_contexts_own_their_buffers():
     b.close(); c.close()
 
 
-@pytest.mark.parametrize("members,split,merge", [(1, "tile", "reduce"), (2, "tile", "reduce"), (2, "tile", "gather"), (3, "sample", "reduce"), (4, "tile", "gather")])
-def test_device_group_shares_and_merges(members, split, merge):
+@pytest.mark.parametrize("members,split,merge,builder", [(1, "tile", "reduce", 0), (2, "tile", "reduce", 0), (2, "tile", "gather", 0), (3, "sample", "reduce", 0), (4, "tile", "gather", 0),
+                                                         (2, "tile", "reduce", 2)],      # 2 = auto, what `nori --gpus N` passes: every member builds its tree on its device
+                         ids=["1-tile-reduce", "2-tile-reduce", "2-tile-gather", "3-sample-reduce", "4-tile-gather", "2-tile-reduce-auto"])
+def test_device_group_shares_and_merges(members, split, merge, builder):
     """nori_hip_group_* (what `nori scene.xml --gpus N` calls): one context + one host thread per group member, every
     member renders its share into its own frame, one merge on the first member.  On a one-GPU box the members are the same
     device listed several times -- the whole path (threads, shares, pack / add kernels, the merge) runs, only the transport
     is a device copy instead of RCCL.  The merged frame equals ONE render of the whole frame up to summation order."""
     from nori_amd.render import DeviceGroup, Renderer
     sc = scenes.cornell_box(64, 40, 12, "path_mis")
-    whole, st = Renderer(0).upload(sc).render_host()
-    g = DeviceGroup([0] * members).upload(sc)
+    import ctypes as C
+    from nori_amd import _capi
+    whole, st = Renderer(0).upload(sc, builder=builder).render_host()
+    g = DeviceGroup([0] * members).upload(sc, builder=builder)
     assert g.size == members and g.transport == "copy"
+    for i in range(members):
+        info = _capi.AccelInfo()
+        assert g._lib.nori_hip_accel_info(g._lib.nori_hip_group_ctx(g._h, i), C.byref(info)) == 0
+        assert info.as_dict()["built_on_device"] == (1 if builder == 2 else 0), (i, info.as_dict())
     got, gst, merge_ms = g.render_host(split, merge)
     assert gst["n_camera_samples"] == st["n_camera_samples"]
     assert gst["n_closest_rays"] == st["n_closest_rays"] and gst["n_shadow_rays"] == st["n_shadow_rays"]
