@@ -21,12 +21,24 @@
  * src/block.cpp:62-102): per 32x32 block, source pixel after source pixel in raster order, sample after sample, each
  * (value * wx) * wy into the block's own accumulator -- and the blocks into the frame in BlockGenerator's spiral order
  * (src/block.cpp:109-152).  Float addition is not associative, so the two differ in the last bits.
- * film_reference_order reproduces the reference's order: one workgroup per 32x32 block, one thread per pixel of the
- * block's bordered accumulator walking the source pixels that reach it in raster order and their samples in index
- * order; then every frame pixel adds the (at most four) blocks that cover it by ascending spiral rank.  With
- * bit-identical radiance per camera sample the FRAME is then bit-identical to a single-threaded
- * render of the CPU oracle.  Slower (every sample is read by up to 25 threads straight from the store): a mode for
- * comparisons, not the default.
+ * film_reference_order reproduces the reference's order with one workgroup per 32x32 block, by one of two kernels:
+ *   film_block_reference_staged_kernel  the one that runs.  A thread owns output pixels of a ring of 2 border + 1
+ *                 accumulator rows; per source row and horizontal tap the row's samples are staged through LDS a chunk
+ *                 at a time (32 samples of every source pixel; 16 for filters of more than 11 taps), premultiplied by
+ *                 wx, and each thread adds its own source pixel's samples of the chunk in index order.  A sample is
+ *                 fetched 2 border + 1 times.
+ *   film_block_reference_kernel  the first implementation, kept for A / B (NORI_HIP_FILM_REF_UNSTAGED, read once per
+ *                 process): one thread per pixel of the block's bordered accumulator walking the source pixels that
+ *                 reach it in raster order and their samples in index order, straight from the store -- every sample
+ *                 is read by up to (2 border + 1)^2 threads, 25 under the default filter.
+ * Both add the same terms in the same order, so they give the same bits.  Then every frame pixel adds the (at most
+ * four) blocks that cover it by ascending spiral rank.  With bit-identical radiance per camera sample (DESIGN.md
+ * section 5) the FRAME is then bit-identical to a single-threaded render of the CPU oracle.  Slower than the fast
+ * path: a mode for comparisons, not the default.
+ *
+ * What the suite holds the two films to (tests/test_gpu_film.py): the reference order to the oracle's bits; the fast
+ * path, at every pixel of the bordered frame, to the first-order summation bound |F - S| <= (n + 16) 2^-24 sum |term|
+ * around the oracle's binary64 film S of the same n terms (oracle/oracle.h: oracle_render_f64).
  */
 #pragma once
 #include <string>

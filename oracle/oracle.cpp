@@ -227,9 +227,68 @@ int oracle_splat(oracle_ctx *ctx, const float *positions, const float *values, s
     return NORI_OK;
 }
 
-int oracle_render(oracle_ctx *ctx, const nori_render_params *params, float *rgbw,
-                  nori_render_stats *stats, int threads) {
-    if (!ctx || !params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;
+} // extern "C"
+
+/* ---- binary64 film (oracle_render_f64) ----
+ * The same camera samples, put through the same DECISIONS as ImageBlock::put (the isValid() guard, the block-relative
+ * float32 position, the ceil / floor bounding box, the float32 filter-table weights), but every term is formed and added
+ * in binary64: (double) v * (double) wx * (double) wy is exact to ~2^-53, so `sum` is the value any float32 film
+ * approximates, `abs_sum` the sum of the terms' magnitudes and `terms` their number -- what a first-order summation
+ * bound needs (tests/test_gpu_parity.py: assert_within_summation_bound). */
+namespace {
+
+struct F64Film {
+    double *sum = nullptr, *abs_sum = nullptr;      /* rows x cols x 4 of the bordered frame */
+    uint32_t *terms = nullptr;                      /* rows x cols */
+    int cols = 0;
+    std::mutex mutex;
+};
+
+struct F64Block {
+    std::vector<double> sum, abs_sum;
+    std::vector<uint32_t> terms;
+    explicit F64Block(const ImageBlock &b) : sum((size_t) b.rows * b.cols * 4), abs_sum(sum.size()), terms((size_t) b.rows * b.cols) {}
+    void clear() { std::fill(sum.begin(), sum.end(), 0.0); std::fill(abs_sum.begin(), abs_sum.end(), 0.0); std::fill(terms.begin(), terms.end(), 0u); }
+
+    /* ImageBlock::put(pos, value), src/block.cpp:62-91, in the geometry of `b` */
+    void put(const ImageBlock &b, const Vec2 &_pos, const Color3 &value) {
+        if (!isValidColor(value)) return;
+        Vec2 pos(_pos.x - 0.5f - (b.offX - b.border), _pos.y - 0.5f - (b.offY - b.border));
+        int minX = (int) std::ceil(pos.x - b.filterRadius), minY = (int) std::ceil(pos.y - b.filterRadius);
+        int maxX = (int) std::floor(pos.x + b.filterRadius), maxY = (int) std::floor(pos.y + b.filterRadius);
+        minX = std::max(minX, 0); minY = std::max(minY, 0);
+        maxX = std::min(maxX, b.cols - 1); maxY = std::min(maxY, b.rows - 1);
+        const double v[4] = {(double) value.x, (double) value.y, (double) value.z, 1.0};
+        for (int y = minY; y <= maxY; ++y) {
+            const float wy = b.filter[(int) (std::abs(y - pos.y) * b.lookupFactor)];
+            for (int x = minX; x <= maxX; ++x) {
+                const float wx = b.filter[(int) (std::abs(x - pos.x) * b.lookupFactor)];
+                const size_t i = (size_t) y * b.cols + x;
+                for (int c = 0; c < 4; ++c) {
+                    const double t = v[c] * (double) wx * (double) wy;
+                    sum[i * 4 + c] += t; abs_sum[i * 4 + c] += std::abs(t);
+                }
+                ++terms[i];
+            }
+        }
+    }
+
+    /* ImageBlock::put(ImageBlock&), src/block.cpp:93-102 (the frame's ImageBlock has offset 0 and the same border) */
+    void merge_into(F64Film &f, const ImageBlock &b) {
+        const int sx = b.sizeX + 2 * b.border, sy = b.sizeY + 2 * b.border;
+        std::lock_guard<std::mutex> lock(f.mutex);
+        for (int y = 0; y < sy; ++y)
+            for (int x = 0; x < sx; ++x) {
+                const size_t s = (size_t) y * b.cols + x, d = (size_t) (b.offY + y) * f.cols + (b.offX + x);
+                for (int c = 0; c < 4; ++c) { f.sum[d * 4 + c] += sum[s * 4 + c]; f.abs_sum[d * 4 + c] += abs_sum[s * 4 + c]; }
+                f.terms[d] += terms[s];
+            }
+    }
+};
+
+/* oracle_render (rgbw set, f64 null: the float film, untouched by the binary64 one) and oracle_render_f64 (f64 set) */
+int render_impl(oracle_ctx *ctx, const nori_render_params *params, float *rgbw, F64Film *f64,
+                nori_render_stats *stats, int threads) {
     if (params->tile_mod == 0 || params->tile_rem >= params->tile_mod) return NORI_ERR_INVALID_ARGUMENT;
     Scene &sc = *ctx->scene;
     const bool noriMode = params->seed_mode == NORI_SEED_NORI_BLOCK;
@@ -249,6 +308,7 @@ int oracle_render(oracle_ctx *ctx, const nori_render_params *params, float *rgbw
 
     auto worker = [&]() {
         ImageBlock block(kBlockSize, kBlockSize, &sc.rfilter);
+        std::unique_ptr<F64Block> block64(f64 ? new F64Block(block) : nullptr);
         Sampler sampler;
         RayCounter rc;
         Integrator integ(&sc, &rc);
@@ -258,6 +318,7 @@ int oracle_render(oracle_ctx *ctx, const nori_render_params *params, float *rgbw
             /* renderBlock, src/main.cpp:27-56 */
             block.clear();
             block.invalid = 0;
+            if (block64) block64->clear();
             for (int y = 0; y < block.sizeY; ++y) {
                 for (int x = 0; x < block.sizeX; ++x) {
                     int px = x + block.offX, py = y + block.offY;
@@ -277,11 +338,13 @@ int oracle_render(oracle_ctx *ctx, const nori_render_params *params, float *rgbw
                         sc.camera.sampleRay(ray, pixelSample);
                         Color3 value = integ.Li(sampler, ray);
                         block.put(pixelSample, value);
+                        if (block64) block64->put(block, pixelSample, value);
                         ++cam;
                     }
                 }
             }
             result.put(block);
+            if (block64) block64->merge_into(*f64, block);
         }
         nCamera += cam; nClosest += rc.closest; nShadow += rc.shadow;
     };
@@ -290,7 +353,7 @@ int oracle_render(oracle_ctx *ctx, const nori_render_params *params, float *rgbw
     for (auto &t : th) t.join();
     auto t1 = std::chrono::steady_clock::now();
 
-    for (size_t i = 0; i < result.px.size(); ++i) rgbw[i] += result.px[i];
+    if (rgbw) for (size_t i = 0; i < result.px.size(); ++i) rgbw[i] += result.px[i];
     if (stats) {
         std::memset(stats, 0, sizeof(*stats));
         stats->n_camera_samples = nCamera; stats->n_closest_rays = nClosest; stats->n_shadow_rays = nShadow;
@@ -300,6 +363,25 @@ int oracle_render(oracle_ctx *ctx, const nori_render_params *params, float *rgbw
     }
     sc.accel.countTests = false;
     return NORI_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int oracle_render(oracle_ctx *ctx, const nori_render_params *params, float *rgbw,
+                  nori_render_stats *stats, int threads) {
+    if (!ctx || !params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;
+    return render_impl(ctx, params, rgbw, nullptr, stats, threads);
+}
+
+int oracle_render_f64(oracle_ctx *ctx, const nori_render_params *params, double *sum, double *abs_sum, uint32_t *terms,
+                      nori_render_stats *stats, int threads) {
+    if (!ctx || !params || !sum || !abs_sum || !terms) return NORI_ERR_INVALID_ARGUMENT;
+    F64Film f;
+    f.sum = sum; f.abs_sum = abs_sum; f.terms = terms;
+    f.cols = ctx->scene->camera.width + 2 * oracle_border_size(ctx);
+    return render_impl(ctx, params, nullptr, &f, stats, threads);
 }
 
 /* src/block.cpp:45-51 + color.h:100-105 */

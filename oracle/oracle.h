@@ -66,6 +66,13 @@ int oracle_libm_eval(int op, const float *x, size_t n, float *out);
  * NORI_TILE_SIZE raster tiles as the device.  stats->kernel_ms = wall ms. */
 int oracle_render(oracle_ctx *ctx, const nori_render_params *params, float *rgbw,
                   nori_render_stats *stats, int threads);
+/* The binary64 film of the same render: the camera samples and every decision of ImageBlock::put as oracle_render
+ * takes them (isValid() guard, block-relative float32 position, bounding box, float32 filter-table weights; params
+ * honoured alike), each term (double) v * (double) wx * (double) wy, v = (r, g, b, 1), added in binary64.  Per pixel of
+ * the bordered frame (rows x cols, accumulated INTO the arrays): sum[4], abs_sum[4] = sum of |term|, terms = number of
+ * (sample, pixel) terms.  What a float32 film of any summation order is held to (tests: assert_within_summation_bound). */
+int oracle_render_f64(oracle_ctx *ctx, const nori_render_params *params, double *sum, double *abs_sum, uint32_t *terms,
+                      nori_render_stats *stats, int threads);
 int oracle_develop(const oracle_ctx *ctx, const float *rgbw, float *rgb);
 
 #ifdef __cplusplus

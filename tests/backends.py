@@ -87,6 +87,7 @@ def oracle_lib():
             "oracle_fresnel": (C.c_float, [C.c_float, C.c_float, C.c_float]),
             "oracle_libm_eval": (C.c_int, [C.c_int, _P, C.c_size_t, _P]),
             "oracle_render": (C.c_int, [_P, C.POINTER(capi.RenderParams), _P, C.POINTER(capi.RenderStats), C.c_int]),
+            "oracle_render_f64": (C.c_int, [_P, C.POINTER(capi.RenderParams), _P, _P, _P, C.POINTER(capi.RenderStats), C.c_int]),
             "oracle_develop": (C.c_int, [_P, _P, _P]),
         }
         _oracle = capi.bind(lib, protos)
@@ -295,6 +296,18 @@ class Oracle(_CpuBackend):
         rc = self.lib.oracle_render(self._h, C.byref(p), ptr(rgbw), C.byref(st), int(threads))
         assert rc == 0, rc
         return rgbw, st.as_dict()
+
+    def render_f64(self, spp_count=None, spp_begin=0, tile_mod=1, tile_rem=0, seed_mode=capi.SEED_PER_SAMPLE, threads=0):
+        """The binary64 film of render_host's frame (oracle.h: oracle_render_f64): per pixel and channel of the bordered frame the
+        sum of the terms v * wx * wy and of their magnitudes, float64 [rows, cols, 4] each, and per pixel their number, uint32
+        [rows, cols]; and the stats dict."""
+        p = self._params(spp_count, spp_begin, tile_mod, tile_rem, False, seed_mode)
+        shape = self.frame_shape()
+        total, abs_total, terms = np.zeros(shape, np.float64), np.zeros(shape, np.float64), np.zeros(shape[:2], np.uint32)
+        st = capi.RenderStats()
+        rc = self.lib.oracle_render_f64(self._h, C.byref(p), ptr(total), ptr(abs_total), ptr(terms), C.byref(st), int(threads))
+        assert rc == 0, rc
+        return total, abs_total, terms, st.as_dict()
 
     def develop(self, rgbw):
         c = self.scene.camera

@@ -59,6 +59,33 @@ def assert_image_parity(ref_rgbw, got_rgbw, border, what=""):
     return frac, mean_rel
 
 
+def assert_within_summation_bound(F, total, abs_total, terms, what=""):
+    """A float32 RGBW frame F against the binary64 film of the same render (Oracle.render_f64), at EVERY pixel of the
+    bordered frame and every channel:
+        |F - total| <= (terms + 16) u abs_total,  u = 2^-24;     F == 0 exactly where abs_total == 0.
+    A pixel's value is a sum of `terms` products v wx wy.  Each product is rounded at most twice and every addition a term
+    passes through rounds once, so -- to first order, for ANY order and grouping of the additions -- the error is at most
+    (n + 1) u sum |term|: a term passes through at most n - 1 additions that are not exact, because adding an exact 0 (an
+    empty part, a tile that does not reach the pixel, the cleared frame) rounds nothing.  The 16 is the allowance for the
+    merges (at most 8 part accumulators, 4 tiles or blocks, the frame add) and covers the second-order terms
+    ((1 + u)^n - 1 - n u < 4 u for the n <= 2^13 a test frame reaches).  Nothing in it is fitted to a measured error.
+    Prints and returns the worst error / bound."""
+    F = np.asarray(F)
+    assert F.dtype == np.float32 and F.shape == total.shape == abs_total.shape and terms.shape == F.shape[:2], what
+    assert np.isfinite(F).all(), what
+    bound = (terms[..., None].astype(np.float64) + 16.0) * 2.0 ** -24 * abs_total
+    err = np.abs(F.astype(np.float64) - total)
+    zero = abs_total == 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(zero, 0.0, err / bound)
+    worst = float(ratio.max()) if ratio.size else 0.0
+    print(f"[film bound] {what}: worst error / bound {worst:.3f}, {int(zero.any(axis=-1).sum())} pixels with a channel no term reaches")
+    assert not F[zero].any(), f"{what}: {int((F[zero] != 0).sum())} values differ from 0 where no term has weight"
+    bad = err > bound
+    assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} values outside the bound, worst error / bound {worst:.3f} at {np.unravel_index(np.argmax(ratio), ratio.shape)}"
+    return worst
+
+
 def test_native_library_is_loaded(renderer_factory):
     import os
     r = renderer_factory(scenes.soup_scene(8))
