@@ -15,6 +15,12 @@
  *   film_resolve  ImageBlock::put(ImageBlock&) (src/block.cpp:93-102): every
  *                 frame pixel gathers the <= 4 tile accumulators that cover it.
  * Deterministic: the same inputs give the same bits, independent of scheduling.
+ * film_gather runs one of two kernels that add the same terms in the same order, so they give the same bits:
+ *   film_gather_strips_kernel  border 1 and 2 (3 and 5 taps: tent, the default gaussian).  A thread owns a vertical
+ *                 strip of R output pixels in registers and walks the source rows that reach it over a zero-padded
+ *                 LDS image of the round: compile-time loop bounds, immediate LDS offsets, 2.6 LDS reads per tap.
+ *   film_gather_kernel  every other border (box; 7 to 17 taps), and every border with NORI_HIP_FILM_GATHER=rounds (A / B,
+ *                 read once per process): one output pixel at a time, run-time tap bounds, 5 LDS reads per tap.
  *
  * REFERENCE ORDER (option film_order = "reference").  The fast path above adds a pixel's samples round by round and
  * tap by tap; the reference adds them in the order of renderBlock / ImageBlock::put (src/main.cpp:33-53,

@@ -137,6 +137,180 @@ __global__ __launch_bounds__(kB) void film_gather_kernel(int width, int height, 
     if (tid == 0 && s_invalid) atomicAdd(st.d_invalid, (unsigned long long) s_invalid);
 }
 
+/* The same gather for border 1 and 2 (3 and 5 taps: tent, the default gaussian, every radius in (0.5, 2.5]) with the tap
+ * loops unrolled and fewer LDS reads per tap.  A thread of the tap phase owns a vertical STRIP of the bordered tile:
+ * column ox, rows oy0 .. oy0 + R - 1, R accumulators in registers.  Per round it walks the source rows sy that reach the
+ * strip from the highest (oy0 + R - 1) to the lowest (oy0 - 2 border), inside a row the horizontal taps k ascending, and
+ * for each source pixel r = (sy, ox - k) reads Lr, Lg, Lb and wx[k] ONCE, then for each output of the strip with
+ * m = oy - sy in [0, 2 border] reads wy[m][r] and does film_gather_kernel's five operations.  Border 2, R = 4:
+ * 8 rows x 5 taps x 4 + 100 = 260 LDS reads per 100 taps, 2.6 per tap against 5; every loop bound is a compile-time
+ * constant, every LDS offset an immediate: 5 vector-ALU instructions per tap against ~12.
+ *
+ * SAME BITS as film_gather_kernel.  An accumulator is a function of the sequence of terms it receives.  For a fixed output
+ * pixel film_gather_kernel's order within a round is m ascending (source row descending), then k ascending, and rounds
+ * go in ascending sample order; the walk above gives every output exactly that sequence (sy descending is m = oy - sy
+ * ascending).  The only difference: taps whose source lies outside the 16 x 16 tile, which film_gather_kernel's loop
+ * bounds skip, are executed here on zero PADDING of the staged arrays (no per-tap bounds test) -- w = (+0)(+0) = +0,
+ * fma(0, +0, acc) = acc + 0 and acc.w + 0 leave acc's bits alone: an accumulator starts at +0 and never becomes -0
+ * (x + y is -0 only if both are), and a rejected sample has L zeroed as before.  Weights, guards, the ftab index, the
+ * n_parts share, the tile_acc slot, the invalid count and the next-round prefetch are film_gather_kernel's; L is not
+ * premultiplied.  So tile_acc, hence the frame, has the parent kernel's bits for any n_parts, batch split and tile share
+ * (tests/test_gpu_film_gather_strips.py).
+ *
+ * LDS image: 3 + 2 taps planes (Lr, Lg, Lb, wx[k], wy[m]) of ROWS x STRIDE floats, source pixel (sy, sx) at
+ * (sy + 2 border) STRIDE + sx + 2 border; 2 border zero rows above, zero rows below down to the last strip's end, and
+ * 2 border zero columns between rows (a row's right padding is the next row's left padding, STRIDE >= 16 + 2 border).
+ * The planes are zeroed once; the rounds write the 256 interior cells only.  STRIDE is chosen so that the tap phase's
+ * ds_read_b32 (two groups of 32 lanes, 32 banks) has no bank conflict: lane l reads (l / tile_w) R STRIDE + l % tile_w +
+ * constant, and R STRIDE = tile_w (mod 32) lays the row segments of 32 consecutive lanes side by side in the banks.
+ * Staging stores are at worst 2-way conflicted, which a ds_write_b32 does not pay for.
+ *
+ * WG threads stage 256 / WG samples each.  The strips' owners are threads 0 .. strips x tile_w - 1; waves past them skip
+ * the tap phase. */
+/* The configurations that run: rows of a strip, workgroup size, row stride of the LDS image.  Chosen by the counts per tap (LDS
+   cycles, instructions), not yet by timing on the GPU; the alternatives that satisfy "three quarters of the tap phase's lanes own
+   outputs" and compile without scratch (DESIGN_HISTORY.md, the last section):
+     border 2:  4 / 128 / 21  100 of 128 lanes, 2.6 reads per tap, 26.4 KB LDS, 94 VGPRs: 6 workgroups = 12 waves per CU (LDS)   <-
+                4 / 256 / 21  one sample staged per thread, the taps by 2 of the 4 waves
+                2 / 256 / 26  200 of 256 lanes, 3.5 reads per tap, 32.7 KB, 70 VGPRs
+     border 1:  3 / 128 / 38  108 of 128 lanes, 2.33 reads per tap, 27.4 KB (stride 19: 13.8 KB, 7 LDS cycles per wave read for 4)   <-
+                2 / 256 / 25  162 of 192 lanes, 3 reads per tap
+                6 / 128 / 19  54 of 64 lanes, one tap wave, 1.67 reads per tap
+   Occupancy needed: the tap phase is unrolled with counted waits and the next round's samples are requested a round ahead, so
+   3 waves per SIMD (what 26 KB of LDS per 2-wave workgroup leave) cover the LDS latency; registers would allow 5. */
+constexpr int kStripRows2 = 4, kStripWg2 = 128, kStripStride2 = 21;
+constexpr int kStripRows1 = 3, kStripWg1 = 128, kStripStride1 = 38;
+
+template <int BORDER, int R, int WG, int STRIDE>
+struct FilmStrips {
+    static constexpr int taps = 2 * BORDER + 1, tile_w = kTile + 2 * BORDER;
+    static constexpr int strips = (tile_w + R - 1) / R, owners = strips * tile_w;
+    static constexpr int rows = strips * R + 2 * BORDER;
+    static constexpr int plane = rows * STRIDE + 2 * BORDER;          /* + the last row's right padding */
+    static constexpr int planes = 3 + 2 * taps;
+    static constexpr size_t lds_bytes = (size_t) planes * plane * sizeof(float);
+    static constexpr int spt = 256 / WG;                              /* samples staged per thread */
+    static_assert(STRIDE >= kTile + 2 * BORDER, "a row's right padding is the next row's left padding");
+    static_assert(WG == 128 || WG == 256, "two samples or one per thread");
+    static_assert(owners <= WG, "one strip per thread");
+    static_assert(4 * owners >= 3 * 64 * ((owners + 63) / 64), "three quarters of the tap phase's lanes own outputs");
+};
+
+template <int BORDER, int R, int WG, int STRIDE>
+__global__ __launch_bounds__(WG) void film_gather_strips_kernel(int width, int height, FilterRec fr, const float *__restrict__ filter_table,
+                                                                FilmStore st, FilmLaunch fl) {
+    using G = FilmStrips<BORDER, R, WG, STRIDE>;
+    constexpr int taps = G::taps, tile_w = G::tile_w, plane = G::plane, spt = G::spt;
+    extern __shared__ float s_dyn[];                          /* Lr, Lg, Lb, wx[taps], wy[taps]: planes of the padded tile */
+    __shared__ float ftab[kFilterRes + 1];
+    __shared__ unsigned int s_invalid;
+    const int tid = threadIdx.x;
+    if (tid <= kFilterRes) ftab[tid] = filter_table[tid];
+    if (tid == 0) s_invalid = 0u;
+    for (int i = tid; i < G::planes * plane; i += WG) s_dyn[i] = 0.0f;      /* the padding stays zero */
+
+    const uint32_t part = blockIdx.x % st.n_parts;
+    const uint32_t ord = fl.tile_first + blockIdx.x / st.n_parts;
+    const uint32_t tile_id = fl.tile_rem + ord * fl.tile_mod;
+    const int x0 = (int) (tile_id % fl.tiles_x) * kTile, y0 = (int) (tile_id / fl.tiles_x) * kTile;
+    constexpr int border = BORDER;
+    const float radius = fr.radius, lookup = fr.lookup_factor;
+    const int bx0 = x0 & ~31, by0 = y0 & ~31;                 /* NORI_BLOCK_SIZE = 32 */
+    const int offx = x0 - bx0, offy = y0 - by0;               /* tile frame -> block frame */
+
+    /* this thread's sample slots (pixels of the tile) and their cells in the planes */
+    bool live[spt]; int sxl[spt], syl[spt], cell[spt];
+#pragma unroll
+    for (int q = 0; q < spt; ++q) {
+        int px, py; film_tile_pixel(tid + q * WG, x0, y0, px, py);
+        live[q] = px < width && py < height;
+        sxl[q] = px - x0; syl[q] = py - y0; cell[q] = (syl[q] + 2 * BORDER) * STRIDE + sxl[q] + 2 * BORDER;
+    }
+
+    /* this thread's strip: column ox, rows oy0 .. oy0 + R - 1 of the bordered tile frame */
+    const bool owner = tid < G::owners;
+    const int ox = tid % tile_w, oy0 = (tid / tile_w) * R;
+    const float *strip = s_dyn + oy0 * STRIDE + ox;           /* source (oy0 + a, ox - k) of plane p at strip[p plane + (a + 2 border) STRIDE + 2 border - k] */
+    f4 acc[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) acc[j].x = acc[j].y = acc[j].z = acc[j].w = 0.0f;
+
+    const size_t first = (size_t) (ord - fl.store_tile_first) * fl.n_spp * 256u;
+    unsigned int invalid = 0;
+    __syncthreads();
+    /* this workgroup's share of the samples per pixel */
+    const uint32_t s_lo = (uint32_t) ((uint64_t) fl.n_spp * part / st.n_parts), s_hi = (uint32_t) ((uint64_t) fl.n_spp * (part + 1) / st.n_parts);
+    /* the NEXT round's samples are requested while this round's taps run, as in film_gather_kernel */
+    f2 p_next[spt]; P3 l_next[spt];
+#pragma unroll
+    for (int q = 0; q < spt; ++q) {
+        p_next[q] = mk2(0.0f, 0.0f); l_next[q].x = l_next[q].y = l_next[q].z = 0.0f;
+        if (live[q] && s_lo < s_hi) { const size_t i0 = first + (size_t) s_lo * 256u + (size_t) (tid + q * WG); p_next[q] = st.pos[i0]; l_next[q] = st.L[i0]; }
+    }
+    for (uint32_t s = s_lo; s < s_hi; ++s) {
+#pragma unroll
+        for (int q = 0; q < spt; ++q) {
+            f4 L; L.x = L.y = L.z = 0.0f;
+            bool ok = false;
+            float bpx = 0.0f, bpy = 0.0f;
+            const f2 p = p_next[q]; const P3 l3 = l_next[q];
+            if (live[q] && s + 1u < s_hi) { const size_t i1 = first + (size_t) (s + 1u) * 256u + (size_t) (tid + q * WG); p_next[q] = st.pos[i1]; l_next[q] = st.L[i1]; }
+            if (live[q]) {
+                L.x = l3.x; L.y = l3.y; L.z = l3.z;
+                ok = color_valid(mk3(L.x, L.y, L.z));
+                if (!ok) { ++invalid; L.x = L.y = L.z = 0.0f; }
+                bpx = p.x - 0.5f - (float) (bx0 - border);
+                bpy = p.y - 0.5f - (float) (by0 - border);
+            }
+            float *c = s_dyn + cell[q];
+            c[0] = L.x; c[plane] = L.y; c[2 * plane] = L.z;
+#pragma unroll
+            for (int k = 0; k < taps; ++k) {
+                const float xb = (float) (sxl[q] + k + offx), yb = (float) (syl[q] + k + offy);
+                const bool inx = ok && xb >= bpx - radius && xb <= bpx + radius;
+                const bool iny = ok && yb >= bpy - radius && yb <= bpy + radius;
+                c[(3 + k) * plane] = inx ? ftab[(int) (fabsf(xb - bpx) * lookup)] : 0.0f;
+                c[(3 + taps + k) * plane] = iny ? ftab[(int) (fabsf(yb - bpy) * lookup)] : 0.0f;
+            }
+        }
+        film_barrier();
+        if (owner) {
+#pragma unroll
+            for (int t = 0; t < R + 2 * BORDER; ++t) {                    /* source row sy = oy0 + a, descending */
+                const int a = R - 1 - t;
+#pragma unroll
+                for (int k = 0; k < taps; ++k) {
+                    const int off = (a + 2 * BORDER) * STRIDE + 2 * BORDER - k;
+                    const float lr = strip[off], lg = strip[plane + off], lb = strip[2 * plane + off], wx = strip[(3 + k) * plane + off];
+#pragma unroll
+                    for (int j = 0; j < R; ++j) {                         /* output row oy0 + j: vertical tap m = j - a */
+                        const int m = j - a;
+                        if (m < 0 || m >= taps) continue;
+                        /* value * (wx * wy), multiply-add fused: film_gather_kernel's five operations */
+                        const float w = wx * strip[(3 + taps + m) * plane + off];
+                        acc[j].x = __builtin_fmaf(lr, w, acc[j].x); acc[j].y = __builtin_fmaf(lg, w, acc[j].y);
+                        acc[j].z = __builtin_fmaf(lb, w, acc[j].z); acc[j].w += w;
+                    }
+                }
+            }
+        }
+        film_barrier();                                        /* round consumed */
+    }
+    if (owner) {
+        f4 *dst = reinterpret_cast<f4 *>(st.tile_acc) + ((size_t) ord * st.n_parts + part) * (tile_w * tile_w);
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+            if (oy0 + j >= tile_w) break;                      /* the last strip may overhang the tile */
+            f4 v = dst[(oy0 + j) * tile_w + ox];
+            v.x += acc[j].x; v.y += acc[j].y; v.z += acc[j].z; v.w += acc[j].w;
+            dst[(oy0 + j) * tile_w + ox] = v;
+        }
+    }
+    if (invalid) atomicAdd(&s_invalid, invalid);
+    __syncthreads();
+    if (tid == 0 && s_invalid) atomicAdd(st.d_invalid, (unsigned long long) s_invalid);
+}
+
 /* ImageBlock::put(ImageBlock&): every frame pixel gathers the (at most four) tile accumulators
    whose bordered area covers it, in a fixed order */
 __global__ void film_resolve_kernel(int width, int height, int border, int tile_w, uint32_t tiles_x, uint32_t tiles_y,
@@ -432,9 +606,22 @@ std::string film_prepare(FilmStore &g_film, size_t n_samples, size_t n_sel_tiles
     return std::string();
 }
 
+template <int BORDER, int R, int WG, int STRIDE>
+static void launch_strips(const DevScene &sc, const float *d_filter_table, const FilmStore &st, const FilmLaunch &fl, void *stream) {
+    using G = FilmStrips<BORDER, R, WG, STRIDE>;
+    hipLaunchKernelGGL((film_gather_strips_kernel<BORDER, R, WG, STRIDE>), dim3(fl.n_tiles * st.n_parts), dim3(WG), G::lds_bytes,
+                       (hipStream_t) stream, sc.camera.width, sc.camera.height, sc.filter, d_filter_table, st, fl);
+}
+
 void film_gather(const DevScene &sc, const float *d_filter_table, const FilmStore &st, const FilmLaunch &fl, void *stream) {
     if (fl.n_tiles == 0 || fl.n_spp == 0) return;
-    const size_t lds = (size_t) (2 * (2 * sc.filter.border + 1) + 3) * 256 * sizeof(float);
+    static const bool rounds = [] { const char *e = getenv("NORI_HIP_FILM_GATHER"); return e && std::string(e) == "rounds"; }();      /* A / B: film_gather_kernel for every border */
+    const int border = sc.filter.border;
+    if (!rounds && fl.tile_w == kTile + 2 * border) {
+        if (border == 2) return launch_strips<2, kStripRows2, kStripWg2, kStripStride2>(sc, d_filter_table, st, fl, stream);
+        if (border == 1) return launch_strips<1, kStripRows1, kStripWg1, kStripStride1>(sc, d_filter_table, st, fl, stream);
+    }
+    const size_t lds = (size_t) (2 * (2 * border + 1) + 3) * 256 * sizeof(float);
     hipLaunchKernelGGL(film_gather_kernel, dim3(fl.n_tiles * st.n_parts), dim3(kB), lds, (hipStream_t) stream, sc.camera.width, sc.camera.height,
                        sc.filter, d_filter_table, st, fl);
 }
