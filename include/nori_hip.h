@@ -460,6 +460,73 @@ int nori_hip_splat(nori_hip_ctx *ctx, const float *positions,
 int nori_hip_render(nori_hip_ctx *ctx, const nori_render_params *params,
                     void *d_rgbw, nori_render_stats *stats);
 
+/* ------------------------------------------- second moments, error map, render to a target error
+ *
+ * No counterpart in the reference, which has no measure of a frame's noise.
+ *
+ * nori_hip_render_moments is nori_hip_render, and the same samples' SECOND MOMENTS ADDED into d_m2, a DEVICE buffer with the
+ * layout of d_rgbw.  For every sample the film accepts and every pixel it reaches with tap weight w = wx wy (as the fast
+ * film forms it), the RGBW pixel receives (L w, w) and the moment pixel (float32(L_c L_c) w, float32(w w)): the square is
+ * rounded to float32 first, then fma(square, w, sum) like the beauty channels (a radiance above 1.8e19, whose square is
+ * not finite, enters as FLT_MAX).  Samples the isValid() guard rejects (src/block.cpp:63-67) reach neither frame.  The RGBW frame has
+ * the bits nori_hip_render gives with the same parameters and options; stats count the samples once.  All engines and
+ * seed modes; film_order must be "fast" (NORI_ERR_UNSUPPORTED otherwise -- nori_hip_render_block_rows keeps no moments
+ * either).  Moment frames of disjoint shares (tiles, sample ranges) add like RGBW frames.
+ * nori_hip_render_moments_host: both frames to zeroed HOST buffers, as nori_hip_render_host. */
+int nori_hip_render_moments(nori_hip_ctx *ctx, const nori_render_params *params,
+                            void *d_rgbw, void *d_m2, nori_render_stats *stats);
+int nori_hip_render_moments_host(nori_hip_ctx *ctx, const nori_render_params *params,
+                                 float *rgbw, float *m2, nori_render_stats *stats);
+
+/* The error map: per pixel of the frame WITHOUT the border, the relative standard error of the pixel's mean under the
+ * plug-in weighted variance.  With S the RGBW pixel and M the moment pixel, in float32 without FMA contraction, IEEE
+ * division and square root, in this order:
+ *   if !(S.w > 0): err = 0 and the pixel counts as empty; else
+ *   r = 1 / S.w;  k = (M.w * r) * r                               (1 / k = (sum w)^2 / sum w^2, the effective sample count)
+ *   num = 0; den = 0
+ *   for c in r, g, b:  mu = S.c * r;  q = M.c * r;  v = q - mu * mu;  if !(v > 0) v = 0
+ *                      num = num + sqrt(v * k);  den = den + |mu|
+ *   err = num / (den + 0.03f)
+ * Limits: below two samples per pixel the map means nothing (one sample has v = 0); the plug-in variance is biased low by
+ * the factor 1 - k; under filters with negative lobes (Mitchell) weights are not probabilities, the formula is applied
+ * as it stands, v clamped at 0 and pixels of W <= 0 counted as empty.
+ * d_err: height * width floats on the DEVICE, row-major, or NULL.  out: the summary, or NULL (one of the two must be
+ * given).  The summary is reduced on the device without floating-point atomics, in a fixed order -- sum_err in binary64,
+ * max_err and the counts exact -- so two calls on the same frames return the same bytes.  With out != NULL the call
+ * synchronises `stream`; otherwise it is asynchronous on it, uses nothing of the context's and may run on several
+ * streams at once.  (Like every call, a summary call must not overlap another call on the same context from a second
+ * thread.)  n_above counts frame pixels only, whatever the sign of `threshold`. */
+typedef struct nori_error_summary {
+    double   sum_err;      /* sum of err over the frame's pixels */
+    float    max_err;
+    float    threshold;    /* as passed in */
+    uint64_t n_pixels, n_empty, n_above;   /* n_above: err > threshold */
+} nori_error_summary;
+int nori_hip_error_map(nori_hip_ctx *ctx, const void *d_rgbw, const void *d_m2,
+                       void *d_err /* height*width floats, may be NULL */,
+                       float threshold, nori_error_summary *out, void *stream);
+/* Convenience: the same for frames and a map in HOST memory (copied to scratch device buffers and back; synchronous). */
+int nori_hip_error_map_host(nori_hip_ctx *ctx, const float *rgbw, const float *m2, float *err /* may be NULL */,
+                            float threshold, nori_error_summary *out);
+
+/* Render until the frame is good enough: samples [spp_begin, spp_begin + spp_count) -- spp_count is the most the call may
+ * spend -- in passes of pass_spp (the last may be shorter) through nori_hip_render_moments, ADDING into d_rgbw and d_m2.
+ * From the second pass on the error map is evaluated after each pass (threshold = target_mean_err); the call stops when
+ * sum_err / n_pixels <= target_mean_err or the samples are spent.  Sampling is uniform over the frame.  *spp_done = samples
+ * per pixel rendered; *last = the summary of the frames as they are left (evaluated once at the end if no pass did);
+ * stats: counters and times summed over the passes, the rest as of the last pass.  Any of the three may be NULL.
+ * params->tile_mod must be 1, pass_spp >= 1, target_mean_err >= 0 (NORI_ERR_INVALID_ARGUMENT).  Synchronous. */
+int nori_hip_render_to_error(nori_hip_ctx *ctx, const nori_render_params *params /* spp_count = the most it may spend */,
+                             uint32_t pass_spp, float target_mean_err,
+                             void *d_rgbw, void *d_m2, uint32_t *spp_done,
+                             nori_error_summary *last, nori_render_stats *stats);
+
+/* Convenience, as nori_hip_render_host: the same loop into scratch device frames; the RGBW frame, and where the pointers are not
+ * NULL the moment frame and the error map (height * width floats) of the frames as they are left, to HOST buffers (overwritten). */
+int nori_hip_render_to_error_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_mean_err,
+                                  float *rgbw, float *m2, float *err, uint32_t *spp_done,
+                                  nori_error_summary *last, nori_render_stats *stats);
+
 /* film_order = "reference" shared out over devices or ranks.  The reference adds a 32x32 block's samples consecutively
  * into the block's own ImageBlock (renderBlock, src/main.cpp:27-55) and the blocks into the frame in BlockGenerator's order
  * (src/block.cpp:93-152): the smallest share that keeps the order is a block, the one handed out here is a ROW of blocks.

@@ -98,6 +98,15 @@ class RenderStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ErrorSummary(C.Structure):
+    """nori_error_summary"""
+    _fields_ = [("sum_err", C.c_double), ("max_err", C.c_float), ("threshold", C.c_float),
+                ("n_pixels", C.c_uint64), ("n_empty", C.c_uint64), ("n_above", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class AccelInfo(C.Structure):
     _fields_ = [("n_triangles", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("max_depth", C.c_uint32), ("node_bytes", C.c_uint32), ("tri_bytes", C.c_uint32),
@@ -152,6 +161,14 @@ HIP_PROTOTYPES = {
     "nori_hip_splat": (C.c_int, [_P, _P, _P, C.c_size_t, _P]),
     "nori_hip_render": (C.c_int, [_P, C.POINTER(RenderParams), _P, C.POINTER(RenderStats)]),
     "nori_hip_render_host": (C.c_int, [_P, C.POINTER(RenderParams), _P, C.POINTER(RenderStats)]),
+    "nori_hip_render_moments": (C.c_int, [_P, C.POINTER(RenderParams), _P, _P, C.POINTER(RenderStats)]),
+    "nori_hip_render_moments_host": (C.c_int, [_P, C.POINTER(RenderParams), _P, _P, C.POINTER(RenderStats)]),
+    "nori_hip_error_map": (C.c_int, [_P, _P, _P, _P, C.c_float, C.POINTER(ErrorSummary), _P]),
+    "nori_hip_error_map_host": (C.c_int, [_P, _P, _P, _P, C.c_float, C.POINTER(ErrorSummary)]),
+    "nori_hip_render_to_error": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_float, _P, _P, C.POINTER(C.c_uint32),
+                                           C.POINTER(ErrorSummary), C.POINTER(RenderStats)]),
+    "nori_hip_render_to_error_host": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_float, _P, _P, _P, C.POINTER(C.c_uint32),
+                                                C.POINTER(ErrorSummary), C.POINTER(RenderStats)]),
     "nori_hip_develop": (C.c_int, [_P, _P, _P, _P]),
     "nori_hip_block_acc_floats": (C.c_int, [_P, C.POINTER(C.c_size_t)]),
     "nori_hip_render_block_rows": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_uint32, _P, C.POINTER(RenderStats)]),

@@ -22,6 +22,14 @@
  *   film_gather_kernel  every other border (box; 7 to 17 taps), and every border with NORI_HIP_FILM_GATHER=rounds (A / B,
  *                 read once per process): one output pixel at a time, run-time tap bounds, 5 LDS reads per tap.
  *
+ * SECOND MOMENTS (nori_hip_render_moments).  A render that keeps moments runs every gather twice over the store: the pass
+ * above, then the same kernel's moments form (film_gather_m2_kernel / film_gather_strips_m2_kernel: one body, a template
+ * flag) with float32(L_c L_c) staged in place of L_c and float32(w w) added in place of w, into a second set of tile
+ * accumulators (FilmMoments, beside the FilmStore; the moments form gets a view of the store whose tile_acc is the second set);
+ * film_resolve_moments adds them into the moment frame.  A second pass rather than more accumulators in the one
+ * gather: the beauty kernels -- their registers, LDS and bits -- stay exactly what a plain render runs, the strip kernel
+ * keeps its 94 VGPRs, and the pass re-reads 20 B per sample from a store that was just read.  The fast film only.
+ *
  * REFERENCE ORDER (option film_order = "reference").  The fast path above adds a pixel's samples round by round and
  * tap by tap; the reference adds them in the order of renderBlock / ImageBlock::put (src/main.cpp:33-53,
  * src/block.cpp:62-102): per 32x32 block, source pixel after source pixel in raster order, sample after sample, each
@@ -69,6 +77,21 @@ struct FilmStore {
     uint32_t rank_bx = 0, rank_by = 0;   /* the block grid the ranks on the device were computed for (uploaded once per frame geometry) */
 };
 
+/* What a context holds for second moments and the error map, beside its FilmStore (which a plain render uses as before):
+   a second set of tile accumulators in the layout of tile_acc, and the partial sums of film_error_map. */
+struct FilmMoments {
+    float *tile_acc2 = nullptr;
+    size_t acc2_floats = 0;
+    void *err_partials = nullptr;
+    size_t err_blocks = 0;
+};
+
+/* nori_error_summary without the caller's threshold (include/nori_hip.h) */
+struct FilmErrorSummary {
+    double sum_err = 0.0; float max_err = 0.0f;
+    unsigned long long n_pixels = 0, n_empty = 0, n_above = 0;
+};
+
 struct FilmLaunch {
     uint32_t tile_first, n_tiles;   /* ordinals (within the selected tiles) handled by this gather */
     uint32_t store_tile_first;      /* ordinal of the tile whose samples start at index 0 of the store */
@@ -91,6 +114,18 @@ std::string film_prepare(FilmStore &store, size_t n_samples, size_t n_sel_tiles,
 void film_gather(const DevScene &sc, const float *d_filter_table, const FilmStore &st, const FilmLaunch &fl, void *stream);
 /* add all accumulators into the caller's RGBW frame */
 void film_resolve(const DevScene &sc, const FilmStore &st, const FilmLaunch &fl, float *d_rgbw, void *stream);
+/* Second moments (renders that keep them only).  film_moments_prepare, after film_prepare of the same render: (re)allocates and
+   zeroes the second set of accumulators for the view's n_parts.  film_gather_moments, right behind film_gather of the same
+   view and launch on the same stream (before anything can overwrite the store): the second pass.  film_resolve_moments adds the
+   second set into the moment frame. */
+std::string film_moments_prepare(FilmMoments &m, const FilmStore &view, size_t n_sel_tiles, int tile_w, void *stream);
+void film_gather_moments(const DevScene &sc, const float *d_filter_table, const FilmStore &st, const FilmMoments &m, const FilmLaunch &fl, void *stream);
+void film_resolve_moments(const DevScene &sc, const FilmStore &st, const FilmMoments &m, const FilmLaunch &fl, float *d_m2, void *stream);
+void film_moments_release(FilmMoments &m);
+/* The per-pixel error map of an (RGBW, moments) pair of frames and its summary (nori_hip_error_map): d_err (height x width floats) and
+   `out` may each be null.  With `out` the call synchronises `stream`.  "" or an error. */
+std::string film_error_map(FilmMoments &store, const DevScene &sc, const float *d_rgbw, const float *d_m2, float *d_err, float threshold,
+                           FilmErrorSummary *out, void *stream);
 /* A share of the reference-order film for one of several devices: whole ROWS of 32x32 blocks (a block's samples are added
    consecutively, so a block is the smallest share), i.e. the contiguous range of 16x16 tiles from
    film_block_rows_first_tile(row_begin) on.  With block_acc set, the call stops after the blocks: it writes the accumulators of

@@ -18,6 +18,13 @@ constexpr int kMaxBorder = 8;                  /* (16 + 2 * 8)^2 / 256 = 4 outpu
 /* a workgroup barrier that waits for LDS only (what film_gather's rounds exchange lives there) */
 __device__ __forceinline__ void film_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+/* the moments passes stage float32(L_c L_c).  A finite radiance above 1.8e19 has no finite square: it is staged as FLT_MAX, so that a
+   tap out of the filter's reach still adds FLT_MAX (+0) = +0 where inf (+0) would poison the accumulator with a NaN */
+__device__ __forceinline__ f4 film_square(f4 L) {
+    f4 q; q.x = fminf(L.x * L.x, 3.402823466e38f); q.y = fminf(L.y * L.y, 3.402823466e38f); q.z = fminf(L.z * L.z, 3.402823466e38f); q.w = 0.0f;
+    return q;
+}
+
 /* ImageBlock::put(pos, value) as a gather.  Sample round by sample round, the tile's 256 current
  * samples are staged in LDS together with their 1-D filter weights; then every pixel of the tile's
  * bordered block (tile_w^2 pixels, <= 4 per thread) adds the samples that can reach it.  Weights follow
@@ -30,8 +37,9 @@ __device__ __forceinline__ void film_barrier() { asm volatile("s_waitcnt lgkmcnt
  * A sample of tile pixel (sx, sy) reaches the output pixels (sx + k, sy + m), k, m in [0, 2 border]
  * of the bordered tile frame: 2 border + 1 taps per axis, zero where out of the filter's reach or
  * for samples the isValid() guard (block.cpp:63-67) rejects. */
-__global__ __launch_bounds__(kB) void film_gather_kernel(int width, int height, FilterRec fr, const float *__restrict__ filter_table,
-                                                         FilmStore st, FilmLaunch fl) {
+template <bool M2>
+__device__ __forceinline__ void film_gather_body(int width, int height, const FilterRec &fr, const float *__restrict__ filter_table,
+                                                 const FilmStore &st, const FilmLaunch &fl) {
     extern __shared__ float s_dyn[];                          /* [taps][256] wx, [taps][256] wy, r, g, b */
     __shared__ float ftab[kFilterRes + 1];
     __shared__ unsigned int s_invalid;
@@ -90,6 +98,7 @@ __global__ __launch_bounds__(kB) void film_gather_kernel(int width, int height, 
                 L.x = l3.x; L.y = l3.y; L.z = l3.z;
                 ok = color_valid(mk3(L.x, L.y, L.z));
                 if (!ok) { ++invalid; L.x = L.y = L.z = 0.0f; }
+                if constexpr (M2) L = film_square(L);
                 bpx = p.x - 0.5f - (float) (bx0 - border);
                 bpy = p.y - 0.5f - (float) (by0 - border);
             }
@@ -118,13 +127,14 @@ __global__ __launch_bounds__(kB) void film_gather_kernel(int width, int height, 
                        film_order = reference keeps order and products exactly. */
                     const float w = s_wx[k][r] * wy_row[r];
                     acc[o].x = __builtin_fmaf(s_Lr[r], w, acc[o].x); acc[o].y = __builtin_fmaf(s_Lg[r], w, acc[o].y);
-                    acc[o].z = __builtin_fmaf(s_Lb[r], w, acc[o].z); acc[o].w += w;
+                    acc[o].z = __builtin_fmaf(s_Lb[r], w, acc[o].z);
+                    if constexpr (M2) acc[o].w += w * w; else acc[o].w += w;
                 }
             }
         }
         film_barrier();                                        /* round consumed */
     }
-    f4 *dst = reinterpret_cast<f4 *>(st.tile_acc) + ((size_t) ord * st.n_parts + part) * n_out;
+    f4 *dst = reinterpret_cast<f4 *>(st.tile_acc) + ((size_t) ord * st.n_parts + part) * n_out;      /* (M2: the launch's view names the second set) */
     for (int o = 0; o < kMaxOut; ++o) {
         const int i = tid + o * kB;
         if (i >= n_out) break;
@@ -132,9 +142,22 @@ __global__ __launch_bounds__(kB) void film_gather_kernel(int width, int height, 
         v.x += acc[o].x; v.y += acc[o].y; v.z += acc[o].z; v.w += acc[o].w;
         dst[i] = v;
     }
+    if constexpr (M2) return;                                  /* (the first pass over the store has counted the rejected samples) */
     if (invalid) atomicAdd(&s_invalid, invalid);
     __syncthreads();
     if (tid == 0 && s_invalid) atomicAdd(st.d_invalid, (unsigned long long) s_invalid);
+}
+
+__global__ __launch_bounds__(kB) void film_gather_kernel(int width, int height, FilterRec fr, const float *__restrict__ filter_table,
+                                                         FilmStore st, FilmLaunch fl) {
+    film_gather_body<false>(width, height, fr, filter_table, st, fl);
+}
+
+/* The SECOND MOMENTS of the same samples, a second pass over the store (film.h): film_gather_kernel with float32(L_c L_c) staged in
+   place of L_c and float32(w w) added in place of w -- the same taps, weights, guards, order and n_parts share, into tile_acc2. */
+__global__ __launch_bounds__(kB) void film_gather_m2_kernel(int width, int height, FilterRec fr, const float *__restrict__ filter_table,
+                                                            FilmStore st, FilmLaunch fl) {
+    film_gather_body<true>(width, height, fr, filter_table, st, fl);
 }
 
 /* The same gather for border 1 and 2 (3 and 5 taps: tent, the default gaussian, every radius in (0.5, 2.5]) with the tap
@@ -196,9 +219,9 @@ struct FilmStrips {
     static_assert(4 * owners >= 3 * 64 * ((owners + 63) / 64), "three quarters of the tap phase's lanes own outputs");
 };
 
-template <int BORDER, int R, int WG, int STRIDE>
-__global__ __launch_bounds__(WG) void film_gather_strips_kernel(int width, int height, FilterRec fr, const float *__restrict__ filter_table,
-                                                                FilmStore st, FilmLaunch fl) {
+template <int BORDER, int R, int WG, int STRIDE, bool M2>
+__device__ __forceinline__ void film_gather_strips_body(int width, int height, const FilterRec &fr, const float *__restrict__ filter_table,
+                                                        const FilmStore &st, const FilmLaunch &fl) {
     using G = FilmStrips<BORDER, R, WG, STRIDE>;
     constexpr int taps = G::taps, tile_w = G::tile_w, plane = G::plane, spt = G::spt;
     extern __shared__ float s_dyn[];                          /* Lr, Lg, Lb, wx[taps], wy[taps]: planes of the padded tile */
@@ -259,6 +282,7 @@ __global__ __launch_bounds__(WG) void film_gather_strips_kernel(int width, int h
                 L.x = l3.x; L.y = l3.y; L.z = l3.z;
                 ok = color_valid(mk3(L.x, L.y, L.z));
                 if (!ok) { ++invalid; L.x = L.y = L.z = 0.0f; }
+                if constexpr (M2) L = film_square(L);
                 bpx = p.x - 0.5f - (float) (bx0 - border);
                 bpy = p.y - 0.5f - (float) (by0 - border);
             }
@@ -289,7 +313,8 @@ __global__ __launch_bounds__(WG) void film_gather_strips_kernel(int width, int h
                         /* value * (wx * wy), multiply-add fused: film_gather_kernel's five operations */
                         const float w = wx * strip[(3 + taps + m) * plane + off];
                         acc[j].x = __builtin_fmaf(lr, w, acc[j].x); acc[j].y = __builtin_fmaf(lg, w, acc[j].y);
-                        acc[j].z = __builtin_fmaf(lb, w, acc[j].z); acc[j].w += w;
+                        acc[j].z = __builtin_fmaf(lb, w, acc[j].z);
+                        if constexpr (M2) acc[j].w += w * w; else acc[j].w += w;
                     }
                 }
             }
@@ -297,7 +322,7 @@ __global__ __launch_bounds__(WG) void film_gather_strips_kernel(int width, int h
         film_barrier();                                        /* round consumed */
     }
     if (owner) {
-        f4 *dst = reinterpret_cast<f4 *>(st.tile_acc) + ((size_t) ord * st.n_parts + part) * (tile_w * tile_w);
+        f4 *dst = reinterpret_cast<f4 *>(st.tile_acc) + ((size_t) ord * st.n_parts + part) * (tile_w * tile_w);      /* (M2: the launch's view names the second set) */
 #pragma unroll
         for (int j = 0; j < R; ++j) {
             if (oy0 + j >= tile_w) break;                      /* the last strip may overhang the tile */
@@ -306,9 +331,24 @@ __global__ __launch_bounds__(WG) void film_gather_strips_kernel(int width, int h
             dst[(oy0 + j) * tile_w + ox] = v;
         }
     }
+    if constexpr (M2) return;                                  /* (the first pass over the store has counted the rejected samples) */
     if (invalid) atomicAdd(&s_invalid, invalid);
     __syncthreads();
     if (tid == 0 && s_invalid) atomicAdd(st.d_invalid, (unsigned long long) s_invalid);
+}
+
+template <int BORDER, int R, int WG, int STRIDE>
+__global__ __launch_bounds__(WG) void film_gather_strips_kernel(int width, int height, FilterRec fr, const float *__restrict__ filter_table,
+                                                                FilmStore st, FilmLaunch fl) {
+    film_gather_strips_body<BORDER, R, WG, STRIDE, false>(width, height, fr, filter_table, st, fl);
+}
+
+/* the strips form of film_gather_m2_kernel: second moments into tile_acc2, the bits film_gather_m2_kernel gives (the argument above
+   holds for the squares: the padding is zero, and a staged square is finite) */
+template <int BORDER, int R, int WG, int STRIDE>
+__global__ __launch_bounds__(WG) void film_gather_strips_m2_kernel(int width, int height, FilterRec fr, const float *__restrict__ filter_table,
+                                                                   FilmStore st, FilmLaunch fl) {
+    film_gather_strips_body<BORDER, R, WG, STRIDE, true>(width, height, fr, filter_table, st, fl);
 }
 
 /* ImageBlock::put(ImageBlock&): every frame pixel gathers the (at most four) tile accumulators
@@ -337,6 +377,79 @@ __global__ void film_resolve_kernel(int width, int height, int border, int tile_
     float4 cur = *dst;
     cur.x += sum.x; cur.y += sum.y; cur.z += sum.z; cur.w += sum.w;
     *dst = cur;
+}
+
+/* ---- error map ---- */
+
+/* per-workgroup (and, slot 0, whole-frame) sums of the error map */
+struct FilmErrorPartial { double sum; float max; uint32_t pad; unsigned long long n_empty, n_above; };
+
+/* adds the 256 partials of a workgroup in a fixed tree: lane t takes lane t + off for off = 128, 64, ..., 1.  No atomics: the same
+   inputs give the same bytes. */
+__device__ __forceinline__ void film_error_tree(double *s_sum, float *s_max, unsigned long long *s_empty64, unsigned long long *s_above64, int tid,
+                                                double sum, float mx, unsigned long long n_empty, unsigned long long n_above, FilmErrorPartial *out) {
+    s_sum[tid] = sum; s_max[tid] = mx; s_empty64[tid] = n_empty; s_above64[tid] = n_above;
+    __syncthreads();
+    for (int off = kB / 2; off > 0; off >>= 1) {
+        if (tid < off) {
+            s_sum[tid] += s_sum[tid + off]; s_max[tid] = fmaxf(s_max[tid], s_max[tid + off]);
+            s_empty64[tid] += s_empty64[tid + off]; s_above64[tid] += s_above64[tid + off];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) { FilmErrorPartial p; p.sum = s_sum[0]; p.max = s_max[0]; p.pad = 0u; p.n_empty = s_empty64[0]; p.n_above = s_above64[0]; *out = p; }
+}
+
+/* The relative standard error of every frame pixel's mean (include/nori_hip.h: nori_hip_error_map states the formula operation by
+   operation; float32, no contraction, IEEE division and square root -- hipcc's correctly rounded default), one thread per pixel
+   of the frame without its border, and the workgroup's partial sums. */
+__global__ __launch_bounds__(kB) void film_error_map_kernel(int width, int height, int border, const float *__restrict__ rgbw, const float *__restrict__ m2,
+                                                            float *__restrict__ err_out, float threshold, FilmErrorPartial *partials) {
+    __shared__ double s_sum[kB];
+    __shared__ float s_max[kB];
+    __shared__ unsigned long long s_empty[kB], s_above[kB];
+    const int tid = threadIdx.x;
+    const size_t i = (size_t) blockIdx.x * kB + (size_t) tid, n = (size_t) width * (size_t) height;
+    float err = 0.0f;
+    bool empty = false;
+    if (i < n) {
+        const int y = (int) (i / (size_t) width), x = (int) (i - (size_t) y * (size_t) width);
+        const size_t at = ((size_t) (y + border) * (size_t) (width + 2 * border) + (size_t) (x + border)) * 4;
+        const float4 S = *reinterpret_cast<const float4 *>(rgbw + at), M = *reinterpret_cast<const float4 *>(m2 + at);
+        if (!(S.w > 0.0f)) empty = true;
+        else {
+            const float r = 1.0f / S.w, k = (M.w * r) * r;
+            float num = 0.0f, den = 0.0f;
+            const float Sc[3] = {S.x, S.y, S.z}, Mc[3] = {M.x, M.y, M.z};
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float mu = Sc[c] * r, q = Mc[c] * r;
+                float v = q - mu * mu;
+                if (!(v > 0.0f)) v = 0.0f;
+                num = num + __builtin_sqrtf(v * k);
+                den = den + fabsf(mu);
+            }
+            err = num / (den + 0.03f);
+        }
+        if (err_out) err_out[i] = err;
+    }
+    if (!partials) return;      /* the map alone: no summary wanted, nothing shared is written (the same for every thread of the launch) */
+    /* (threads past the last pixel add nothing: not an empty pixel, and not one above a negative threshold either) */
+    film_error_tree(s_sum, s_max, s_empty, s_above, tid, (double) err, err, empty ? 1ull : 0ull, i < n && err > threshold ? 1ull : 0ull, partials + blockIdx.x);
+}
+
+/* one workgroup: lane t adds the partials t, t + 256, ... in ascending order, then the tree */
+__global__ __launch_bounds__(kB) void film_error_reduce_kernel(const FilmErrorPartial *partials, uint32_t n, FilmErrorPartial *total) {
+    __shared__ double s_sum[kB];
+    __shared__ float s_max[kB];
+    __shared__ unsigned long long s_empty[kB], s_above[kB];
+    const int tid = threadIdx.x;
+    double sum = 0.0; float mx = 0.0f; unsigned long long n_empty = 0, n_above = 0;
+    for (uint32_t i = (uint32_t) tid; i < n; i += kB) {
+        const FilmErrorPartial p = partials[i];
+        sum += p.sum; mx = fmaxf(mx, p.max); n_empty += p.n_empty; n_above += p.n_above;
+    }
+    film_error_tree(s_sum, s_max, s_empty, s_above, tid, sum, mx, n_empty, n_above, total);
 }
 
 /* ---- reference order ---- */
@@ -606,24 +719,62 @@ std::string film_prepare(FilmStore &g_film, size_t n_samples, size_t n_sel_tiles
     return std::string();
 }
 
-template <int BORDER, int R, int WG, int STRIDE>
+void film_moments_release(FilmMoments &m) {
+    if (m.tile_acc2) (void) hipFree(m.tile_acc2);
+    if (m.err_partials) (void) hipFree(m.err_partials);
+    m = FilmMoments();
+}
+
+std::string film_moments_prepare(FilmMoments &m, const FilmStore &view, size_t n_sel_tiles, int tile_w, void *stream) {
+    const size_t acc = n_sel_tiles * view.n_parts * (size_t) tile_w * tile_w * 4;      /* film_prepare's */
+    if (m.acc2_floats < acc || !m.tile_acc2) {
+        if (m.tile_acc2) (void) hipFree(m.tile_acc2);
+        m.tile_acc2 = nullptr; m.acc2_floats = 0;
+        FILM_TRY(hipMalloc((void **) &m.tile_acc2, std::max<size_t>(acc, 4) * sizeof(float)));
+        m.acc2_floats = acc;
+    }
+    FILM_TRY(hipMemsetAsync(m.tile_acc2, 0, std::max<size_t>(acc, 4) * sizeof(float), (hipStream_t) stream));
+    return std::string();
+}
+
+template <int BORDER, int R, int WG, int STRIDE, bool M2>
 static void launch_strips(const DevScene &sc, const float *d_filter_table, const FilmStore &st, const FilmLaunch &fl, void *stream) {
     using G = FilmStrips<BORDER, R, WG, STRIDE>;
-    hipLaunchKernelGGL((film_gather_strips_kernel<BORDER, R, WG, STRIDE>), dim3(fl.n_tiles * st.n_parts), dim3(WG), G::lds_bytes,
-                       (hipStream_t) stream, sc.camera.width, sc.camera.height, sc.filter, d_filter_table, st, fl);
+    if constexpr (M2)
+        hipLaunchKernelGGL((film_gather_strips_m2_kernel<BORDER, R, WG, STRIDE>), dim3(fl.n_tiles * st.n_parts), dim3(WG), G::lds_bytes,
+                           (hipStream_t) stream, sc.camera.width, sc.camera.height, sc.filter, d_filter_table, st, fl);
+    else
+        hipLaunchKernelGGL((film_gather_strips_kernel<BORDER, R, WG, STRIDE>), dim3(fl.n_tiles * st.n_parts), dim3(WG), G::lds_bytes,
+                           (hipStream_t) stream, sc.camera.width, sc.camera.height, sc.filter, d_filter_table, st, fl);
+}
+
+/* one pass over the store: the beauty sums, or (M2) the second moments by the same choice of kernel */
+template <bool M2>
+static void gather_pass(const DevScene &sc, const float *d_filter_table, const FilmStore &st, const FilmLaunch &fl, void *stream) {
+    static const bool rounds = [] { const char *e = getenv("NORI_HIP_FILM_GATHER"); return e && std::string(e) == "rounds"; }();      /* A / B: film_gather_kernel for every border */
+    const int border = sc.filter.border;
+    if (!rounds && fl.tile_w == kTile + 2 * border) {
+        if (border == 2) return launch_strips<2, kStripRows2, kStripWg2, kStripStride2, M2>(sc, d_filter_table, st, fl, stream);
+        if (border == 1) return launch_strips<1, kStripRows1, kStripWg1, kStripStride1, M2>(sc, d_filter_table, st, fl, stream);
+    }
+    const size_t lds = (size_t) (2 * (2 * border + 1) + 3) * 256 * sizeof(float);
+    if constexpr (M2)
+        hipLaunchKernelGGL(film_gather_m2_kernel, dim3(fl.n_tiles * st.n_parts), dim3(kB), lds, (hipStream_t) stream, sc.camera.width, sc.camera.height,
+                           sc.filter, d_filter_table, st, fl);
+    else
+        hipLaunchKernelGGL(film_gather_kernel, dim3(fl.n_tiles * st.n_parts), dim3(kB), lds, (hipStream_t) stream, sc.camera.width, sc.camera.height,
+                           sc.filter, d_filter_table, st, fl);
 }
 
 void film_gather(const DevScene &sc, const float *d_filter_table, const FilmStore &st, const FilmLaunch &fl, void *stream) {
     if (fl.n_tiles == 0 || fl.n_spp == 0) return;
-    static const bool rounds = [] { const char *e = getenv("NORI_HIP_FILM_GATHER"); return e && std::string(e) == "rounds"; }();      /* A / B: film_gather_kernel for every border */
-    const int border = sc.filter.border;
-    if (!rounds && fl.tile_w == kTile + 2 * border) {
-        if (border == 2) return launch_strips<2, kStripRows2, kStripWg2, kStripStride2>(sc, d_filter_table, st, fl, stream);
-        if (border == 1) return launch_strips<1, kStripRows1, kStripWg1, kStripStride1>(sc, d_filter_table, st, fl, stream);
-    }
-    const size_t lds = (size_t) (2 * (2 * border + 1) + 3) * 256 * sizeof(float);
-    hipLaunchKernelGGL(film_gather_kernel, dim3(fl.n_tiles * st.n_parts), dim3(kB), lds, (hipStream_t) stream, sc.camera.width, sc.camera.height,
-                       sc.filter, d_filter_table, st, fl);
+    gather_pass<false>(sc, d_filter_table, st, fl, stream);
+}
+
+void film_gather_moments(const DevScene &sc, const float *d_filter_table, const FilmStore &st, const FilmMoments &m, const FilmLaunch &fl, void *stream) {
+    if (fl.n_tiles == 0 || fl.n_spp == 0 || !m.tile_acc2) return;
+    FilmStore v = st; v.tile_acc = m.tile_acc2;      /* the same samples, parts and slots; the second set of accumulators */
+    gather_pass<true>(sc, d_filter_table, v, fl, stream);
 }
 
 void film_resolve(const DevScene &sc, const FilmStore &st, const FilmLaunch &fl, float *d_rgbw, void *stream) {
@@ -631,6 +782,43 @@ void film_resolve(const DevScene &sc, const FilmStore &st, const FilmLaunch &fl,
     hipLaunchKernelGGL(film_resolve_kernel, dim3((cols + 255) / 256, rows), dim3(256), 0, (hipStream_t) stream, sc.camera.width,
                        sc.camera.height, border, fl.tile_w, fl.tiles_x, fl.tiles_y, fl.tile_mod, fl.tile_rem, st.n_parts,
                        (const float *) st.tile_acc, d_rgbw);
+}
+
+void film_resolve_moments(const DevScene &sc, const FilmStore &st, const FilmMoments &m, const FilmLaunch &fl, float *d_m2, void *stream) {
+    if (!m.tile_acc2 || !d_m2) return;
+    FilmStore v = st; v.tile_acc = m.tile_acc2;
+    film_resolve(sc, v, fl, d_m2, stream);
+}
+
+std::string film_error_map(FilmMoments &store, const DevScene &sc, const float *d_rgbw, const float *d_m2, float *d_err, float threshold,
+                           FilmErrorSummary *out, void *stream) {
+    const int w = sc.camera.width, h = sc.camera.height;
+    const size_t n_pixels = (size_t) w * h;
+    if (n_pixels == 0 || n_pixels > ((size_t) 1 << 31)) return "error_map: frame of no pixels or more than 2^31";
+    const uint32_t n_blocks = (uint32_t) ((n_pixels + kB - 1) / kB);
+    if (!out) {      /* the map alone touches nothing of the context's: such calls may run on several streams at once */
+        hipLaunchKernelGGL(film_error_map_kernel, dim3(n_blocks), dim3(kB), 0, (hipStream_t) stream, w, h, sc.filter.border, d_rgbw, d_m2, d_err, threshold, (FilmErrorPartial *) nullptr);
+        FILM_TRY(hipGetLastError());
+        return std::string();
+    }
+    /* the summary goes through the context's one array of partial sums; the call ends with the stream synchronised, so calls that
+       follow one another on a context -- whatever their streams -- never share it (two threads on one context must not overlap) */
+    if (store.err_blocks < (size_t) n_blocks + 1) {
+        if (store.err_partials) (void) hipFree(store.err_partials);
+        store.err_partials = nullptr; store.err_blocks = 0;
+        FILM_TRY(hipMalloc((void **) &store.err_partials, ((size_t) n_blocks + 1) * sizeof(FilmErrorPartial)));
+        store.err_blocks = (size_t) n_blocks + 1;
+    }
+    FilmErrorPartial *part = (FilmErrorPartial *) store.err_partials;
+    hipLaunchKernelGGL(film_error_map_kernel, dim3(n_blocks), dim3(kB), 0, (hipStream_t) stream, w, h, sc.filter.border, d_rgbw, d_m2, d_err, threshold, part + 1);
+    FILM_TRY(hipGetLastError());
+    hipLaunchKernelGGL(film_error_reduce_kernel, dim3(1), dim3(kB), 0, (hipStream_t) stream, (const FilmErrorPartial *) (part + 1), n_blocks, part);
+    FILM_TRY(hipGetLastError());
+    FilmErrorPartial total;
+    FILM_TRY(hipMemcpyAsync(&total, part, sizeof(total), hipMemcpyDeviceToHost, (hipStream_t) stream));
+    FILM_TRY(hipStreamSynchronize((hipStream_t) stream));
+    out->sum_err = total.sum; out->max_err = total.max; out->n_pixels = n_pixels; out->n_empty = total.n_empty; out->n_above = total.n_above;
+    return std::string();
 }
 
 size_t film_block_acc_floats(const DevScene &sc) {

@@ -435,6 +435,7 @@ struct nori_hip_ctx {
        engine's state pool / streams / events and the film's sample store + tile accumulators */
     WfEngine *wf = nullptr;
     FilmStore film;
+    FilmMoments moments;      /* renders that keep second moments, nori_hip_error_map: a second set of tile accumulators, partial sums */
 };
 
 static std::string g_create_error;
@@ -539,6 +540,7 @@ void nori_hip_destroy(nori_hip_ctx *ctx) {
     free_pool(ctx->allocs_scene); free_pool(ctx->allocs_accel);
     wavefront_destroy(ctx->wf);
     film_release(ctx->film);
+    film_moments_release(ctx->moments);
     if (ctx->d_stats) (void) hipFree(ctx->d_stats);
     delete ctx;
 }
@@ -1064,9 +1066,14 @@ static hipError_t launch_render(nori_hip_ctx *ctx, const RenderArgs &a, const Fi
 
 /* nori_hip_render, and nori_hip_render_block_rows (share != nullptr: the block rows of a reference-order film; the accumulators
    of their blocks go to share->block_acc instead of a frame) */
-static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void *d_rgbw, nori_render_stats *stats, const FilmBlockRows *share) {
+static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void *d_rgbw, nori_render_stats *stats, const FilmBlockRows *share,
+                       float *d_m2 = nullptr /* nori_hip_render_moments: the same samples' second moments are added here */) {
     REQUIRE_ACCEL(ctx);
     if (!params || (!d_rgbw && !share)) return NORI_ERR_INVALID_ARGUMENT;
+    if (d_m2 && (ctx->film_reference || share)) {
+        ctx->error = "render_moments: second moments are kept by the fast film only (film_order = fast, no block rows)";
+        return NORI_ERR_UNSUPPORTED;
+    }
     if (params->tile_mod == 0 || params->tile_rem >= params->tile_mod) { ctx->error = "render: bad tile_mod/tile_rem"; return NORI_ERR_INVALID_ARGUMENT; }
     if (share && (!ctx->film_reference || params->tile_mod != 1 || params->seed_mode != NORI_SEED_PER_SAMPLE || !share->block_acc)) {
         ctx->error = "render_block_rows: needs film_order = reference, tile_mod 1, NORI_SEED_PER_SAMPLE and an accumulator array";
@@ -1136,6 +1143,7 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
         if (n_samples > ((size_t) 1 << 30)) { ctx->error = "render: NORI_SEED_NORI_BLOCK keeps the whole frame's samples in the film store (limit 2^30)"; return NORI_ERR_UNSUPPORTED; }
         FilmStore film;
         std::string ferr = film_prepare(ctx->film, n_samples, a.n_sel_tiles, a.tile_w, s, film);
+        if (ferr.empty() && d_m2) ferr = film_moments_prepare(ctx->moments, film, a.n_sel_tiles, a.tile_w, s);
         if (!ferr.empty()) { ctx->error = ferr; return NORI_ERR_OUT_OF_MEMORY; }
         /* (slots of edge-tile pixels outside the image stay unwritten: film_gather never reads them) */
         const uint32_t bx = (uint32_t) ((ctx->host.camera.width + kNoriBlock - 1) / kNoriBlock), by = (uint32_t) ((ctx->host.camera.height + kNoriBlock - 1) / kNoriBlock);
@@ -1164,6 +1172,10 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
         } else {
             film_gather(ctx->dev, ctx->d_filter, film, fl, s);
             film_resolve(ctx->dev, film, fl, (float *) d_rgbw, s);
+            if (d_m2) {
+                film_gather_moments(ctx->dev, ctx->d_filter, film, ctx->moments, fl, s);
+                film_resolve_moments(ctx->dev, film, ctx->moments, fl, d_m2, s);
+            }
         }
         timer.end(s);
         HIP_TRY(ctx, hipGetLastError());
@@ -1181,6 +1193,7 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
         /* paths in flight: the option, bounded by what this GPU has free right now (state already held by
            this context counts as free) -- a second context or another process may own part of the HBM */
         wl.film_reference = ctx->film_reference; wl.film_share = share;
+        wl.d_m2 = d_m2; wl.moments = d_m2 ? &ctx->moments : nullptr;
         /* what the call can use at all: a batch never holds more samples than the call has, the pool never more paths than a batch */
         const size_t call_samples = (size_t) a.n_sel_tiles * 256 * a.spp_count;
         /* (reference film order: the frame is one batch whatever the options say -- the pool need not hold it) */
@@ -1210,6 +1223,7 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
             (void) hipGetLastError();
             wavefront_release_pool(ctx->wf);
             film_release(ctx->film);
+            if (d_m2) film_moments_release(ctx->moments);
             const bool pool_bigger = wl.max_paths * per_path >= wl.max_samples * per_sample || ctx->film_reference;
             if (pool_bigger && wl.max_paths > ((size_t) 1 << 20)) wl.max_paths /= 2;
             else if (ctx->film_reference) break;      /* (its one batch cannot shrink) */
@@ -1232,6 +1246,7 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
         if (ctx->film_reference && spp_per_launch != a.spp_count) { ctx->error = "render: film_order = reference needs all samples of the frame in the film store at once"; return NORI_ERR_UNSUPPORTED; }
         FilmStore film;
         std::string ferr = film_prepare(ctx->film, (size_t) a.n_sel_tiles * 256 * spp_per_launch, a.n_sel_tiles, a.tile_w, s, film);
+        if (ferr.empty() && d_m2) ferr = film_moments_prepare(ctx->moments, film, a.n_sel_tiles, a.tile_w, s);
         if (!ferr.empty()) { ctx->error = ferr; return NORI_ERR_OUT_OF_MEMORY; }
         FilmLaunch fl;
         fl.tile_first = 0; fl.store_tile_first = 0; fl.n_tiles = a.n_sel_tiles; fl.tile_mod = a.tile_mod; fl.tile_rem = a.tile_rem;
@@ -1254,6 +1269,7 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
             fl.n_spp = a2.spp_count;
             timer.begin(KC_FILM, s);
             if (!(a.debug_flags & 1u) && !ctx->film_reference) film_gather(ctx->dev, ctx->d_filter, film, fl, s);
+            if (d_m2 && !(a.debug_flags & 1u)) film_gather_moments(ctx->dev, ctx->d_filter, film, ctx->moments, fl, s);      /* before the next launch overwrites the store */
             timer.end(s);
             n_workgroups += a2.n_sel_tiles * a2.n_chunks;
         }
@@ -1262,6 +1278,7 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
             std::string rerr = film_reference_order(ctx->film, film, ctx->dev, ctx->d_filter, a.spp_count, a.tiles_x, share, (float *) d_rgbw, s);
             if (!rerr.empty()) { ctx->error = rerr; return NORI_ERR_INTERNAL; }
         } else film_resolve(ctx->dev, film, fl, (float *) d_rgbw, s);
+        if (d_m2) film_resolve_moments(ctx->dev, film, ctx->moments, fl, d_m2, s);
         timer.end(s);
         HIP_TRY(ctx, hipGetLastError());
         if (stats) n_invalid = film_invalid_count(film, s);
@@ -1303,6 +1320,120 @@ extern "C" {
 
 int nori_hip_render(nori_hip_ctx *ctx, const nori_render_params *params, void *d_rgbw, nori_render_stats *stats) {
     return render_impl(ctx, params, d_rgbw, stats, nullptr);
+}
+
+int nori_hip_render_moments(nori_hip_ctx *ctx, const nori_render_params *params, void *d_rgbw, void *d_m2, nori_render_stats *stats) {
+    if (ctx && (!d_rgbw || !d_m2)) { ctx->error = "render_moments: needs an RGBW frame and a moment frame"; return NORI_ERR_INVALID_ARGUMENT; }
+    return render_impl(ctx, params, d_rgbw, stats, nullptr, (float *) d_m2);
+}
+
+int nori_hip_render_moments_host(nori_hip_ctx *ctx, const nori_render_params *params, float *rgbw, float *m2, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !rgbw || !m2) return NORI_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    const size_t fb = frame_floats(ctx) * sizeof(float);
+    SCRATCH_OUT(ctx, df, 2 * fb);
+    HIP_TRY(ctx, hipMemset(df.p, 0, 2 * fb));
+    nori_render_stats local;
+    int rc = nori_hip_render_moments(ctx, params, df.p, (char *) df.p + fb, stats ? stats : &local);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(rgbw, df.p, fb, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(m2, (char *) df.p + fb, fb, hipMemcpyDeviceToHost));
+    return NORI_OK;
+}
+
+int nori_hip_error_map(nori_hip_ctx *ctx, const void *d_rgbw, const void *d_m2, void *d_err, float threshold, nori_error_summary *out, void *stream) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (!d_rgbw || !d_m2 || (!d_err && !out)) { ctx->error = "error_map: needs both frames and a map or a summary to fill"; return NORI_ERR_INVALID_ARGUMENT; }
+    DeviceGuard g(ctx->device);
+    FilmErrorSummary sum;
+    const std::string err = film_error_map(ctx->moments, ctx->dev, (const float *) d_rgbw, (const float *) d_m2, (float *) d_err, threshold, out ? &sum : nullptr, stream);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        out->sum_err = sum.sum_err; out->max_err = sum.max_err; out->threshold = threshold;
+        out->n_pixels = sum.n_pixels; out->n_empty = sum.n_empty; out->n_above = sum.n_above;
+    }
+    return NORI_OK;
+}
+
+int nori_hip_error_map_host(nori_hip_ctx *ctx, const float *rgbw, const float *m2, float *err, float threshold, nori_error_summary *out) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (!rgbw || !m2 || (!err && !out)) { ctx->error = "error_map: needs both frames and a map or a summary to fill"; return NORI_ERR_INVALID_ARGUMENT; }
+    DeviceGuard g(ctx->device);
+    const size_t fb = frame_floats(ctx) * sizeof(float);
+    const size_t eb = (size_t) ctx->host.camera.width * (size_t) ctx->host.camera.height * sizeof(float);
+    SCRATCH_OUT(ctx, df, 2 * fb + eb);
+    char *d_rgbw = (char *) df.p, *d_m2 = d_rgbw + fb, *d_err = d_m2 + fb;
+    HIP_TRY(ctx, hipMemcpy(d_rgbw, rgbw, fb, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d_m2, m2, fb, hipMemcpyHostToDevice));
+    int rc = nori_hip_error_map(ctx, d_rgbw, d_m2, err ? d_err : nullptr, threshold, out, nullptr);
+    if (rc) return rc;
+    if (err) HIP_TRY(ctx, hipMemcpy(err, d_err, eb, hipMemcpyDeviceToHost));      /* (a blocking copy: behind the kernel on the default stream) */
+    return NORI_OK;
+}
+
+int nori_hip_render_to_error(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_mean_err,
+                             void *d_rgbw, void *d_m2, uint32_t *spp_done, nori_error_summary *last, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !d_rgbw || !d_m2) return NORI_ERR_INVALID_ARGUMENT;
+    if (pass_spp == 0) { ctx->error = "render_to_error: pass_spp must be at least 1"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (!(target_mean_err >= 0.0f)) { ctx->error = "render_to_error: the target error must be a number >= 0"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (params->tile_mod != 1) { ctx->error = "render_to_error: renders whole frames (tile_mod 1): the error of a share says nothing about the frame"; return NORI_ERR_INVALID_ARGUMENT; }
+    nori_render_stats total; memset(&total, 0, sizeof(total));
+    nori_error_summary sum; memset(&sum, 0, sizeof(sum));
+    bool evaluated = false;
+    uint32_t done = 0, passes = 0;
+    while (done < params->spp_count) {
+        nori_render_params p = *params;
+        p.spp_begin = params->spp_begin + done; p.spp_count = std::min(pass_spp, params->spp_count - done);
+        nori_render_stats st;
+        int rc = nori_hip_render_moments(ctx, &p, d_rgbw, d_m2, &st);
+        if (rc) return rc;
+        total.n_camera_samples += st.n_camera_samples; total.n_closest_rays += st.n_closest_rays; total.n_shadow_rays += st.n_shadow_rays;
+        total.n_node_tests += st.n_node_tests; total.n_tri_tests += st.n_tri_tests; total.n_invalid += st.n_invalid;
+        total.kernel_ms += st.kernel_ms; total.trace_ms += st.trace_ms; total.shade_ms += st.shade_ms; total.film_ms += st.film_ms; total.tail_ms += st.tail_ms;
+        total.n_workgroups += st.n_workgroups; total.n_trace_launches += st.n_trace_launches;
+        total.lds_bytes = st.lds_bytes; total.engine = st.engine; total.trace_cus = st.trace_cus; total.tail_cus = st.tail_cus;
+        done += p.spp_count; ++passes;
+        evaluated = false;
+        if (passes >= 2) {      /* (one pass of few samples has no variance to speak of) */
+            rc = nori_hip_error_map(ctx, d_rgbw, d_m2, nullptr, target_mean_err, &sum, params->stream);
+            if (rc) return rc;
+            evaluated = true;
+            if (sum.sum_err / (double) sum.n_pixels <= (double) target_mean_err) break;
+        }
+    }
+    if (last) {
+        if (!evaluated) { int rc = nori_hip_error_map(ctx, d_rgbw, d_m2, nullptr, target_mean_err, &sum, params->stream); if (rc) return rc; }
+        *last = sum;
+    }
+    if (spp_done) *spp_done = done;
+    if (stats) *stats = total;
+    return NORI_OK;
+}
+
+int nori_hip_render_to_error_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_mean_err,
+                                  float *rgbw, float *m2, float *err, uint32_t *spp_done, nori_error_summary *last, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    const size_t fb = frame_floats(ctx) * sizeof(float);
+    const size_t eb = (size_t) ctx->host.camera.width * (size_t) ctx->host.camera.height * sizeof(float);
+    SCRATCH_OUT(ctx, df, 2 * fb + eb);
+    HIP_TRY(ctx, hipMemset(df.p, 0, 2 * fb + eb));
+    char *d_rgbw = (char *) df.p, *d_m2 = d_rgbw + fb, *d_err = d_m2 + fb;
+    int rc = nori_hip_render_to_error(ctx, params, pass_spp, target_mean_err, d_rgbw, d_m2, spp_done, last, stats);
+    if (rc) return rc;
+    if (err) {
+        rc = nori_hip_error_map(ctx, d_rgbw, d_m2, d_err, target_mean_err, nullptr, params->stream);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipStreamSynchronize((hipStream_t) params->stream));
+        HIP_TRY(ctx, hipMemcpy(err, d_err, eb, hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(ctx, hipMemcpy(rgbw, d_rgbw, fb, hipMemcpyDeviceToHost));
+    if (m2) HIP_TRY(ctx, hipMemcpy(m2, d_m2, fb, hipMemcpyDeviceToHost));
+    return NORI_OK;
 }
 
 int nori_hip_block_acc_floats(nori_hip_ctx *ctx, size_t *n_floats) {

@@ -21,6 +21,8 @@ struct WfLaunch {
                                    starts its samples pass by pass -- regeneration, wavefront.hip) */
     bool film_reference;        /* add the samples in the reference's order (film.h): needs the whole frame in ONE batch */
     const FilmBlockRows *film_share = nullptr;      /* reference order: the selected tiles are these block rows (tile_mod 1, tile_rem = their first tile) */
+    float *d_m2 = nullptr;      /* non-null: the film keeps the samples' second moments and adds them into this frame (film.h) ... */
+    FilmMoments *moments = nullptr;      /* ... through the context's second set of accumulators */
 };
 
 struct WfStats {

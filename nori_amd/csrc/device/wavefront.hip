@@ -1360,6 +1360,11 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
     FilmStore film;
     err = film_prepare(film_store, per_pipe * (overlap ? 2 : n_pipes), L.n_sel_tiles, L.tile_w, s, film);
     if (!err.empty()) return err;
+    const bool moments = L.d_m2 != nullptr && L.moments != nullptr;
+    if (moments) {
+        err = film_moments_prepare(*L.moments, film, L.n_sel_tiles, L.tile_w, s);
+        if (!err.empty()) return err;
+    }
     stats.state_bytes = g_pool.bytes + per_pipe * (overlap ? 2 : n_pipes) * (sizeof(f2) + sizeof(P3));
     WF_TRY(hipMemsetAsync(g_pool.buf.stats, 0, 2 * S_COUNT * sizeof(unsigned long long), s));
 
@@ -1567,6 +1572,7 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
                 WF_TRY(hipStreamWaitEvent(P.stream, eng.tail_events[1], 0));
                 timer.begin(KC_FILM, P.stream);
                 film_gather(sc, d_filter_table, pend.film, pend.fl, P.stream);
+                if (moments) film_gather_moments(sc, d_filter_table, pend.film, *L.moments, pend.fl, P.stream);
                 timer.end(P.stream);
                 stats.n_launches++;
                 pend.active = false;
@@ -1610,6 +1616,7 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
                 fl.tile_first = P.bt.tile_first; fl.store_tile_first = P.bt.tile_first; fl.n_tiles = P.bt.n_tiles; fl.n_spp = P.bt.n_spp;
                 timer.begin(KC_FILM, P.stream);
                 if (!L.film_reference) film_gather(sc, d_filter_table, P.film, fl, P.stream);
+                if (moments) film_gather_moments(sc, d_filter_table, P.film, *L.moments, fl, P.stream);
                 timer.end(P.stream);
                 stats.n_launches++;
             }
@@ -1632,6 +1639,7 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
         err = film_reference_order(film_store, film, sc, d_filter_table, L.spp_count, L.tiles_x, L.film_share, d_rgbw, s);
         if (!err.empty()) return err;
     } else film_resolve(sc, film, fl, d_rgbw, s);
+    if (moments) film_resolve_moments(sc, film, *L.moments, fl, L.d_m2, s);
     timer.end(s);
     stats.n_launches++;
     WF_TRY(hipGetLastError());

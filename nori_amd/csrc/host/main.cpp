@@ -1,5 +1,5 @@
 /*
- * main.cpp -- `nori <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference]`
+ * main.cpp -- `nori <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K]]`
  * Command line of the reference (src/main.cpp:150-246).  There is no GUI on a
  * compute node: --no-gui is accepted and implied; --threads is accepted for
  * compatibility (the work runs on the GPU).  --seed block renders with the
@@ -7,7 +7,11 @@
  * src/independent.cpp:36-41; one GPU lane per block, slow by design) instead of
  * one stream per camera sample.  --gpus N shares the frame over the first N GPUs
  * of the node (render.cpp: what TBB workers are in the reference; --split / --merge
- * choose how the work is cut and how the frames come together).  A <test> root runs during parsing
+ * choose how the work is cut and how the frames come together).  --target-error E renders
+ * in passes of K samples per pixel (--pass-spp, default 16) until the mean of the per-pixel
+ * error map (include/nori_hip.h: nori_hip_error_map) is at most E, the scene's sampleCount
+ * being the most it spends; it prints where it stopped and writes the map as
+ * <scene>.error.exr next to the frame (one device only).  A <test> root runs during parsing
  * (its activate()), as in the reference; failures exit with -1.
  */
 #include <nori/bitmap.h>
@@ -17,10 +21,14 @@ using namespace nori;
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        cerr << "Syntax: " << argv[0] << " <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference]" << endl;
+        cerr << "Syntax: " << argv[0] << " <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K]]" << endl;
         return -1;
     }
     std::string sceneName;
+    bool toError = false, havePassSpp = false;
+    float targetError = 0.0f;
+    long passSpp = 16;
+    int gpus = 1;
     for (int i = 1; i < argc; ++i) {
         std::string token(argv[i]);
         if (token == "-t" || token == "--threads") {
@@ -44,7 +52,26 @@ int main(int argc, char **argv) {
                 cerr << "\"--gpus\" argument expects a positive integer following it." << endl;
                 return -1;
             }
+            gpus = atoi(argv[i + 1]);
             setenv("NORI_GPUS", argv[++i], 1);
+            continue;
+        } else if (token == "--target-error") {
+            char *end = nullptr;
+            if (i + 1 < argc) targetError = std::strtof(argv[i + 1], &end);
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !(targetError >= 0.0f) || std::isinf(targetError)) {
+                cerr << "Usage: \"--target-error\" expects a mean relative error >= 0 following it, e.g. --target-error 0.05 [--pass-spp K]." << endl;
+                return -1;
+            }
+            toError = true; ++i;
+            continue;
+        } else if (token == "--pass-spp") {
+            char *end = nullptr;
+            if (i + 1 < argc) passSpp = std::strtol(argv[i + 1], &end, 10);
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || passSpp <= 0 || passSpp > 0x7fffffffl) {
+                cerr << "Usage: \"--pass-spp\" expects a positive number of samples per pixel and pass following it (with --target-error E)." << endl;
+                return -1;
+            }
+            havePassSpp = true; ++i;
             continue;
         } else if (token == "--split" || token == "--merge" || token == "--film-order") {
             if (i + 1 >= argc) {
@@ -65,6 +92,14 @@ int main(int argc, char **argv) {
             cerr << "Fatal error: unknown file \"" << token << "\", expected an extension of type .xml or .exr" << endl;
         }
     }
+    if (havePassSpp && !toError) {
+        cerr << "Usage: \"--pass-spp\" goes with --target-error E." << endl;
+        return -1;
+    }
+    if (toError && gpus > 1) {
+        cerr << "\"--target-error\" renders on one device: moment frames over several GPUs are not supported (got --gpus " << gpus << ")." << endl;
+        return -1;
+    }
     if (sceneName.empty()) {
         cerr << "Please provide the path to a .xml (or .exr) file." << endl;
         return -1;
@@ -77,7 +112,11 @@ int main(int argc, char **argv) {
             cout.flush();
             Timer timer;
             nori_render_stats st;
-            std::unique_ptr<ImageBlock> result = renderScene(scene, &st);
+            uint32_t sppDone = 0;
+            nori_error_summary summary;
+            std::vector<float> errorMap;
+            std::unique_ptr<ImageBlock> result = toError ? renderSceneToError(scene, targetError, (uint32_t) passSpp, sppDone, summary, errorMap, &st)
+                                                         : renderScene(scene, &st);
             cout << "done. (took " << timer.elapsedString() << "; kernel " << timeString(st.kernel_ms, true) << ", "
                  << (double) (st.n_closest_rays + st.n_shadow_rays) / (st.kernel_ms * 1e3) << " Mrays/s)" << endl;
             std::unique_ptr<Bitmap> bitmap(result->toBitmap());
@@ -86,6 +125,15 @@ int main(int argc, char **argv) {
             if (lastdot != std::string::npos) outputName.erase(lastdot, std::string::npos);
             bitmap->saveEXR(outputName);
             bitmap->savePNG(outputName);
+            if (toError) {
+                cout << "Stopped at " << sppDone << " samples per pixel: mean error " << summary.sum_err / (double) std::max<uint64_t>(summary.n_pixels, 1)
+                     << " (target " << targetError << ", max " << summary.max_err << ", " << summary.n_above << " of " << summary.n_pixels << " pixels above the target)" << endl;
+                Bitmap errorBitmap(scene->getCamera()->getOutputSize());
+                for (int y = 0; y < errorBitmap.rows(); ++y)
+                    for (int x = 0; x < errorBitmap.cols(); ++x)
+                        errorBitmap.set(y, x, Color3f(errorMap[(size_t) y * errorBitmap.cols() + x]));
+                errorBitmap.saveEXR(outputName + ".error");
+            }
         }
     } catch (const std::exception &e) {
         cerr << e.what() << endl;

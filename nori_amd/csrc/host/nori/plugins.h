@@ -298,4 +298,10 @@ NoriObject *loadFromXML(const std::string &filename);
    full-frame block; fills `stats` if given. */
 std::unique_ptr<ImageBlock> renderScene(Scene *scene, nori_render_stats *stats = nullptr);
 
+/* The same on one device, in passes of `passSpp` samples per pixel until the mean of the per-pixel error map
+   (nori_hip_error_map) is at most `targetError` or the sampler's sampleCount is spent (nori_hip_render_to_error).
+   `errorMap` (width * height floats) receives the map of the frame as returned. */
+std::unique_ptr<ImageBlock> renderSceneToError(Scene *scene, float targetError, uint32_t passSpp, uint32_t &sppDone,
+                                               nori_error_summary &summary, std::vector<float> &errorMap, nori_render_stats *stats = nullptr);
+
 NORI_NAMESPACE_END

@@ -80,4 +80,29 @@ std::unique_ptr<ImageBlock> renderScene(Scene *scene, nori_render_stats *stats) 
     return result;
 }
 
+std::unique_ptr<ImageBlock> renderSceneToError(Scene *scene, float targetError, uint32_t passSpp, uint32_t &sppDone,
+                                               nori_error_summary &summary, std::vector<float> &errorMap, nori_render_stats *stats) {
+    const Camera *camera = scene->getCamera();
+    scene->getIntegrator()->preprocess(scene);
+    if (const char *gpus = std::getenv("NORI_GPUS"))
+        if (std::atoi(gpus) > 1) throw NoriException("--target-error renders on one device: moment frames over a device group are not supported (got --gpus %s)", gpus);
+    if (const char *seed = std::getenv("NORI_SEED"))
+        if (std::string(seed) == "block") throw NoriException("--target-error renders in passes, which --seed block cannot (a block's stream is serial from sample 0)");
+    std::unique_ptr<ImageBlock> result(new ImageBlock(camera->getOutputSize(), camera->getReconstructionFilter()));
+    result->clear();
+    errorMap.assign((size_t) camera->getOutputSize().x() * camera->getOutputSize().y(), 0.0f);
+
+    nori_render_params params;
+    std::memset(&params, 0, sizeof(params));
+    params.spp_begin = 0;
+    params.spp_count = (uint32_t) scene->getSampler()->getSampleCount();      /* the ceiling */
+    params.tile_mod = 1; params.tile_rem = 0;
+    params.seed_mode = NORI_SEED_PER_SAMPLE;
+    nori_render_stats local;
+    Device &dev = scene->device();
+    dev.check(nori_hip_render_to_error_host(dev.ctx(), &params, passSpp, targetError, result->data(), nullptr, errorMap.data(), &sppDone, &summary,
+                                            stats ? stats : &local), "nori_hip_render_to_error_host");
+    return result;
+}
+
 NORI_NAMESPACE_END

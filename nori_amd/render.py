@@ -226,6 +226,66 @@ class Renderer:
                                               C.byref(st) if st is not None else None), "render")
         return st.as_dict() if st is not None else None
 
+    # -- second moments, error map, render to a target error (include/nori_hip.h) --
+    def _is_frame(self, t):
+        return t.is_cuda and t.is_contiguous() and tuple(t.shape) == tuple(self.frame_shape()) and str(t.dtype) == "torch.float32"
+
+    def render_moments_into(self, rgbw_tensor, m2_tensor, spp_count=None, spp_begin=0, tile_mod=1, tile_rem=0,
+                            count_traversal=False, stream=None, want_stats=True, time_kernels=False, seed_mode=capi.SEED_PER_SAMPLE):
+        """render_into, and the same samples' second moments accumulated into `m2_tensor` (shape and layout of the frame):
+        per tap of weight w the frame receives (L w, w), the moment frame (float32(L L) w, float32(w w))."""
+        assert self._is_frame(rgbw_tensor) and self._is_frame(m2_tensor)
+        spp = self.scene.sample_count if spp_count is None else spp_count
+        raw = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        p = self._params(spp_begin, spp, tile_mod, tile_rem, count_traversal, raw, time_kernels, seed_mode)
+        st = capi.RenderStats() if want_stats else None
+        self._check(self._lib.nori_hip_render_moments(self._h, C.byref(p), C.c_void_p(rgbw_tensor.data_ptr()), C.c_void_p(m2_tensor.data_ptr()),
+                                                      C.byref(st) if st is not None else None), "render_moments")
+        return st.as_dict() if st is not None else None
+
+    def render_moments_host(self, spp_count=None, spp_begin=0, tile_mod=1, tile_rem=0, count_traversal=False, seed_mode=capi.SEED_PER_SAMPLE):
+        """Render into fresh host frames; returns (rgbw, m2, stats dict)."""
+        spp = self.scene.sample_count if spp_count is None else spp_count
+        p = self._params(spp_begin, spp, tile_mod, tile_rem, count_traversal, None, seed_mode=seed_mode)
+        rgbw, m2 = np.zeros(self.frame_shape(), np.float32), np.zeros(self.frame_shape(), np.float32)
+        st = capi.RenderStats()
+        self._check(self._lib.nori_hip_render_moments_host(self._h, C.byref(p), ptr(rgbw), ptr(m2), C.byref(st)), "render_moments_host")
+        return rgbw, m2, st.as_dict()
+
+    def error_map(self, rgbw, m2, threshold=0.0, stream=None):
+        """(err, summary dict): the per-pixel relative standard error of the mean (height x width, no border) of a frame and its
+        moment frame, and its deterministic summary (sum_err, max_err, threshold, n_pixels, n_empty, n_above).  Torch CUDA
+        tensors give a CUDA tensor; numpy arrays are copied to the device and give a numpy array."""
+        c = self.scene.camera
+        out = capi.ErrorSummary()
+        if isinstance(rgbw, np.ndarray):
+            rgbw, m2 = (np.ascontiguousarray(a, dtype=np.float32) for a in (rgbw, m2))
+            assert rgbw.shape == m2.shape == tuple(self.frame_shape())
+            err = np.zeros((c.height, c.width), np.float32)
+            self._check(self._lib.nori_hip_error_map_host(self._h, ptr(rgbw), ptr(m2), ptr(err), float(threshold), C.byref(out)), "error_map_host")
+            return err, out.as_dict()
+        import torch
+        assert self._is_frame(rgbw) and self._is_frame(m2)
+        err = torch.empty((c.height, c.width), dtype=torch.float32, device=rgbw.device)
+        raw = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._check(self._lib.nori_hip_error_map(self._h, C.c_void_p(rgbw.data_ptr()), C.c_void_p(m2.data_ptr()), C.c_void_p(err.data_ptr()),
+                                                 float(threshold), C.byref(out), raw), "error_map")
+        return err, out.as_dict()
+
+    def render_to_error(self, rgbw_tensor, m2_tensor, target_mean_err, pass_spp=16, spp_count=None, spp_begin=0, stream=None,
+                        count_traversal=False, time_kernels=False):
+        """Render in passes of `pass_spp` samples per pixel, at most `spp_count` (default: the scene's sample count), until the
+        mean of the error map is at most `target_mean_err`; accumulates into both tensors.  Returns (spp_done, summary dict,
+        stats dict with counters and times summed over the passes)."""
+        assert self._is_frame(rgbw_tensor) and self._is_frame(m2_tensor)
+        spp = self.scene.sample_count if spp_count is None else spp_count
+        raw = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        p = self._params(spp_begin, spp, 1, 0, count_traversal, raw, time_kernels)
+        done, last, st = C.c_uint32(0), capi.ErrorSummary(), capi.RenderStats()
+        self._check(self._lib.nori_hip_render_to_error(self._h, C.byref(p), int(pass_spp), float(target_mean_err), C.c_void_p(rgbw_tensor.data_ptr()),
+                                                       C.c_void_p(m2_tensor.data_ptr()), C.byref(done), C.byref(last), C.byref(st)), "render_to_error")
+        return int(done.value), last.as_dict(), st.as_dict()
+
     # -- film_order = reference shared out: rows of 32x32 blocks (include/nori_hip.h: nori_hip_render_block_rows) --
     def block_rows(self) -> int:
         """rows of 32x32 blocks (NORI_BLOCK_SIZE) in the frame"""
