@@ -527,6 +527,82 @@ int nori_hip_render_to_error_host(nori_hip_ctx *ctx, const nori_render_params *p
                                   float *rgbw, float *m2, float *err, uint32_t *spp_done,
                                   nori_error_summary *last, nori_render_stats *stats);
 
+/* ------------------------------------------- tile lists, tile errors, selection, adaptive sampling
+ *
+ * No counterpart in the reference, whose BlockGenerator hands out every block once.
+ *
+ * nori_hip_render_tiles renders samples [spp_begin, spp_begin + spp_count) of exactly the listed NORI_TILE_SIZE^2 tiles and ADDS
+ * them into d_rgbw -- and, where d_m2 is not NULL, their second moments into d_m2 -- exactly as nori_hip_render /
+ * nori_hip_render_moments do for a progression: a list that equals {tile_rem + k tile_mod} gives the frames, moment frames and
+ * counters of that call, bit for bit.  tiles: n_tiles raster ids ty * tiles_x + tx in HOST memory, strictly ascending (so no
+ * tile twice); NORI_ERR_INVALID_ARGUMENT, with a message, for an id outside the frame or a list that is not strictly
+ * ascending.  params->tile_mod must be 1 and tile_rem 0.  n_tiles == 0 succeeds and touches nothing.  Both engines ("auto"
+ * picks by the list's camera samples); film_order must be "fast" and seed_mode NORI_SEED_PER_SAMPLE (NORI_ERR_UNSUPPORTED
+ * otherwise: reference order and the block-serial sampler render whole frames).  The list is copied to device memory of the
+ * context's: the call synchronises params->stream once before it renders.  Frames of disjoint lists add like the frames
+ * of disjoint shares.
+ * nori_hip_render_tiles_host: into zeroed HOST frames (m2 may be NULL), as nori_hip_render_host. */
+int nori_hip_render_tiles(nori_hip_ctx *ctx, const nori_render_params *params,
+                          const uint32_t *tiles /* HOST */, uint32_t n_tiles,
+                          void *d_rgbw, void *d_m2 /* may be NULL */, nori_render_stats *stats);
+int nori_hip_render_tiles_host(nori_hip_ctx *ctx, const nori_render_params *params, const uint32_t *tiles, uint32_t n_tiles,
+                               float *rgbw, float *m2 /* may be NULL */, nori_render_stats *stats);
+
+/* The tile errors: per tile t = ty * tiles_x + tx of the frame (tiles_x = ceil(width / 16), tiles_y likewise), the mean of the
+ * error map over the tile's pixels inside the frame.  One workgroup of 256 threads per tile:
+ *   thread ly * 16 + lx:  e = err of frame pixel (16 tx + lx, 16 ty + ly) by the formula of nori_hip_error_map (the same device
+ *                         function), 0 for a pixel outside the frame (and for an empty one, as there)
+ *   the 256 values, converted to binary64, are added in a fixed tree: for off = 128, 64, ..., 1: lane t < off takes lane t + off
+ *   tile_err = (float) (sum / n),  n = the tile's pixels inside the frame (binary64 division, then rounded to float32)
+ * No atomics: the same frames give the same bytes.  d_tile_err: tiles_x * tiles_y floats on the DEVICE.  Asynchronous on
+ * `stream`; reads the context's frame geometry and writes nothing of the context's, so it may run on several streams at once.  nori_hip_tile_errors_host: frames and the array in HOST memory; synchronous. */
+int nori_hip_tile_errors(nori_hip_ctx *ctx, const void *d_rgbw, const void *d_m2,
+                         void *d_tile_err /* tiles_x*tiles_y floats */, void *stream);
+int nori_hip_tile_errors_host(nori_hip_ctx *ctx, const float *rgbw, const float *m2, float *tile_err);
+
+/* Selection: tiles_out = the tiles t of tiles_in (HOST, strictly ascending, checked as for nori_hip_render_tiles) with
+ * !(d_tile_err[t] <= target), in the order of tiles_in -- a tile whose error is NaN stays in --, *n_out their number
+ * (tiles_out holds up to n_in entries).  d_tile_err: DEVICE, as nori_hip_tile_errors fills it.  On the device this is a stable
+ * compaction by prefix sum, not an atomic append: the order is part of the result, and two calls return the same bytes.  The
+ * adaptive loop below runs the same kernels on its list in device memory; this twin exists so that they can be driven without a
+ * render.  Synchronous; replaces the context's current tile list. */
+int nori_hip_select_tiles(nori_hip_ctx *ctx, const void *d_tile_err, float target,
+                          const uint32_t *tiles_in, uint32_t n_in,
+                          uint32_t *tiles_out, uint32_t *n_out);
+
+/* Adaptive sampling: nori_hip_render_to_error with the samples steered by the tile errors.  The active set starts as all
+ * tiles.  Pass k = 0, 1, ... renders samples [spp_begin + k pass_spp, spp_begin + (k + 1) pass_spp) -- the last pass may be
+ * shorter: params->spp_count is the most a pixel may get -- of the ACTIVE tiles through the tile-list render with moments,
+ * ADDING into d_rgbw and d_m2, and adds that count to tile_spp of the active tiles.  From the second pass on, the tile errors of
+ * the whole frame are then evaluated and the active set is replaced by its members with !(tile_err <= target_tile_err).  A
+ * retired tile never returns -- the set only shrinks, even where taps of a neighbour raise a retired tile's error again --, so all
+ * active tiles share one sample range and the result can be replayed from outside: pass k is nori_hip_render_tiles of
+ * {t : tile_spp[t] > k pass_spp}.  The loop stops when the set is empty or the samples are spent.
+ * d_tile_spp: tiles_x * tiles_y uint32 on the DEVICE, overwritten, or NULL.  out (may be NULL): the passes rendered, the tiles of
+ * the frame, the tiles still active when the call stopped (after the last evaluation; if the samples were spent in one pass,
+ * the tiles above the target in a measurement made for the summary alone), the least and most samples a tile received, and the
+ * error-map summary of the frames as they are left (threshold = target_tile_err).  stats (may be NULL): counters and times
+ * summed over the passes, the rest as of the last pass.  Arguments are checked as for nori_hip_render_to_error (tile_mod 1,
+ * pass_spp >= 1, target_tile_err >= 0) and nori_hip_render_tiles (fast film, NORI_SEED_PER_SAMPLE).  Synchronous.
+ * Limits.  The stopping rule looks at the samples it stops on, so a tile that stops early does so on an estimate of its
+ * variance that is biased low -- as in every such scheme; the mean stays a mean of independent samples per pixel, but the
+ * number of them depends on their values.  A retired tile's edge pixels still receive taps from active neighbours: pixels are
+ * normalised by their weight, so this is consistent.  Granularity is a tile: one noisy pixel keeps 256 sampling.
+ * nori_hip_render_adaptive_host: the same loop into scratch device frames; the RGBW frame, and where the pointers are not NULL
+ * the moment frame, the error map (height * width floats) and tile_spp of the frames as they are left, to HOST buffers. */
+typedef struct nori_adaptive_summary {
+    uint32_t passes, n_tiles, n_unconverged;   /* tiles still above the target when the call stopped */
+    uint32_t spp_min, spp_max;                 /* over the tiles */
+    nori_error_summary frame;                  /* of the frames as they are left, threshold = target */
+} nori_adaptive_summary;
+int nori_hip_render_adaptive(nori_hip_ctx *ctx, const nori_render_params *params /* spp_count = the most a pixel may get */,
+                             uint32_t pass_spp, float target_tile_err, void *d_rgbw, void *d_m2,
+                             void *d_tile_spp /* tiles_x*tiles_y uint32, may be NULL; overwritten */,
+                             nori_adaptive_summary *out, nori_render_stats *stats);
+int nori_hip_render_adaptive_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_tile_err,
+                                  float *rgbw, float *m2, float *err, uint32_t *tile_spp,
+                                  nori_adaptive_summary *out, nori_render_stats *stats);
+
 /* film_order = "reference" shared out over devices or ranks.  The reference adds a 32x32 block's samples consecutively
  * into the block's own ImageBlock (renderBlock, src/main.cpp:27-55) and the blocks into the frame in BlockGenerator's order
  * (src/block.cpp:93-152): the smallest share that keeps the order is a block, the one handed out here is a ROW of blocks.

@@ -107,6 +107,17 @@ class ErrorSummary(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AdaptiveSummary(C.Structure):
+    """nori_adaptive_summary"""
+    _fields_ = [("passes", C.c_uint32), ("n_tiles", C.c_uint32), ("n_unconverged", C.c_uint32),
+                ("spp_min", C.c_uint32), ("spp_max", C.c_uint32), ("frame", ErrorSummary)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "frame"}
+        d["frame"] = self.frame.as_dict()
+        return d
+
+
 class AccelInfo(C.Structure):
     _fields_ = [("n_triangles", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("max_depth", C.c_uint32), ("node_bytes", C.c_uint32), ("tri_bytes", C.c_uint32),
@@ -169,6 +180,15 @@ HIP_PROTOTYPES = {
                                            C.POINTER(ErrorSummary), C.POINTER(RenderStats)]),
     "nori_hip_render_to_error_host": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_float, _P, _P, _P, C.POINTER(C.c_uint32),
                                                 C.POINTER(ErrorSummary), C.POINTER(RenderStats)]),
+    "nori_hip_render_tiles": (C.c_int, [_P, C.POINTER(RenderParams), _P, C.c_uint32, _P, _P, C.POINTER(RenderStats)]),
+    "nori_hip_render_tiles_host": (C.c_int, [_P, C.POINTER(RenderParams), _P, C.c_uint32, _P, _P, C.POINTER(RenderStats)]),
+    "nori_hip_tile_errors": (C.c_int, [_P, _P, _P, _P, _P]),
+    "nori_hip_tile_errors_host": (C.c_int, [_P, _P, _P, _P]),
+    "nori_hip_select_tiles": (C.c_int, [_P, _P, C.c_float, _P, C.c_uint32, _P, C.POINTER(C.c_uint32)]),
+    "nori_hip_render_adaptive": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_float, _P, _P, _P,
+                                           C.POINTER(AdaptiveSummary), C.POINTER(RenderStats)]),
+    "nori_hip_render_adaptive_host": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_float, _P, _P, _P, _P,
+                                                C.POINTER(AdaptiveSummary), C.POINTER(RenderStats)]),
     "nori_hip_develop": (C.c_int, [_P, _P, _P, _P]),
     "nori_hip_block_acc_floats": (C.c_int, [_P, C.POINTER(C.c_size_t)]),
     "nori_hip_render_block_rows": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_uint32, _P, C.POINTER(RenderStats)]),

@@ -98,6 +98,10 @@ struct FilmLaunch {
     uint32_t n_spp;                 /* samples per pixel present in the store */
     uint32_t tile_mod, tile_rem, tiles_x, tiles_y;
     int32_t tile_w;
+    /* renders of a tile list (film_tiles.h): ordinal -> tile in place of tile_rem + ordinal * tile_mod, and tile -> ordinal or
+       0xffffffff for the resolve; DEVICE memory.  Null: the progression */
+    const uint32_t *tile_list = nullptr;
+    const uint32_t *tile_inverse = nullptr;
 };
 
 /* pixel of index `pix` (0..255) inside the tile at (x0, y0): wave w covers the 8x8 quad (w&1, w>>1) */

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "film.h"
+#include "film_tiles.h"
 
 using namespace nrt;
 
@@ -49,7 +50,7 @@ __device__ __forceinline__ void film_gather_body(int width, int height, const Fi
 
     const uint32_t part = blockIdx.x % st.n_parts;
     const uint32_t ord = fl.tile_first + blockIdx.x / st.n_parts;
-    const uint32_t tile_id = fl.tile_rem + ord * fl.tile_mod;
+    const uint32_t tile_id = fl.tile_list ? fl.tile_list[ord] : fl.tile_rem + ord * fl.tile_mod;
     const int x0 = (int) (tile_id % fl.tiles_x) * kTile, y0 = (int) (tile_id / fl.tiles_x) * kTile;
     const int border = fr.border, tile_w = fl.tile_w, taps = 2 * border + 1;
     float (*s_wx)[256] = reinterpret_cast<float (*)[256]>(s_dyn), (*s_wy)[256] = s_wx + taps;
@@ -234,7 +235,7 @@ __device__ __forceinline__ void film_gather_strips_body(int width, int height, c
 
     const uint32_t part = blockIdx.x % st.n_parts;
     const uint32_t ord = fl.tile_first + blockIdx.x / st.n_parts;
-    const uint32_t tile_id = fl.tile_rem + ord * fl.tile_mod;
+    const uint32_t tile_id = fl.tile_list ? fl.tile_list[ord] : fl.tile_rem + ord * fl.tile_mod;
     const int x0 = (int) (tile_id % fl.tiles_x) * kTile, y0 = (int) (tile_id / fl.tiles_x) * kTile;
     constexpr int border = BORDER;
     const float radius = fr.radius, lookup = fr.lookup_factor;
@@ -416,21 +417,7 @@ __global__ __launch_bounds__(kB) void film_error_map_kernel(int width, int heigh
         const int y = (int) (i / (size_t) width), x = (int) (i - (size_t) y * (size_t) width);
         const size_t at = ((size_t) (y + border) * (size_t) (width + 2 * border) + (size_t) (x + border)) * 4;
         const float4 S = *reinterpret_cast<const float4 *>(rgbw + at), M = *reinterpret_cast<const float4 *>(m2 + at);
-        if (!(S.w > 0.0f)) empty = true;
-        else {
-            const float r = 1.0f / S.w, k = (M.w * r) * r;
-            float num = 0.0f, den = 0.0f;
-            const float Sc[3] = {S.x, S.y, S.z}, Mc[3] = {M.x, M.y, M.z};
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float mu = Sc[c] * r, q = Mc[c] * r;
-                float v = q - mu * mu;
-                if (!(v > 0.0f)) v = 0.0f;
-                num = num + __builtin_sqrtf(v * k);
-                den = den + fabsf(mu);
-            }
-            err = num / (den + 0.03f);
-        }
+        err = film_pixel_error(f4{S.x, S.y, S.z, S.w}, f4{M.x, M.y, M.z, M.w}, empty);
         if (err_out) err_out[i] = err;
     }
     if (!partials) return;      /* the map alone: no summary wanted, nothing shared is written (the same for every thread of the launch) */
@@ -778,6 +765,7 @@ void film_gather_moments(const DevScene &sc, const float *d_filter_table, const 
 }
 
 void film_resolve(const DevScene &sc, const FilmStore &st, const FilmLaunch &fl, float *d_rgbw, void *stream) {
+    if (fl.tile_inverse) return film_resolve_tiles(sc, st, fl, d_rgbw, stream);      /* a render by list (film_tiles.h) */
     const int border = sc.filter.border, cols = sc.camera.width + 2 * border, rows = sc.camera.height + 2 * border;
     hipLaunchKernelGGL(film_resolve_kernel, dim3((cols + 255) / 256, rows), dim3(256), 0, (hipStream_t) stream, sc.camera.width,
                        sc.camera.height, border, fl.tile_w, fl.tiles_x, fl.tiles_y, fl.tile_mod, fl.tile_rem, st.n_parts,

@@ -35,6 +35,7 @@
 
 #include "../../../include/nori_hip.h"
 #include "film.h"
+#include "film_tiles.h"
 #include "ktimer.h"
 #include "shade_tables.h"
 #include "rt_path.h"
@@ -78,6 +79,7 @@ struct RenderArgs {
     int32_t tile_w;             /* kTile + 2 * border                      */
     uint32_t debug_flags;       /* bit0: skip the filtered splat (experiments only) */
     uint32_t th_shade, th_inner, th_leaf;   /* lanes of a wave that must want a kind of work for it to run */
+    const uint32_t *tile_list = nullptr;    /* a render by list (film_tiles.h): selected-tile ordinal -> tile, DEVICE memory; null: the progression */
 };
 
 /* MATSET = kAnyBsdf | kTextured (rt_path.h): the kernel of scenes with textured albedos; kAnyBsdf: every other scene */
@@ -96,7 +98,7 @@ __global__ __launch_bounds__(kBlock, NORI_RENDER_MIN_WAVES) void render_kernel(D
 
     /* which tile / which samples */
     const uint32_t sel = blockIdx.x / args.n_chunks, chunk = blockIdx.x % args.n_chunks;
-    const uint32_t tile_id = args.tile_rem + sel * args.tile_mod;
+    const uint32_t tile_id = args.tile_list ? args.tile_list[sel] : args.tile_rem + sel * args.tile_mod;
     const int x0 = (int) (tile_id % args.tiles_x) * kTile, y0 = (int) (tile_id / args.tiles_x) * kTile;
     const uint32_t s0 = args.spp_begin + chunk * args.chunk_spp;
     const uint32_t s1 = min(s0 + args.chunk_spp, args.spp_begin + args.spp_count);
@@ -436,6 +438,7 @@ struct nori_hip_ctx {
     WfEngine *wf = nullptr;
     FilmStore film;
     FilmMoments moments;      /* renders that keep second moments, nori_hip_error_map: a second set of tile accumulators, partial sums */
+    FilmTiles tiles;          /* renders by tile list, tile selection, the adaptive loop: lists, inverse table, tile errors (film_tiles.h) */
 };
 
 static std::string g_create_error;
@@ -541,6 +544,7 @@ void nori_hip_destroy(nori_hip_ctx *ctx) {
     wavefront_destroy(ctx->wf);
     film_release(ctx->film);
     film_moments_release(ctx->moments);
+    film_tiles_release(ctx->tiles);
     if (ctx->d_stats) (void) hipFree(ctx->d_stats);
     delete ctx;
 }
@@ -1067,7 +1071,8 @@ static hipError_t launch_render(nori_hip_ctx *ctx, const RenderArgs &a, const Fi
 /* nori_hip_render, and nori_hip_render_block_rows (share != nullptr: the block rows of a reference-order film; the accumulators
    of their blocks go to share->block_acc instead of a frame) */
 static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void *d_rgbw, nori_render_stats *stats, const FilmBlockRows *share,
-                       float *d_m2 = nullptr /* nori_hip_render_moments: the same samples' second moments are added here */) {
+                       float *d_m2 = nullptr /* nori_hip_render_moments: the same samples' second moments are added here */,
+                       const FilmTiles *tiles = nullptr /* nori_hip_render_tiles: exactly the tiles of its current list */) {
     REQUIRE_ACCEL(ctx);
     if (!params || (!d_rgbw && !share)) return NORI_ERR_INVALID_ARGUMENT;
     if (d_m2 && (ctx->film_reference || share)) {
@@ -1086,6 +1091,11 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
     }
     if (ctx->host.filter.border > 8) { ctx->error = "render: reconstruction filter radius too large for the LDS tile"; return NORI_ERR_UNSUPPORTED; }
     if (ctx->film_reference && params->tile_mod != 1) { ctx->error = "render: film_order = reference renders whole frames (a block's samples are added consecutively)"; return NORI_ERR_UNSUPPORTED; }
+    if (tiles && (ctx->film_reference || share || params->seed_mode == NORI_SEED_NORI_BLOCK)) {
+        ctx->error = "render_tiles: a tile list is rendered by the fast film with NORI_SEED_PER_SAMPLE only (reference order and the block-serial sampler render whole frames)";
+        return NORI_ERR_UNSUPPORTED;
+    }
+    if (tiles && (params->tile_mod != 1 || params->tile_rem != 0)) { ctx->error = "render_tiles: the list names the tiles (tile_mod 1, tile_rem 0)"; return NORI_ERR_INVALID_ARGUMENT; }
     DeviceGuard g(ctx->device);
     hipStream_t s = (hipStream_t) params->stream;
 
@@ -1104,6 +1114,8 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
         const uint32_t t0 = std::min(film_block_rows_first_tile(row0, a.tiles_x), n_tiles), t1 = std::min(film_block_rows_first_tile(row1, a.tiles_x), n_tiles);
         a.tile_rem = t0; a.n_sel_tiles = t1 - t0;
     }
+    const uint32_t *tile_inverse = nullptr;
+    if (tiles) { a.n_sel_tiles = tiles->n; a.tile_list = tiles->list[tiles->cur]; tile_inverse = tiles->inverse; }
     a.tile_w = kTile + 2 * ctx->host.filter.border;
     a.th_shade = 44; a.th_inner = 1; a.th_leaf = 1;
     a.debug_flags = getenv("NORI_HIP_NOSPLAT") ? 1u : 0u;
@@ -1194,6 +1206,7 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
            this context counts as free) -- a second context or another process may own part of the HBM */
         wl.film_reference = ctx->film_reference; wl.film_share = share;
         wl.d_m2 = d_m2; wl.moments = d_m2 ? &ctx->moments : nullptr;
+        wl.tile_list = a.tile_list; wl.tile_inverse = tile_inverse;
         /* what the call can use at all: a batch never holds more samples than the call has, the pool never more paths than a batch */
         const size_t call_samples = (size_t) a.n_sel_tiles * 256 * a.spp_count;
         /* (reference film order: the frame is one batch whatever the options say -- the pool need not hold it) */
@@ -1251,6 +1264,7 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
         FilmLaunch fl;
         fl.tile_first = 0; fl.store_tile_first = 0; fl.n_tiles = a.n_sel_tiles; fl.tile_mod = a.tile_mod; fl.tile_rem = a.tile_rem;
         fl.tiles_x = a.tiles_x; fl.tiles_y = a.tiles_y; fl.tile_w = a.tile_w;
+        fl.tile_list = a.tile_list; fl.tile_inverse = tile_inverse;
         const bool count = params->count_traversal != 0;
         const uint32_t need = ctx->bvh.max_depth + 1;
         for (uint32_t sb = 0; sb < a.spp_count; sb += spp_per_launch) {
@@ -1433,6 +1447,202 @@ int nori_hip_render_to_error_host(nori_hip_ctx *ctx, const nori_render_params *p
     }
     HIP_TRY(ctx, hipMemcpy(rgbw, d_rgbw, fb, hipMemcpyDeviceToHost));
     if (m2) HIP_TRY(ctx, hipMemcpy(m2, d_m2, fb, hipMemcpyDeviceToHost));
+    return NORI_OK;
+}
+
+/* ---- tile lists, tile errors, selection, the adaptive loop (film_tiles.h) ---- */
+
+static uint32_t frame_tiles(const nori_hip_ctx *ctx) {
+    return (uint32_t) ((ctx->host.camera.width + kTile - 1) / kTile) * (uint32_t) ((ctx->host.camera.height + kTile - 1) / kTile);
+}
+
+/* a host list: strictly ascending raster ids of tiles of the frame */
+static int check_tile_list(nori_hip_ctx *ctx, const char *what, const uint32_t *tiles, uint32_t n) {
+    const uint32_t n_frame = frame_tiles(ctx);
+    if (n && !tiles) { ctx->error = std::string(what) + ": no tile list"; return NORI_ERR_INVALID_ARGUMENT; }
+    for (uint32_t i = 0; i < n; ++i) {
+        if (tiles[i] >= n_frame) { ctx->error = std::string(what) + ": tile " + std::to_string(tiles[i]) + " (entry " + std::to_string(i) + ") is out of range: the frame has " + std::to_string(n_frame) + " tiles"; return NORI_ERR_INVALID_ARGUMENT; }
+        if (i && tiles[i] <= tiles[i - 1]) { ctx->error = std::string(what) + ": the tile list must be strictly ascending (entry " + std::to_string(i) + ": " + std::to_string(tiles[i]) + " after " + std::to_string(tiles[i - 1]) + ")"; return NORI_ERR_INVALID_ARGUMENT; }
+    }
+    return NORI_OK;
+}
+
+/* what render_impl refuses for a list, checked before the list is looked at (an empty list is refused the same way) */
+static int check_tiles_render(nori_hip_ctx *ctx, const nori_render_params *params) {
+    if (ctx->film_reference || params->seed_mode == NORI_SEED_NORI_BLOCK) {
+        ctx->error = "render_tiles: a tile list is rendered by the fast film with NORI_SEED_PER_SAMPLE only (reference order and the block-serial sampler render whole frames)";
+        return NORI_ERR_UNSUPPORTED;
+    }
+    if (params->tile_mod != 1 || params->tile_rem != 0) { ctx->error = "render_tiles: the list names the tiles (tile_mod 1, tile_rem 0)"; return NORI_ERR_INVALID_ARGUMENT; }
+    return NORI_OK;
+}
+
+static void add_stats(nori_render_stats &total, const nori_render_stats &st) {
+    total.n_camera_samples += st.n_camera_samples; total.n_closest_rays += st.n_closest_rays; total.n_shadow_rays += st.n_shadow_rays;
+    total.n_node_tests += st.n_node_tests; total.n_tri_tests += st.n_tri_tests; total.n_invalid += st.n_invalid;
+    total.kernel_ms += st.kernel_ms; total.trace_ms += st.trace_ms; total.shade_ms += st.shade_ms; total.film_ms += st.film_ms; total.tail_ms += st.tail_ms;
+    total.n_workgroups += st.n_workgroups; total.n_trace_launches += st.n_trace_launches;
+    total.lds_bytes = st.lds_bytes; total.engine = st.engine; total.trace_cus = st.trace_cus; total.tail_cus = st.tail_cus;
+}
+
+int nori_hip_render_tiles(nori_hip_ctx *ctx, const nori_render_params *params, const uint32_t *tiles, uint32_t n_tiles,
+                          void *d_rgbw, void *d_m2, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !d_rgbw) return NORI_ERR_INVALID_ARGUMENT;
+    int rc = check_tiles_render(ctx, params);
+    if (rc) return rc;
+    rc = check_tile_list(ctx, "render_tiles", tiles, n_tiles);
+    if (rc) return rc;
+    if (n_tiles == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return NORI_OK; }      /* nothing is touched */
+    DeviceGuard g(ctx->device);
+    const std::string err = film_tiles_upload(ctx->tiles, tiles, n_tiles, frame_tiles(ctx), params->stream);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    return render_impl(ctx, params, d_rgbw, stats, nullptr, (float *) d_m2, &ctx->tiles);
+}
+
+int nori_hip_render_tiles_host(nori_hip_ctx *ctx, const nori_render_params *params, const uint32_t *tiles, uint32_t n_tiles,
+                               float *rgbw, float *m2, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    const size_t fb = frame_floats(ctx) * sizeof(float);
+    SCRATCH_OUT(ctx, df, 2 * fb);
+    HIP_TRY(ctx, hipMemset(df.p, 0, 2 * fb));
+    nori_render_stats local;
+    int rc = nori_hip_render_tiles(ctx, params, tiles, n_tiles, df.p, m2 ? (char *) df.p + fb : nullptr, stats ? stats : &local);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(rgbw, df.p, fb, hipMemcpyDeviceToHost));
+    if (m2) HIP_TRY(ctx, hipMemcpy(m2, (char *) df.p + fb, fb, hipMemcpyDeviceToHost));
+    return NORI_OK;
+}
+
+int nori_hip_tile_errors(nori_hip_ctx *ctx, const void *d_rgbw, const void *d_m2, void *d_tile_err, void *stream) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (!d_rgbw || !d_m2 || !d_tile_err) { ctx->error = "tile_errors: needs both frames and an array to fill"; return NORI_ERR_INVALID_ARGUMENT; }
+    DeviceGuard g(ctx->device);
+    const std::string err = film_tile_errors(ctx->dev, (const float *) d_rgbw, (const float *) d_m2, (float *) d_tile_err, stream);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    return NORI_OK;
+}
+
+int nori_hip_tile_errors_host(nori_hip_ctx *ctx, const float *rgbw, const float *m2, float *tile_err) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (!rgbw || !m2 || !tile_err) { ctx->error = "tile_errors: needs both frames and an array to fill"; return NORI_ERR_INVALID_ARGUMENT; }
+    DeviceGuard g(ctx->device);
+    const size_t fb = frame_floats(ctx) * sizeof(float), eb = (size_t) frame_tiles(ctx) * sizeof(float);
+    SCRATCH_OUT(ctx, df, 2 * fb + eb);
+    char *d_rgbw = (char *) df.p, *d_m2 = d_rgbw + fb, *d_err = d_m2 + fb;
+    HIP_TRY(ctx, hipMemcpy(d_rgbw, rgbw, fb, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(d_m2, m2, fb, hipMemcpyHostToDevice));
+    int rc = nori_hip_tile_errors(ctx, d_rgbw, d_m2, d_err, nullptr);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(tile_err, d_err, eb, hipMemcpyDeviceToHost));      /* (a blocking copy: behind the kernel on the default stream) */
+    return NORI_OK;
+}
+
+int nori_hip_select_tiles(nori_hip_ctx *ctx, const void *d_tile_err, float target, const uint32_t *tiles_in, uint32_t n_in,
+                          uint32_t *tiles_out, uint32_t *n_out) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (!d_tile_err || !n_out || (n_in && !tiles_out)) { ctx->error = "select_tiles: needs the tile errors, a list to fill and its length"; return NORI_ERR_INVALID_ARGUMENT; }
+    int rc = check_tile_list(ctx, "select_tiles", tiles_in, n_in);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    std::string err = film_tiles_upload(ctx->tiles, tiles_in, n_in, frame_tiles(ctx), nullptr);
+    if (err.empty()) err = film_tiles_select(ctx->tiles, (const float *) d_tile_err, target, frame_tiles(ctx), nullptr);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    *n_out = ctx->tiles.n;
+    if (ctx->tiles.n) HIP_TRY(ctx, hipMemcpy(tiles_out, ctx->tiles.list[ctx->tiles.cur], (size_t) ctx->tiles.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return NORI_OK;
+}
+
+int nori_hip_render_adaptive(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_tile_err,
+                             void *d_rgbw, void *d_m2, void *d_tile_spp, nori_adaptive_summary *out, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !d_rgbw || !d_m2) return NORI_ERR_INVALID_ARGUMENT;
+    if (pass_spp == 0) { ctx->error = "render_adaptive: pass_spp must be at least 1"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (!(target_tile_err >= 0.0f)) { ctx->error = "render_adaptive: the target error must be a number >= 0"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (params->tile_mod != 1) { ctx->error = "render_adaptive: renders whole frames (tile_mod 1): the loop shares the tiles out itself"; return NORI_ERR_INVALID_ARGUMENT; }
+    int rc = check_tiles_render(ctx, params);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    hipStream_t s = (hipStream_t) params->stream;
+    FilmTiles &T = ctx->tiles;
+    const uint32_t n_frame = frame_tiles(ctx);
+    {      /* the active set starts as all tiles */
+        std::vector<uint32_t> all(n_frame);
+        for (uint32_t i = 0; i < n_frame; ++i) all[i] = i;
+        const std::string err = film_tiles_upload(T, all.data(), n_frame, n_frame, s);
+        if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    }
+    HIP_TRY(ctx, hipMemsetAsync(T.tile_spp, 0, (size_t) n_frame * sizeof(uint32_t), s));
+    nori_render_stats total; memset(&total, 0, sizeof(total));
+    uint32_t done = 0, passes = 0;
+    bool evaluated = false;
+    while (done < params->spp_count && T.n > 0) {
+        nori_render_params p = *params;
+        p.spp_begin = params->spp_begin + done; p.spp_count = std::min(pass_spp, params->spp_count - done);
+        nori_render_stats st;
+        rc = render_impl(ctx, &p, d_rgbw, &st, nullptr, (float *) d_m2, &T);
+        if (rc) return rc;
+        add_stats(total, st);
+        film_tiles_add_spp(T, T.tile_spp, p.spp_count, s);
+        done += p.spp_count; ++passes;
+        evaluated = false;
+        if (passes >= 2) {      /* (one pass of few samples has no variance to speak of) */
+            std::string err = film_tile_errors(ctx->dev, (const float *) d_rgbw, (const float *) d_m2, T.tile_err, s);
+            if (err.empty()) err = film_tiles_select(T, T.tile_err, target_tile_err, n_frame, s);
+            if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+            evaluated = true;
+        }
+    }
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        uint32_t n_unconverged = T.n;
+        if (!evaluated) {      /* the samples were spent in one pass: the frames as they are left are measured once, without retiring anything */
+            std::string err = film_tile_errors(ctx->dev, (const float *) d_rgbw, (const float *) d_m2, T.tile_err, s);
+            if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+            std::vector<float> te(n_frame);
+            HIP_TRY(ctx, hipMemcpyAsync(te.data(), T.tile_err, (size_t) n_frame * sizeof(float), hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, hipStreamSynchronize(s));
+            n_unconverged = 0;
+            for (uint32_t i = 0; i < n_frame; ++i) n_unconverged += !(te[i] <= target_tile_err) ? 1u : 0u;
+        }
+        std::vector<uint32_t> spp(n_frame);
+        HIP_TRY(ctx, hipMemcpyAsync(spp.data(), T.tile_spp, (size_t) n_frame * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        out->passes = passes; out->n_tiles = n_frame; out->n_unconverged = n_unconverged;
+        out->spp_min = *std::min_element(spp.begin(), spp.end()); out->spp_max = *std::max_element(spp.begin(), spp.end());
+        rc = nori_hip_error_map(ctx, d_rgbw, d_m2, nullptr, target_tile_err, &out->frame, params->stream);
+        if (rc) return rc;
+    }
+    if (d_tile_spp) HIP_TRY(ctx, hipMemcpyAsync(d_tile_spp, T.tile_spp, (size_t) n_frame * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    if (stats) *stats = total;
+    return NORI_OK;
+}
+
+int nori_hip_render_adaptive_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_tile_err,
+                                  float *rgbw, float *m2, float *err, uint32_t *tile_spp, nori_adaptive_summary *out, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    const size_t fb = frame_floats(ctx) * sizeof(float);
+    const size_t eb = (size_t) ctx->host.camera.width * (size_t) ctx->host.camera.height * sizeof(float);
+    const size_t tb = (size_t) frame_tiles(ctx) * sizeof(uint32_t);
+    SCRATCH_OUT(ctx, df, 2 * fb + eb + tb);
+    HIP_TRY(ctx, hipMemset(df.p, 0, 2 * fb + eb + tb));
+    char *d_rgbw = (char *) df.p, *d_m2 = d_rgbw + fb, *d_err = d_m2 + fb, *d_spp = d_err + eb;
+    int rc = nori_hip_render_adaptive(ctx, params, pass_spp, target_tile_err, d_rgbw, d_m2, d_spp, out, stats);
+    if (rc) return rc;
+    if (err) {
+        rc = nori_hip_error_map(ctx, d_rgbw, d_m2, d_err, target_tile_err, nullptr, params->stream);
+        if (rc) return rc;
+        HIP_TRY(ctx, hipStreamSynchronize((hipStream_t) params->stream));
+        HIP_TRY(ctx, hipMemcpy(err, d_err, eb, hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(ctx, hipMemcpy(rgbw, d_rgbw, fb, hipMemcpyDeviceToHost));
+    if (m2) HIP_TRY(ctx, hipMemcpy(m2, d_m2, fb, hipMemcpyDeviceToHost));
+    if (tile_spp) HIP_TRY(ctx, hipMemcpy(tile_spp, d_spp, tb, hipMemcpyDeviceToHost));
     return NORI_OK;
 }
 

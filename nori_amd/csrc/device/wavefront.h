@@ -23,6 +23,8 @@ struct WfLaunch {
     const FilmBlockRows *film_share = nullptr;      /* reference order: the selected tiles are these block rows (tile_mod 1, tile_rem = their first tile) */
     float *d_m2 = nullptr;      /* non-null: the film keeps the samples' second moments and adds them into this frame (film.h) ... */
     FilmMoments *moments = nullptr;      /* ... through the context's second set of accumulators */
+    const uint32_t *tile_list = nullptr;      /* a render by list (film_tiles.h): the n_sel_tiles tiles by ordinal, DEVICE memory; null: the progression ... */
+    const uint32_t *tile_inverse = nullptr;   /* ... and the list's inverse table for the resolve */
 };
 
 struct WfStats {

@@ -37,6 +37,7 @@
 #include <cstdlib>
 #include <string>
 #include <type_traits>
+#include <mutex>
 #include <vector>
 
 /* The laboratory -- perturbations of the node step and of wf_shade, the cycle profile of a wave -- lives in wf_experiments.h and is
@@ -110,6 +111,7 @@ struct WfBatch {
     int32_t inner_repeat;               /* wf_extend: node steps repeat while at least this many lanes are at inner nodes (65: never) */
     uint32_t flags;                     /* kBatch* */
     uint32_t pool;                      /* paths a pass works on: the stored survivors + as many NEW camera samples of the batch as fill it up */
+    const uint32_t *tile_list = nullptr;    /* a render by list (film_tiles.h): selected-tile ordinal -> tile; null: tile_rem + ordinal * tile_mod */
 };
 
 /* Regeneration (constant population).  A pass over state copy `cur` works on the n_s survivors the last wf_shade stored plus
@@ -286,7 +288,7 @@ __device__ __forceinline__ bool first_vertex(const DevScene &sc, const WfBatch &
     const uint32_t per_tile = 256u * bt.n_spp;
     const uint32_t tsel = p / per_tile, rem = p - tsel * per_tile;
     const uint32_t sl = rem >> 8, pix = rem & 255u;
-    const uint32_t tile_id = bt.tile_rem + (bt.tile_first + tsel) * bt.tile_mod;
+    const uint32_t tile_id = bt.tile_list ? bt.tile_list[bt.tile_first + tsel] : bt.tile_rem + (bt.tile_first + tsel) * bt.tile_mod;
     const int x0 = (int) (tile_id % bt.tiles_x) * kTile, y0 = (int) (tile_id / bt.tiles_x) * kTile;
     int px, py; film_tile_pixel((int) pix, x0, y0, px, py);
     if (px >= sc.camera.width || py >= sc.camera.height) return false;
@@ -1119,7 +1121,39 @@ int wf_top_capacity(bool wide_nodes, bool records_32b, bool deeper_than_lds_stac
    events, what the device offers.  One per nori_hip_ctx (= per GPU); nothing here is process-global,
    so contexts on different devices, or two contexts on one device, never share or free each
    other's buffers. */
+/* Streams the engines are done with are PARKED, not destroyed, and the next engine on the same device that wants a stream of the
+   same kind takes a parked one.  Why: with the HIP runtime this is built against, a hipMalloc that fails on a full device ends
+   in a segmentation fault inside the runtime if streams with a CU mask that ran kernels with scratch memory were destroyed earlier
+   in the process -- with project code or without (a 60-line program: create two masked streams, run a kernel with a private
+   array on them, destroy them, fill the device, ask for more).  The same program survives when the streams are kept.  The
+   out-of-memory retry of render_impl depends on that failure being an error code, and a process renders through many contexts.
+   Parked streams are idle (synchronised before they are parked) and belong to nobody; one mutex guards the list. */
+enum StreamKind { kStreamPlain = 0, kStreamSplitExtend = 1, kStreamSplitShade = 2, kStreamTail = 3 };
+struct ParkedStream { int device, kind, cus; hipStream_t stream; };
+std::mutex g_parked_mutex;
+std::vector<ParkedStream> g_parked;
+
+void park_stream(int device, int kind, int cus, hipStream_t &st) {
+    if (!st) return;
+    (void) hipStreamSynchronize(st);
+    std::lock_guard<std::mutex> lock(g_parked_mutex);
+    g_parked.push_back(ParkedStream{device, kind, cus, st});
+    st = nullptr;
+}
+
+hipStream_t unpark_stream(int device, int kind, int cus) {
+    std::lock_guard<std::mutex> lock(g_parked_mutex);
+    for (size_t i = 0; i < g_parked.size(); ++i)
+        if (g_parked[i].device == device && g_parked[i].kind == kind && g_parked[i].cus == cus) {
+            hipStream_t st = g_parked[i].stream;
+            g_parked.erase(g_parked.begin() + (long) i);
+            return st;
+        }
+    return nullptr;
+}
+
 struct WfEngine {
+    int device = 0;                 /* the context's device: parked streams are handed out per device */
     Pool pool;
     hipStream_t streams[2] = {nullptr, nullptr};
     hipEvent_t events[3] = {nullptr, nullptr, nullptr};
@@ -1148,8 +1182,9 @@ struct WfEngine {
    profiles/r5_07_tail_overlap_masks.txt). */
 bool ensure_tail_stream(WfEngine &e, int cus) {
     if (e.tail_stream && e.tail_stream_cus == cus) return true;
-    if (e.tail_stream) { (void) hipStreamDestroy(e.tail_stream); e.tail_stream = nullptr; e.tail_stream_cus = 0; }
+    if (e.tail_stream) { park_stream(e.device, kStreamTail, e.tail_stream_cus, e.tail_stream); e.tail_stream_cus = 0; }
     if (cus < 8 || cus >= e.n_cus) return false;
+    if ((e.tail_stream = unpark_stream(e.device, kStreamTail, cus)) != nullptr) { e.tail_stream_cus = cus; return true; }
     const uint32_t words = (uint32_t) ((e.n_cus + 31) / 32);
     std::vector<uint32_t> mask(words, 0u);
     for (int i = 0; i < cus; ++i) mask[(size_t) i / 32] |= 1u << (i % 32);
@@ -1184,8 +1219,13 @@ std::string ensure_tail_side(WfEngine &e, size_t records, size_t spill_ints) {
    two sets are even over XCDs and shader engines.  Returns false (and leaves the engine unsplit) if the runtime refuses. */
 bool ensure_split_streams(WfEngine &e, int cus) {
     if (e.split_cus == cus && e.split_streams[0] && e.split_streams[1]) return true;
-    for (hipStream_t &st : e.split_streams) if (st) { (void) hipStreamDestroy(st); st = nullptr; }
+    park_stream(e.device, kStreamSplitExtend, e.split_cus, e.split_streams[0]); park_stream(e.device, kStreamSplitShade, e.split_cus, e.split_streams[1]);
     e.split_cus = 0;
+    {      /* a parked pair of this device and share */
+        hipStream_t a = unpark_stream(e.device, kStreamSplitExtend, cus), b = a ? unpark_stream(e.device, kStreamSplitShade, cus) : nullptr;
+        if (a && b) { e.split_streams[0] = a; e.split_streams[1] = b; e.split_cus = cus; return true; }
+        if (a) park_stream(e.device, kStreamSplitExtend, cus, a);
+    }
     const int rows_total = e.n_cus / 8, rows = cus / 8;
     if (rows < 1 || rows >= rows_total) return false;
     const uint32_t words = (uint32_t) ((e.n_cus + 31) / 32);
@@ -1199,7 +1239,7 @@ bool ensure_split_streams(WfEngine &e, int cus) {
     if (hipExtStreamCreateWithCUMask(&e.split_streams[0], words, extend.data()) != hipSuccess ||
         hipExtStreamCreateWithCUMask(&e.split_streams[1], words, shade.data()) != hipSuccess) {
         (void) hipGetLastError();
-        for (hipStream_t &st : e.split_streams) if (st) { (void) hipStreamDestroy(st); st = nullptr; }
+        for (hipStream_t &st : e.split_streams) if (st) { (void) hipStreamDestroy(st); st = nullptr; }      /* (never ran a kernel) */
         return false;
     }
     e.split_cus = cus;
@@ -1210,6 +1250,7 @@ WfEngine *wavefront_create() {
     WfEngine *e = new WfEngine();
     int dev = 0; hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) e->n_cus = prop.multiProcessorCount;
+    e->device = dev;
     if (e->n_cus <= 0) e->n_cus = 256;
     return e;
 }
@@ -1217,12 +1258,12 @@ WfEngine *wavefront_create() {
 void wavefront_destroy(WfEngine *e) {
     if (!e) return;
     e->pool.release();
-    for (hipStream_t &st : e->streams) if (st) { (void) hipStreamDestroy(st); st = nullptr; }
-    for (hipStream_t &st : e->split_streams) if (st) { (void) hipStreamDestroy(st); st = nullptr; }
+    for (hipStream_t &st : e->streams) park_stream(e->device, kStreamPlain, 0, st);
+    park_stream(e->device, kStreamSplitExtend, e->split_cus, e->split_streams[0]); park_stream(e->device, kStreamSplitShade, e->split_cus, e->split_streams[1]);
     for (hipEvent_t &ev : e->events) if (ev) { (void) hipEventDestroy(ev); ev = nullptr; }
     for (auto &pe : e->pipe_events) for (hipEvent_t &ev : pe) if (ev) { (void) hipEventDestroy(ev); ev = nullptr; }
     for (hipEvent_t &ev : e->tail_events) if (ev) { (void) hipEventDestroy(ev); ev = nullptr; }
-    if (e->tail_stream) { (void) hipStreamDestroy(e->tail_stream); e->tail_stream = nullptr; }
+    park_stream(e->device, kStreamTail, e->tail_stream_cus, e->tail_stream);
     e->tail.release();
     delete e;
 }
@@ -1378,6 +1419,7 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
         } else if (n_pipes == 1 && !overlap) P.stream = P.extend_stream = s;
         else {      /* (overlap: the bulk on a stream of the engine's own, too -- the caller's may be the legacy default stream, which
                        runs nothing beside the work of another stream) */
+            if (!g_streams[k]) g_streams[k] = unpark_stream(eng.device, kStreamPlain, 0);
             if (!g_streams[k]) WF_TRY(hipStreamCreateWithFlags(&g_streams[k], hipStreamNonBlocking));
             P.stream = P.extend_stream = g_streams[k];
         }
@@ -1493,6 +1535,7 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
     for (int k = 0; k < n_pipes; ++k) pipes[k].b.census = d_census;
     FilmLaunch fl;
     fl.tile_mod = L.tile_mod; fl.tile_rem = L.tile_rem; fl.tiles_x = L.tiles_x; fl.tiles_y = L.tiles_y; fl.tile_w = L.tile_w;
+    fl.tile_list = L.tile_list; fl.tile_inverse = L.tile_inverse;
 
     while (true) {
         bool any = false;
@@ -1503,6 +1546,7 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
             const uint32_t nt = std::min(P.tiles_b, P.tile_hi - P.t0), ns = std::min(P.spp_b, L.spp_count - P.s0);
             P.bt.tile_first = P.t0; P.bt.n_tiles = nt; P.bt.s_first = L.spp_begin + P.s0; P.bt.n_spp = ns;
             P.bt.tile_mod = L.tile_mod; P.bt.tile_rem = L.tile_rem; P.bt.tiles_x = L.tiles_x; P.bt.tile_w = L.tile_w;
+            P.bt.tile_list = L.tile_list;
             P.bt.inner_repeat = inner_repeat;
             P.bt.flags = (no_asm_loop ? kBatchNoAsmLoop : 0u) | (count_q ? kBatchCountQ : 0u);
             P.bt.pool = (uint32_t) pool_paths;

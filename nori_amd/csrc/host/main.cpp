@@ -1,5 +1,5 @@
 /*
- * main.cpp -- `nori <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K]]`
+ * main.cpp -- `nori <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]]`
  * Command line of the reference (src/main.cpp:150-246).  There is no GUI on a
  * compute node: --no-gui is accepted and implied; --threads is accepted for
  * compatibility (the work runs on the GPU).  --seed block renders with the
@@ -11,7 +11,9 @@
  * in passes of K samples per pixel (--pass-spp, default 16) until the mean of the per-pixel
  * error map (include/nori_hip.h: nori_hip_error_map) is at most E, the scene's sampleCount
  * being the most it spends; it prints where it stopped and writes the map as
- * <scene>.error.exr next to the frame (one device only).  A <test> root runs during parsing
+ * <scene>.error.exr next to the frame (one device only).  With --adaptive a pass renders only
+ * the 16x16 tiles whose mean error is still above E (nori_hip_render_adaptive); the samples
+ * every pixel's tile received are written as <scene>.spp.exr.  A <test> root runs during parsing
  * (its activate()), as in the reference; failures exit with -1.
  */
 #include <nori/bitmap.h>
@@ -21,11 +23,11 @@ using namespace nori;
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        cerr << "Syntax: " << argv[0] << " <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K]]" << endl;
+        cerr << "Syntax: " << argv[0] << " <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]]" << endl;
         return -1;
     }
     std::string sceneName;
-    bool toError = false, havePassSpp = false;
+    bool toError = false, havePassSpp = false, adaptive = false;
     float targetError = 0.0f;
     long passSpp = 16;
     int gpus = 1;
@@ -73,6 +75,9 @@ int main(int argc, char **argv) {
             }
             havePassSpp = true; ++i;
             continue;
+        } else if (token == "--adaptive") {
+            adaptive = true;
+            continue;
         } else if (token == "--split" || token == "--merge" || token == "--film-order") {
             if (i + 1 >= argc) {
                 cerr << "\"" << token << "\" expects a value." << endl;
@@ -96,6 +101,10 @@ int main(int argc, char **argv) {
         cerr << "Usage: \"--pass-spp\" goes with --target-error E." << endl;
         return -1;
     }
+    if (adaptive && !toError) {
+        cerr << "Usage: \"--adaptive\" goes with --target-error E." << endl;
+        return -1;
+    }
     if (toError && gpus > 1) {
         cerr << "\"--target-error\" renders on one device: moment frames over several GPUs are not supported (got --gpus " << gpus << ")." << endl;
         return -1;
@@ -115,7 +124,10 @@ int main(int argc, char **argv) {
             uint32_t sppDone = 0;
             nori_error_summary summary;
             std::vector<float> errorMap;
-            std::unique_ptr<ImageBlock> result = toError ? renderSceneToError(scene, targetError, (uint32_t) passSpp, sppDone, summary, errorMap, &st)
+            nori_adaptive_summary adaptiveSummary;
+            std::vector<uint32_t> tileSpp;
+            std::unique_ptr<ImageBlock> result = adaptive ? renderSceneAdaptive(scene, targetError, (uint32_t) passSpp, adaptiveSummary, errorMap, tileSpp, &st)
+                                                 : toError ? renderSceneToError(scene, targetError, (uint32_t) passSpp, sppDone, summary, errorMap, &st)
                                                          : renderScene(scene, &st);
             cout << "done. (took " << timer.elapsedString() << "; kernel " << timeString(st.kernel_ms, true) << ", "
                  << (double) (st.n_closest_rays + st.n_shadow_rays) / (st.kernel_ms * 1e3) << " Mrays/s)" << endl;
@@ -125,7 +137,21 @@ int main(int argc, char **argv) {
             if (lastdot != std::string::npos) outputName.erase(lastdot, std::string::npos);
             bitmap->saveEXR(outputName);
             bitmap->savePNG(outputName);
-            if (toError) {
+            if (adaptive) {
+                const nori_error_summary &f = adaptiveSummary.frame;
+                cout << "Stopped after " << adaptiveSummary.passes << " passes: " << adaptiveSummary.spp_min << " to " << adaptiveSummary.spp_max << " samples per pixel, "
+                     << adaptiveSummary.n_unconverged << " of " << adaptiveSummary.n_tiles << " tiles above the target " << targetError << "; mean error "
+                     << f.sum_err / (double) std::max<uint64_t>(f.n_pixels, 1) << " (max " << f.max_err << ", " << f.n_above << " of " << f.n_pixels << " pixels above the target)" << endl;
+                Bitmap errorBitmap(scene->getCamera()->getOutputSize()), sppBitmap(scene->getCamera()->getOutputSize());
+                const int tilesX = ((int) errorBitmap.cols() + NORI_TILE_SIZE - 1) / NORI_TILE_SIZE;
+                for (int y = 0; y < errorBitmap.rows(); ++y)
+                    for (int x = 0; x < errorBitmap.cols(); ++x) {
+                        errorBitmap.set(y, x, Color3f(errorMap[(size_t) y * errorBitmap.cols() + x]));
+                        sppBitmap.set(y, x, Color3f((float) tileSpp[(size_t) (y / NORI_TILE_SIZE) * tilesX + x / NORI_TILE_SIZE]));
+                    }
+                errorBitmap.saveEXR(outputName + ".error");
+                sppBitmap.saveEXR(outputName + ".spp");
+            } else if (toError) {
                 cout << "Stopped at " << sppDone << " samples per pixel: mean error " << summary.sum_err / (double) std::max<uint64_t>(summary.n_pixels, 1)
                      << " (target " << targetError << ", max " << summary.max_err << ", " << summary.n_above << " of " << summary.n_pixels << " pixels above the target)" << endl;
                 Bitmap errorBitmap(scene->getCamera()->getOutputSize());

@@ -303,5 +303,9 @@ std::unique_ptr<ImageBlock> renderScene(Scene *scene, nori_render_stats *stats =
    `errorMap` (width * height floats) receives the map of the frame as returned. */
 std::unique_ptr<ImageBlock> renderSceneToError(Scene *scene, float targetError, uint32_t passSpp, uint32_t &sppDone,
                                                nori_error_summary &summary, std::vector<float> &errorMap, nori_render_stats *stats = nullptr);
+/* `--target-error E --adaptive`: nori_hip_render_adaptive_host -- passes over the tiles whose error is still above E; tileSpp: the
+   samples every 16x16 tile received (row-major tile grid) */
+std::unique_ptr<ImageBlock> renderSceneAdaptive(Scene *scene, float targetError, uint32_t passSpp, nori_adaptive_summary &summary,
+                                                std::vector<float> &errorMap, std::vector<uint32_t> &tileSpp, nori_render_stats *stats = nullptr);
 
 NORI_NAMESPACE_END

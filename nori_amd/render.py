@@ -286,6 +286,98 @@ class Renderer:
                                                        C.c_void_p(m2_tensor.data_ptr()), C.byref(done), C.byref(last), C.byref(st)), "render_to_error")
         return int(done.value), last.as_dict(), st.as_dict()
 
+    # -- tile lists, tile errors, selection, adaptive sampling (include/nori_hip.h) --
+    def tile_grid(self):
+        """(tiles_y, tiles_x) of the frame's 16x16 tiles; tile t = ty * tiles_x + tx"""
+        c = self.scene.camera
+        return ((c.height + capi.TILE_SIZE - 1) // capi.TILE_SIZE, (c.width + capi.TILE_SIZE - 1) // capi.TILE_SIZE)
+
+    @staticmethod
+    def _tile_list(tiles):
+        return np.ascontiguousarray(np.asarray(list(tiles) if not isinstance(tiles, np.ndarray) else tiles).reshape(-1), dtype=np.uint32)
+
+    def render_tiles_into(self, tiles, rgbw_tensor, m2_tensor=None, spp_count=None, spp_begin=0, count_traversal=False, stream=None,
+                          want_stats=True, time_kernels=False, seed_mode=capi.SEED_PER_SAMPLE):
+        """render_moments_into (render_into where m2_tensor is None) for exactly the listed tiles: strictly ascending raster ids."""
+        assert self._is_frame(rgbw_tensor) and (m2_tensor is None or self._is_frame(m2_tensor))
+        t = self._tile_list(tiles)
+        spp = self.scene.sample_count if spp_count is None else spp_count
+        raw = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        p = self._params(spp_begin, spp, 1, 0, count_traversal, raw, time_kernels, seed_mode)
+        st = capi.RenderStats() if want_stats else None
+        self._check(self._lib.nori_hip_render_tiles(self._h, C.byref(p), ptr(t), t.shape[0], C.c_void_p(rgbw_tensor.data_ptr()),
+                                                    C.c_void_p(m2_tensor.data_ptr()) if m2_tensor is not None else None,
+                                                    C.byref(st) if st is not None else None), "render_tiles")
+        return st.as_dict() if st is not None else None
+
+    def render_tiles_host(self, tiles, spp_count=None, spp_begin=0, count_traversal=False, seed_mode=capi.SEED_PER_SAMPLE):
+        """The listed tiles into fresh host frames; returns (rgbw, m2, stats dict)."""
+        t = self._tile_list(tiles)
+        spp = self.scene.sample_count if spp_count is None else spp_count
+        p = self._params(spp_begin, spp, 1, 0, count_traversal, None, seed_mode=seed_mode)
+        rgbw, m2 = np.zeros(self.frame_shape(), np.float32), np.zeros(self.frame_shape(), np.float32)
+        st = capi.RenderStats()
+        self._check(self._lib.nori_hip_render_tiles_host(self._h, C.byref(p), ptr(t), t.shape[0], ptr(rgbw), ptr(m2), C.byref(st)), "render_tiles_host")
+        return rgbw, m2, st.as_dict()
+
+    def tile_errors(self, rgbw, m2, stream=None):
+        """(tiles_y, tiles_x) float32: the mean of the error map over each tile's pixels inside the frame.  Torch CUDA tensors give a
+        CUDA tensor; numpy arrays are copied to the device and give a numpy array."""
+        if isinstance(rgbw, np.ndarray):
+            rgbw, m2 = (np.ascontiguousarray(a, dtype=np.float32) for a in (rgbw, m2))
+            assert rgbw.shape == m2.shape == tuple(self.frame_shape())
+            out = np.zeros(self.tile_grid(), np.float32)
+            self._check(self._lib.nori_hip_tile_errors_host(self._h, ptr(rgbw), ptr(m2), ptr(out)), "tile_errors_host")
+            return out
+        import torch
+        assert self._is_frame(rgbw) and self._is_frame(m2)
+        out = torch.empty(self.tile_grid(), dtype=torch.float32, device=rgbw.device)
+        raw = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._check(self._lib.nori_hip_tile_errors(self._h, C.c_void_p(rgbw.data_ptr()), C.c_void_p(m2.data_ptr()), C.c_void_p(out.data_ptr()), raw), "tile_errors")
+        return out
+
+    def select_tiles(self, tile_err, target, tiles):
+        """uint32 array: the tiles of `tiles` (strictly ascending) with not (tile_err[t] <= target), in order -- a NaN stays in.
+        tile_err: one float per tile of the frame, a torch CUDA tensor or a numpy array (copied to the device)."""
+        import torch
+        if isinstance(tile_err, np.ndarray):
+            tile_err = torch.from_numpy(np.ascontiguousarray(tile_err, dtype=np.float32)).to(f"cuda:{self.device}")
+        ty, tx = self.tile_grid()
+        assert tile_err.is_cuda and tile_err.is_contiguous() and tile_err.numel() == ty * tx and str(tile_err.dtype) == "torch.float32"
+        t = self._tile_list(tiles)
+        out, n = np.zeros(max(t.shape[0], 1), np.uint32), C.c_uint32(0)
+        torch.cuda.synchronize(tile_err.device)      # the call runs on the default stream
+        self._check(self._lib.nori_hip_select_tiles(self._h, C.c_void_p(tile_err.data_ptr()), float(target), ptr(t), t.shape[0], ptr(out), C.byref(n)), "select_tiles")
+        return out[:int(n.value)].copy()
+
+    def render_adaptive(self, rgbw_tensor, m2_tensor, target_tile_err, pass_spp=16, spp_count=None, spp_begin=0, stream=None,
+                        count_traversal=False, time_kernels=False):
+        """render_to_error with the samples steered by the tile errors: passes of `pass_spp` samples per pixel over the tiles whose
+        error is still above `target_tile_err`, at most `spp_count` per pixel; accumulates into both tensors.  Returns (tile_spp: a
+        (tiles_y, tiles_x) int32 CUDA tensor of the samples each tile received, summary dict, stats dict)."""
+        import torch
+        assert self._is_frame(rgbw_tensor) and self._is_frame(m2_tensor)
+        spp = self.scene.sample_count if spp_count is None else spp_count
+        raw = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        p = self._params(spp_begin, spp, 1, 0, count_traversal, raw, time_kernels)
+        tile_spp = torch.zeros(self.tile_grid(), dtype=torch.int32, device=rgbw_tensor.device)
+        out, st = capi.AdaptiveSummary(), capi.RenderStats()
+        self._check(self._lib.nori_hip_render_adaptive(self._h, C.byref(p), int(pass_spp), float(target_tile_err), C.c_void_p(rgbw_tensor.data_ptr()),
+                                                       C.c_void_p(m2_tensor.data_ptr()), C.c_void_p(tile_spp.data_ptr()), C.byref(out), C.byref(st)), "render_adaptive")
+        return tile_spp, out.as_dict(), st.as_dict()
+
+    def render_adaptive_host(self, target_tile_err, pass_spp=16, spp_count=None, spp_begin=0, count_traversal=False):
+        """The adaptive loop into fresh host frames; returns (rgbw, m2, err, tile_spp, summary dict, stats dict)."""
+        c = self.scene.camera
+        spp = self.scene.sample_count if spp_count is None else spp_count
+        p = self._params(spp_begin, spp, 1, 0, count_traversal, None)
+        rgbw, m2 = np.zeros(self.frame_shape(), np.float32), np.zeros(self.frame_shape(), np.float32)
+        err, tile_spp = np.zeros((c.height, c.width), np.float32), np.zeros(self.tile_grid(), np.uint32)
+        out, st = capi.AdaptiveSummary(), capi.RenderStats()
+        self._check(self._lib.nori_hip_render_adaptive_host(self._h, C.byref(p), int(pass_spp), float(target_tile_err), ptr(rgbw), ptr(m2), ptr(err),
+                                                            ptr(tile_spp), C.byref(out), C.byref(st)), "render_adaptive_host")
+        return rgbw, m2, err, tile_spp, out.as_dict(), st.as_dict()
+
     # -- film_order = reference shared out: rows of 32x32 blocks (include/nori_hip.h: nori_hip_render_block_rows) --
     def block_rows(self) -> int:
         """rows of 32x32 blocks (NORI_BLOCK_SIZE) in the frame"""
