@@ -432,6 +432,26 @@ int nori_hip_warp(nori_hip_ctx *ctx, int warp /* nori_warp_type */,
 int nori_hip_warp_pdf(nori_hip_ctx *ctx, int warp, float param,
                       const float *points, size_t n, float *pdf);
 
+/* The device's own arithmetic, element by element: out[k] = op(a[k], b[k]) through the functions the kernels call
+ * (rt_types.h: exact_rcp, exact_div, the shared-reciprocal quotient of f3 / float, exact_sqrt; rt_trace.h: slab_rcp;
+ * rt_math.h: det_sincosf, det_logf, det_expf), compiled with the product's flags.  They have no CPU twin that says
+ * anything about them (the CPU builds use the plain operators), so this is where tests/test_gpu_arith.py holds them
+ * against IEEE arithmetic.  b is read by the two quotients only and may be NULL otherwise.  In libnori_hip_count.so the
+ * calls count into nori_hip_debug_excursions like any other.  No scene is needed. */
+typedef enum nori_arith_op {
+    NORI_ARITH_RCP = 0,           /* exact_rcp(a) */
+    NORI_ARITH_DIV = 1,           /* exact_div(a, b) */
+    NORI_ARITH_DIV_SHARED = 2,    /* x of (f3) {a, a, a} / b: one exact_rcp_raw(b), exact_div_by per component */
+    NORI_ARITH_SQRT = 3,          /* exact_sqrt(a) */
+    NORI_ARITH_SLAB_RCP = 4,      /* slab_rcp(a) */
+    NORI_ARITH_SIN = 5,           /* det_sincosf(a): the sine */
+    NORI_ARITH_COS = 6,           /*                 the cosine */
+    NORI_ARITH_LOG = 7,           /* det_logf(a) */
+    NORI_ARITH_EXP = 8            /* det_expf(a) */
+} nori_arith_op;
+int nori_hip_debug_arith(nori_hip_ctx *ctx, int op /* nori_arith_op */,
+                         const float *a, const float *b, size_t n, float *out);
+
 /* pcg32::nextFloat stream (Independent::next1D, src/independent.cpp:46-48):
  * out[k*count + j] = j-th float of pcg32.seed(seed_state[k], seed_seq[k]). */
 int nori_hip_pcg32_floats(nori_hip_ctx *ctx, const uint64_t *seed_state,

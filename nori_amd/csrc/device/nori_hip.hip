@@ -361,6 +361,27 @@ __global__ void warp_kernel(int warp, float param, int pdf, const float *in, siz
     }
 }
 
+/* nori_hip_debug_arith: the arithmetic primitives themselves, one element per thread (b == nullptr for the unary ones) */
+__global__ void arith_kernel(int op, const float *a, const float *b, size_t n, float *out) {
+    const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float x = a[i], y = b ? b[i] : 1.0f;
+    float r = 0.0f, s, c;
+    switch (op) {
+    case NORI_ARITH_RCP: r = exact_rcp(x); break;
+    case NORI_ARITH_DIV: r = exact_div(x, y); break;
+    case NORI_ARITH_DIV_SHARED: r = (mk3(x, x, x) / y).x; break;
+    case NORI_ARITH_SQRT: r = exact_sqrt(x); break;
+    case NORI_ARITH_SLAB_RCP: r = slab_rcp(x); break;
+    case NORI_ARITH_SIN: det_sincosf(x, &s, &c); r = s; break;
+    case NORI_ARITH_COS: det_sincosf(x, &s, &c); r = c; break;
+    case NORI_ARITH_LOG: r = det_logf(x); break;
+    case NORI_ARITH_EXP: r = det_expf(x); break;
+    default: break;
+    }
+    out[i] = r;
+}
+
 __global__ void pcg32_kernel(const uint64_t *state, const uint64_t *seq, uint64_t skip, size_t n, uint32_t count, float *out) {
     const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -977,6 +998,23 @@ int nori_hip_warp_pdf(nori_hip_ctx *ctx, int warp, float param, const float *poi
     hipLaunchKernelGGL(warp_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, warp, param, 1, (const float *) din.p, n, (float *) dout.p);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpy(pdf, dout.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    return NORI_OK;
+}
+
+int nori_hip_debug_arith(nori_hip_ctx *ctx, int op, const float *a, const float *b, size_t n, float *out) {
+    if (!ctx) return NORI_ERR_INVALID_ARGUMENT;
+    const bool binary = op == NORI_ARITH_DIV || op == NORI_ARITH_DIV_SHARED;
+    if (op < NORI_ARITH_RCP || op > NORI_ARITH_EXP) { ctx->error = "debug_arith: unknown op " + std::to_string(op); return NORI_ERR_INVALID_ARGUMENT; }
+    if (n == 0) return NORI_OK;
+    if (!a || !out || (binary && !b)) { ctx->error = "debug_arith: a, out and (for the quotients) b must not be NULL"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (n > ((size_t) 1 << 31)) { ctx->error = "debug_arith: at most 2^31 elements per call"; return NORI_ERR_INVALID_ARGUMENT; }
+    DeviceGuard g(ctx->device);
+    SCRATCH_IN(ctx, da, a, n * sizeof(float));
+    SCRATCH_IN(ctx, db, binary ? b : nullptr, binary ? n * sizeof(float) : 0);
+    SCRATCH_OUT(ctx, dout, n * sizeof(float));
+    hipLaunchKernelGGL(arith_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, op, (const float *) da.p, binary ? (const float *) db.p : nullptr, n, (float *) dout.p);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpy(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost));
     return NORI_OK;
 }
 

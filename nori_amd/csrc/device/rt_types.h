@@ -51,14 +51,26 @@ NORI_HD float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
  * square root and on 2^36 pairs -- exponents of both operands within +-60, hard mantissa patterns included -- for the
  * quotient; results in profiles/r2_exact_rcp.txt and profiles/r2_exact_div_sqrt.txt), and the render path's operands
  * -- lengths, cosines, pdfs, areas of scenes whose unit is not 1e-15 of their size -- lie well inside it.  The CPU twins
- * (emulation harness, host code) use the plain operators.
+ * (emulation harness, host code) use the plain operators, so they say nothing about these sequences.  The standing
+ * evidence is tests/test_gpu_arith.py: it runs the functions below on the device (nori_hip_debug_arith) and holds them,
+ * bit pattern by bit pattern, to IEEE arithmetic done on the CPU -- whole binades of the reciprocal and the root, and
+ * 2^24 quotients over the WHOLE domain stated here, among them the hardest a quotient of floats can be (2^-24 ulp from a
+ * rounding boundary), zero numerators of both signs and the edges of the domain (operands: tests/arith_cases.py).
  *
  *   exact_rcp(x)    = 1.0f / x   for 2^-126 <= |x| < 2^126: r0 = v_rcp_f32(x) (1 ulp), one Newton step with two fma.
  *   exact_div(a, b) = a / b      y = exact_rcp(b) is the correctly rounded reciprocal, q = a y is within 2 ulp, the
  *                                residual r = a - b q is exact (fma), and RN(q + r y) is the correctly rounded quotient
  *                                (Markstein 1990).  Domain: b as for exact_rcp; a = 0, or a and a / b normal numbers with
- *                                |a| >= 2^-100 (so that r does not underflow).  Three numerators over one denominator
+ *                                |a| >= 2^-100 (so that r does not underflow) and |a / b| below the largest finite float
+ *                                (a quotient that rounds to FLT_MAX may round to infinity in q, and r is then NaN:
+ *                                0x7f7ffffe / 0x3f7fffff is one).  Three numerators over one denominator
  *                                (a vector / its length) share y: 12 instructions instead of 39.
+ *                                A ZERO NUMERATOR gives a zero of IEEE's sign with one exception: -0 / b is +0 for
+ *                                b > 0 (q = -0, the residual (+0) + (-0) is +0, and (+0) y + (-0) is +0); +0 / b and
+ *                                -0 / b with b < 0 are IEEE's -0 and +0.  This is part of the contract, not fixed:
+ *                                a select on a == 0 is two more instructions in each of the ~22 quotients of a path
+ *                                vertex, and no decision of the renderer reads the sign of such a zero (DESIGN.md
+ *                                section 5 lists where a zero quotient can go).
  *   exact_sqrt(x)   = sqrtf(x)   s = v_sqrt_f32(x) (1 ulp); the residuals x - (s -+ 1 ulp) s, exact in one fma each,
  *                                say whether a neighbour is the correctly rounded root (the compiler's own correction
  *                                step without its scaling).  Domain: x = 0, +inf, or x >= 2^-104 (below that the residuals
@@ -71,7 +83,8 @@ NORI_HD float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
  * a triangle's 1 / det is only used after |det| >= 1e-8 was checked).
  * Builds with -DNORI_COUNT_EXCURSIONS (libnori_hip_count.so) count every operand of the shading code outside the verified
  * domains; the GPU suite renders the golden scenes through that build and asserts zeros
- * (test_shading_arithmetic_stays_inside_its_verified_domain). */
+ * (test_shading_arithmetic_stays_inside_its_verified_domain), and shows that the counters count
+ * (tests/test_gpu_arith.py::test_the_excursion_counters_count: a known number of operands outside each domain). */
 #if defined(NORI_COUNT_EXCURSIONS) && defined(__HIP__)
 static __device__ unsigned long long g_nori_excursions[4];      /* rcp, div, sqrt operands outside the domain; results that are NaN or infinite (per translation unit) */
 #endif
@@ -102,7 +115,7 @@ NORI_HD float exact_rcp(float x) {
 NORI_HD float exact_div_by(float a, float b, float rcp_b) {      /* rcp_b = exact_rcp_raw(b) or exact_rcp(b) */
 #if defined(__HIP_DEVICE_COMPILE__)
     NORI_EXCURSION(1, !(fabsf(b) >= 1.17549435e-38f && fabsf(b) < 8.5070592e37f) ||
-                      (a != 0.0f && !(fabsf(a) >= 7.8886091e-31f && fabsf(a * rcp_b) >= 1.17549435e-38f && fabsf(a * rcp_b) < kInf)));
+                      (a != 0.0f && !(fabsf(a) >= 7.8886091e-31f && fabsf(a * rcp_b) >= 1.17549435e-38f && fabsf(a * rcp_b) < 3.4028235e38f)));      /* the quotient is judged from its estimate, 2 ulp at most from a / b */
     const float q = a * rcp_b;
     const float r = __builtin_fmaf(__builtin_fmaf(-b, q, a), rcp_b, q);
     NORI_EXCURSION(3, !(fabsf(r) < kInf));

@@ -174,6 +174,22 @@ class Renderer:
         self._check(self._lib.nori_hip_warp_pdf(self._h, capi.WARP_NAMES[name], float(param), ptr(p), p.shape[0], ptr(out)), "warp_pdf")
         return out
 
+    def arith(self, op_name: str, a, b=None) -> np.ndarray:
+        """float32 array of a's shape: the device's own `op_name` (capi.ARITH_OP_NAMES: rcp, div, div_shared, sqrt, slab_rcp, sin,
+        cos, log, exp) of every element of a -- and of b for the two quotients -- through the functions the kernels call
+        (include/nori_hip.h: nori_hip_debug_arith)."""
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        binary = op_name in ("div", "div_shared")
+        if binary != (b is not None):
+            raise ValueError(f"arith({op_name}): takes {'two operands' if binary else 'one operand'}")
+        if binary:
+            b = np.ascontiguousarray(b, dtype=np.float32)
+            if b.shape != a.shape:
+                raise ValueError(f"arith({op_name}): operands of shapes {a.shape} and {b.shape}")
+        out = np.zeros_like(a)
+        self._check(self._lib.nori_hip_debug_arith(self._h, capi.ARITH_OP_NAMES[op_name], ptr(a), ptr(b), a.size, ptr(out)), f"debug_arith({op_name})")
+        return out
+
     def pcg32_floats(self, seed_state, seed_seq, count: int):
         ss = np.ascontiguousarray(seed_state, dtype=np.uint64)
         sq = np.ascontiguousarray(seed_seq, dtype=np.uint64)
