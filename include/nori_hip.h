@@ -452,6 +452,29 @@ typedef enum nori_arith_op {
 int nori_hip_debug_arith(nori_hip_ctx *ctx, int op /* nori_arith_op */,
                          const float *a, const float *b, size_t n, float *out);
 
+/* The emitter pick itself: for n samples (xiE, xiT, xi1, xi2) -- samples[4 k ..] -- the mesh index of the emitter that
+ * emitter_pick (rt_path.h) selects, the triangle within that mesh and the point p[3 k ..] that emitter_point places on it:
+ * the functions sample_direct calls, 256 threads per workgroup, one sample per thread.  `reader` names how the kernel reads
+ * the scene's small tables (mesh records, emitter list, triangle CDFs), one for each way the render kernels do
+ * (shade_tables.h).  NORI_TABLES_LDS returns NORI_ERR_UNSUPPORTED for a scene whose tables do not fit the LDS copy (more
+ * than 32 meshes or 960 CDF entries): wf_shade reads those from global memory.  An unknown reader or a scene without
+ * emitters is NORI_ERR_INVALID_ARGUMENT.  Samples are expected in [0, 1], ends included.  Needs a scene, no tree. */
+typedef enum nori_tables_reader {
+    NORI_TABLES_GLOBAL = 0,       /* SceneTables through DevScene's pointers: li_kernel, wf_shade of a scene that does not fit */
+    NORI_TABLES_REDIRECTED = 1,   /* shade_tables_to_lds, then SceneTables on the redirected pointers: render_kernel, wf_finish
+                                     (global memory when the tables do not fit) */
+    NORI_TABLES_LDS = 2           /* shade_tables_copy + LdsTables: wf_shade of a scene that fits */
+} nori_tables_reader;
+int nori_hip_debug_emitter_sample(nori_hip_ctx *ctx, int reader /* nori_tables_reader */, const float *samples, size_t n,
+                                  uint32_t *mesh, uint32_t *tri, float *p);
+
+/* The tables those samples are drawn from, read back from device memory: counts = {n_meshes, n_emitters, n_cdf}; then,
+ * where the pointer is not NULL, the emitter list (n_emitters mesh indices), per mesh its cdf_offset, n_triangles and
+ * inv_area (n_meshes each; cdf_offset and inv_area mean something for emitters only) and the CDF entries (n_cdf floats: per
+ * emitter n_triangles + 1, from 0 to 1).  Call it with NULL arrays first to size them. */
+int nori_hip_debug_emitter_tables(nori_hip_ctx *ctx, uint32_t counts[3], uint32_t *emitters, uint32_t *cdf_offset,
+                                  uint32_t *n_triangles, float *inv_area, float *cdf);
+
 /* pcg32::nextFloat stream (Independent::next1D, src/independent.cpp:46-48):
  * out[k*count + j] = j-th float of pcg32.seed(seed_state[k], seed_seq[k]). */
 int nori_hip_pcg32_floats(nori_hip_ctx *ctx, const uint64_t *seed_state,

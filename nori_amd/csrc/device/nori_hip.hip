@@ -382,6 +382,41 @@ __global__ void arith_kernel(int op, const float *a, const float *b, size_t n, f
     out[i] = r;
 }
 
+/* nori_hip_debug_emitter_sample: emitter_pick + emitter_point for one sample (xiE, xiT, xi1, xi2) per thread, the tables read the
+   way READER says -- 0: SceneTables on global memory (li_kernel); 1: shade_tables_to_lds, then SceneTables on the redirected
+   DevScene (render_kernel, wf_finish; global memory when the tables do not fit); 2: shade_tables_copy + LdsTables (wf_shade's
+   LDS policy; the host refuses it when shade_tables_fit is false).  Every thread reaches the copies' barrier; only stores are
+   conditional on i < n. */
+constexpr int kEmitterSampleBlock = 256;
+template <int READER>
+__global__ __launch_bounds__(kEmitterSampleBlock) void emitter_sample_kernel(DevScene sc, const float *xi, size_t n, uint32_t *mesh,
+                                                                             uint32_t *tri, float *p) {
+    __shared__ uint4 s_tab[kShadeTabWords / 4];
+    const size_t i = (size_t) blockIdx.x * kEmitterSampleBlock + threadIdx.x;
+    const bool live = i < n;
+    const float xiE = live ? xi[4 * i] : 0.0f, xiT = live ? xi[4 * i + 1] : 0.0f;
+    const f2 u = live ? mk2(xi[4 * i + 2], xi[4 * i + 3]) : mk2(0.0f, 0.0f);
+    const uint32_t nE = sc.n_emitters;
+    const f4 *shade_tris = sc.shade_tris;
+    MeshRec m; uint32_t t, mi;
+    if (READER == 2) {
+        const LdsTables tab = shade_tables_copy(sc, s_tab);
+        mi = emitter_pick(tab, nE, xiE, xiT, m, t);
+    } else {
+        if (READER == 1) shade_tables_to_lds(sc, s_tab);
+        SceneTables tab; tab.sc = &sc;
+        mi = emitter_pick(tab, nE, xiE, xiT, m, t);
+    }
+    const f4 *rec = shade_tris + (size_t) (m.tri_offset + t) * kShadeQuads;
+    const bool hn = (m.flags & kMeshHasNormals) != 0u;
+    const f3 z = mk3(0.0f);
+    f3 q, nq;
+    emitter_point(u, xyz(rec[0]), xyz(rec[1]), xyz(rec[2]), hn, hn ? xyz(rec[3]) : z, hn ? xyz(rec[4]) : z, hn ? xyz(rec[5]) : z, q, nq);
+    if (!live) return;
+    mesh[i] = mi; tri[i] = t;
+    p[3 * i] = q.x; p[3 * i + 1] = q.y; p[3 * i + 2] = q.z;
+}
+
 __global__ void pcg32_kernel(const uint64_t *state, const uint64_t *seq, uint64_t skip, size_t n, uint32_t count, float *out) {
     const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -1015,6 +1050,57 @@ int nori_hip_debug_arith(nori_hip_ctx *ctx, int op, const float *a, const float 
     hipLaunchKernelGGL(arith_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, op, (const float *) da.p, binary ? (const float *) db.p : nullptr, n, (float *) dout.p);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpy(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    return NORI_OK;
+}
+
+int nori_hip_debug_emitter_sample(nori_hip_ctx *ctx, int reader, const float *samples, size_t n, uint32_t *mesh, uint32_t *tri, float *p) {
+    if (!ctx) return NORI_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_scene) { ctx->error = "debug_emitter_sample: no scene"; return NORI_ERR_NOT_READY; }
+    if (reader < NORI_TABLES_GLOBAL || reader > NORI_TABLES_LDS) { ctx->error = "debug_emitter_sample: unknown reader " + std::to_string(reader); return NORI_ERR_INVALID_ARGUMENT; }
+    if (ctx->dev.n_emitters == 0) { ctx->error = "debug_emitter_sample: the scene has no emitters"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (reader == NORI_TABLES_LDS && !shade_tables_fit(ctx->dev)) {
+        ctx->error = "debug_emitter_sample: the scene's tables do not fit the LDS copy (shade_tables.h); wf_shade reads them from global memory";
+        return NORI_ERR_UNSUPPORTED;
+    }
+    if (n == 0) return NORI_OK;
+    if (!samples || !mesh || !tri || !p) { ctx->error = "debug_emitter_sample: samples, mesh, tri and p must not be NULL"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (n > ((size_t) 1 << 28)) { ctx->error = "debug_emitter_sample: at most 2^28 samples per call"; return NORI_ERR_INVALID_ARGUMENT; }
+    DeviceGuard g(ctx->device);
+    SCRATCH_IN(ctx, dx, samples, n * 4 * sizeof(float));
+    SCRATCH_OUT(ctx, dm, n * sizeof(uint32_t));
+    SCRATCH_OUT(ctx, dt, n * sizeof(uint32_t));
+    SCRATCH_OUT(ctx, dp, n * 3 * sizeof(float));
+    const dim3 grid((unsigned) ((n + kEmitterSampleBlock - 1) / kEmitterSampleBlock)), block(kEmitterSampleBlock);
+    switch (reader) {
+    case NORI_TABLES_GLOBAL: hipLaunchKernelGGL((emitter_sample_kernel<0>), grid, block, 0, 0, ctx->dev, (const float *) dx.p, n, (uint32_t *) dm.p, (uint32_t *) dt.p, (float *) dp.p); break;
+    case NORI_TABLES_REDIRECTED: hipLaunchKernelGGL((emitter_sample_kernel<1>), grid, block, 0, 0, ctx->dev, (const float *) dx.p, n, (uint32_t *) dm.p, (uint32_t *) dt.p, (float *) dp.p); break;
+    default: hipLaunchKernelGGL((emitter_sample_kernel<2>), grid, block, 0, 0, ctx->dev, (const float *) dx.p, n, (uint32_t *) dm.p, (uint32_t *) dt.p, (float *) dp.p); break;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpy(mesh, dm.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(tri, dt.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(p, dp.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return NORI_OK;
+}
+
+int nori_hip_debug_emitter_tables(nori_hip_ctx *ctx, uint32_t counts[3], uint32_t *emitters, uint32_t *cdf_offset, uint32_t *n_triangles,
+                                  float *inv_area, float *cdf) {
+    if (!ctx || !counts) return NORI_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_scene) { ctx->error = "debug_emitter_tables: no scene"; return NORI_ERR_NOT_READY; }
+    const DevScene &d = ctx->dev;
+    counts[0] = d.n_meshes; counts[1] = d.n_emitters; counts[2] = d.n_cdf;
+    DeviceGuard g(ctx->device);
+    if (emitters && d.n_emitters) HIP_TRY(ctx, hipMemcpy(emitters, d.emitters, d.n_emitters * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (cdf && d.n_cdf) HIP_TRY(ctx, hipMemcpy(cdf, d.emitter_cdf, d.n_cdf * sizeof(float), hipMemcpyDeviceToHost));
+    if ((cdf_offset || n_triangles || inv_area) && d.n_meshes) {
+        std::vector<MeshRec> recs(d.n_meshes);
+        HIP_TRY(ctx, hipMemcpy(recs.data(), d.meshes, d.n_meshes * sizeof(MeshRec), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < d.n_meshes; ++i) {
+            if (cdf_offset) cdf_offset[i] = recs[i].cdf_offset;
+            if (n_triangles) n_triangles[i] = recs[i].n_triangles;
+            if (inv_area) inv_area[i] = recs[i].inv_area;
+        }
+    }
     return NORI_OK;
 }
 

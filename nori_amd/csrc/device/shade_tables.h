@@ -15,7 +15,9 @@
 
 namespace nrt {
 
-/* capacities in 32-bit words: 32 mesh records, 64 emitters, 960 CDF entries (6 KB) */
+/* capacities in 32-bit words: 32 mesh records, 64 emitters, 960 CDF entries (6 KB).  The emitter capacity can never be the
+   binding limit: an emitter is a mesh, so there are no more emitters than meshes, and the mesh limit is 32 -- the fit test
+   decides on the mesh records and the CDF entries (tests/light_cases.py sits on both: 32 / 33 meshes, 960 / 961 entries). */
 constexpr uint32_t kShadeMeshWords = 32u * (uint32_t) (sizeof(MeshRec) / 4), kShadeEmitterWords = 64u, kShadeCdfWords = 960u;
 constexpr uint32_t kShadeTabWords = kShadeMeshWords + kShadeEmitterWords + kShadeCdfWords;
 

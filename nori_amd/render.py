@@ -190,6 +190,29 @@ class Renderer:
         self._check(self._lib.nori_hip_debug_arith(self._h, capi.ARITH_OP_NAMES[op_name], ptr(a), ptr(b), a.size, ptr(out)), f"debug_arith({op_name})")
         return out
 
+    def emitter_sample(self, samples, reader="global"):
+        """(mesh uint32 [n], tri uint32 [n], p float32 [n, 3]): the emitter's mesh, the triangle within it and the point on it that the
+        device's emitter_pick / emitter_point select for each sample (xiE, xiT, xi1, xi2) of `samples` [n, 4], the tables read as
+        `reader` says (capi.TABLES_READER_NAMES or its number; include/nori_hip.h: nori_hip_debug_emitter_sample)."""
+        x = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1, 4)
+        n = x.shape[0]
+        mesh, tri, p = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros((n, 3), np.float32)
+        rd = capi.TABLES_READER_NAMES[reader] if isinstance(reader, str) else int(reader)
+        self._check(self._lib.nori_hip_debug_emitter_sample(self._h, rd, ptr(x), n, ptr(mesh), ptr(tri), ptr(p)), f"debug_emitter_sample({reader})")
+        return mesh, tri, p
+
+    def emitter_tables(self) -> dict:
+        """The scene's emitter tables as they are in device memory (include/nori_hip.h: nori_hip_debug_emitter_tables): n_meshes,
+        n_emitters, n_cdf, emitters [n_emitters], cdf_offset / n_triangles / inv_area [n_meshes], cdf [n_cdf]."""
+        counts = np.zeros(3, np.uint32)
+        self._check(self._lib.nori_hip_debug_emitter_tables(self._h, ptr(counts), None, None, None, None, None), "debug_emitter_tables")
+        nm, ne, nc = (int(c) for c in counts)
+        em, off, nt = np.zeros(max(ne, 1), np.uint32), np.zeros(max(nm, 1), np.uint32), np.zeros(max(nm, 1), np.uint32)
+        inv, cdf = np.zeros(max(nm, 1), np.float32), np.zeros(max(nc, 1), np.float32)
+        self._check(self._lib.nori_hip_debug_emitter_tables(self._h, ptr(counts), ptr(em), ptr(off), ptr(nt), ptr(inv), ptr(cdf)), "debug_emitter_tables")
+        return {"n_meshes": nm, "n_emitters": ne, "n_cdf": nc, "emitters": em[:ne], "cdf_offset": off[:nm], "n_triangles": nt[:nm],
+                "inv_area": inv[:nm], "cdf": cdf[:nc]}
+
     def pcg32_floats(self, seed_state, seed_seq, count: int):
         ss = np.ascontiguousarray(seed_state, dtype=np.uint64)
         sq = np.ascontiguousarray(seed_seq, dtype=np.uint64)

@@ -114,6 +114,8 @@ def emu_lib():
             "emu_sample_rays": (C.c_int, [_P, _P, C.c_size_t, _P]),
             "emu_li": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P]),
             "emu_li_records": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P]),
+            "emu_emitter_sample": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P]),
+            "emu_emitter_tables": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
             "emu_bsdf_sample": (C.c_int, [C.POINTER(capi.BsdfDesc), _P, _P, C.c_size_t, _P, _P, _P, _P]),
             "emu_bsdf_eval": (C.c_int, [C.POINTER(capi.BsdfDesc), _P, _P, C.c_size_t, _P]),
             "emu_bsdf_pdf": (C.c_int, [C.POINTER(capi.BsdfDesc), _P, _P, C.c_size_t, _P]),
@@ -357,6 +359,25 @@ class Emu(_CpuBackend):
         counts = np.zeros(2, np.uint64)
         bad = self.lib.emu_nodeq_check(self._h, ptr(rays), rays.shape[0], ptr(counts))
         return None if bad < 0 else (int(bad), int(counts[0]), int(counts[1]))
+
+    def emitter_sample(self, samples):
+        """Renderer.emitter_sample on the CPU: (mesh, tri, p) of emitter_pick / emitter_point per sample (xiE, xiT, xi1, xi2)."""
+        x = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1, 4)
+        n = x.shape[0]
+        mesh, tri, p = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros((n, 3), np.float32)
+        assert self.lib.emu_emitter_sample(self._h, ptr(x), n, ptr(mesh), ptr(tri), ptr(p)) == 0
+        return mesh, tri, p
+
+    def emitter_tables(self):
+        """Renderer.emitter_tables of the tables scene_prep.cpp made on the host (the device holds a copy of them)."""
+        counts = np.zeros(3, np.uint32)
+        assert self.lib.emu_emitter_tables(self._h, ptr(counts), None, None, None, None, None) == 0
+        nm, ne, nc = (int(c) for c in counts)
+        em, off, nt = np.zeros(max(ne, 1), np.uint32), np.zeros(max(nm, 1), np.uint32), np.zeros(max(nm, 1), np.uint32)
+        inv, cdf = np.zeros(max(nm, 1), np.float32), np.zeros(max(nc, 1), np.float32)
+        assert self.lib.emu_emitter_tables(self._h, ptr(counts), ptr(em), ptr(off), ptr(nt), ptr(inv), ptr(cdf)) == 0
+        return {"n_meshes": nm, "n_emitters": ne, "n_cdf": nc, "emitters": em[:ne], "cdf_offset": off[:nm], "n_triangles": nt[:nm],
+                "inv_area": inv[:nm], "cdf": cdf[:nc]}
 
     def render_host(self, spp_count=None, spp_begin=0, tile_mod=1, tile_rem=0, count_traversal=False):
         p = self._params(spp_count, spp_begin, tile_mod, tile_rem, count_traversal)

@@ -487,6 +487,41 @@ int emu_li(emu_ctx *c, const nori_ray *rays, size_t n, const uint64_t *ss, const
     return NORI_OK;
 }
 
+/* emitter_pick + emitter_point (rt_path.h) per sample (xiE, xiT, xi1, xi2), through SceneTables: what
+   nori_hip_debug_emitter_sample runs on the device */
+int emu_emitter_sample(emu_ctx *c, const float *xi, size_t n, uint32_t *mesh, uint32_t *tri, float *p) {
+    const DevScene &sc = c->dev;
+    if (sc.n_emitters == 0) return NORI_ERR_INVALID_ARGUMENT;
+    SceneTables tab; tab.sc = &sc;
+    for (size_t i = 0; i < n; ++i) {
+        MeshRec m; uint32_t t;
+        mesh[i] = emitter_pick(tab, sc.n_emitters, xi[4 * i], xi[4 * i + 1], m, t);
+        tri[i] = t;
+        const f4 *rec = sc.shade_tris + (size_t) (m.tri_offset + t) * kShadeQuads;
+        const bool hn = (m.flags & kMeshHasNormals) != 0u;
+        const f3 z = mk3(0.0f);
+        f3 q, nq;
+        emitter_point(mk2(xi[4 * i + 2], xi[4 * i + 3]), xyz(rec[0]), xyz(rec[1]), xyz(rec[2]), hn, hn ? xyz(rec[3]) : z, hn ? xyz(rec[4]) : z,
+                      hn ? xyz(rec[5]) : z, q, nq);
+        p[3 * i] = q.x; p[3 * i + 1] = q.y; p[3 * i + 2] = q.z;
+    }
+    return NORI_OK;
+}
+
+/* the tables prepare_scene made (nori_hip_debug_emitter_tables reads the device's copy of the same) */
+int emu_emitter_tables(emu_ctx *c, uint32_t counts[3], uint32_t *emitters, uint32_t *cdf_offset, uint32_t *n_triangles, float *inv_area, float *cdf) {
+    const HostScene &h = c->host;
+    counts[0] = (uint32_t) h.meshes.size(); counts[1] = (uint32_t) h.emitters.size(); counts[2] = (uint32_t) h.emitter_cdf.size();
+    if (emitters) std::copy(h.emitters.begin(), h.emitters.end(), emitters);
+    if (cdf) std::copy(h.emitter_cdf.begin(), h.emitter_cdf.end(), cdf);
+    for (size_t i = 0; i < h.meshes.size(); ++i) {
+        if (cdf_offset) cdf_offset[i] = h.meshes[i].cdf_offset;
+        if (n_triangles) n_triangles[i] = h.meshes[i].n_triangles;
+        if (inv_area) inv_area[i] = h.meshes[i].inv_area;
+    }
+    return NORI_OK;
+}
+
 int emu_li_records(emu_ctx *c, const nori_ray *rays, size_t n, const uint64_t *ss, const uint64_t *sq, float *rgb) {
     const DevScene &sc = c->dev;
     ArrayStack stack; TraversalCounters tc; tc.nodes = tc.tris = 0;
