@@ -295,7 +295,8 @@ typedef struct nori_render_stats {
     float trace_ms, shade_ms, film_ms;
     uint32_t n_trace_launches;
     uint32_t engine;         /* what rendered this call: 0 = megakernel (render_kernel), 1 = wavefront (wf_extend / wf_shade),
-                                2 = the block-serial kernel of NORI_SEED_NORI_BLOCK.  The option "engine" is a request: "auto"
+                                2 = the block-serial kernel of NORI_SEED_NORI_BLOCK, 3 = the first-hit feature pass
+                                (nori_hip_render_features: feature_pass_kernel).  The option "engine" is a request: "auto"
                                 picks by job size, and trees with wide nodes are walked by the wavefront engine only */
     uint32_t trace_cus;      /* CUs the ray-query kernels ran on: all of the device's, or -- wavefront engine, big jobs -- all but
                                 the CUs set aside for the shading and film kernels, which then run BESIDE the ray queries of
@@ -645,6 +646,53 @@ int nori_hip_render_adaptive(nori_hip_ctx *ctx, const nori_render_params *params
 int nori_hip_render_adaptive_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_tile_err,
                                   float *rgbw, float *m2, float *err, uint32_t *tile_spp,
                                   nori_adaptive_summary *out, nori_render_stats *stats);
+
+/* ------------------------------------------- first-hit feature frames: albedo, shading normal, depth
+ *
+ * No counterpart in the reference.  What a denoiser is guided by: per camera sample the albedo, the shading normal and the
+ * distance of the FIRST surface the sample's camera ray meets, filtered into frames laid out like the beauty frame.  A pass of
+ * its own (features.h): one closest-hit ray per camera sample, no path; the kernels of nori_hip_render are not involved and
+ * render the same bits before and after a call.
+ *
+ * The camera sample (px, py, s) is the one nori_hip_render draws (NORI_SEED_PER_SAMPLE), in float32 without FMA contraction:
+ *   pcg32.seed(py * width + px, s);  j = (nextFloat, nextFloat);  pixelSample = (px + j.x, py + j.y)
+ *   a second pair of floats is drawn for the aperture and not used (src/perspective.cpp:78)
+ *   ray = PerspectiveCamera::sampleRay(pixelSample)                      (src/perspective.cpp:76-97; nori_hip_sample_rays)
+ *   its = the closest hit of ray in [mint, maxt]                         (Accel::rayIntersect; nori_hip_intersect)
+ * and the sample's three values are
+ *   albedo  miss: (0, 0, 0).  Hit on mesh m: NORI_BSDF_MIRROR and NORI_BSDF_DIELECTRIC give (1, 1, 1); NORI_BSDF_DIFFUSE and
+ *           NORI_BSDF_MICROFACET give bsdf.albedo (the microfacet's kd), a textured mesh (albedo_texture != 0) the texture
+ *           lookup stated under nori_texture_desc at its.uv instead -- the value the shading multiplies with.  An emitter is a
+ *           mesh like any other: the albedo of its BSDF, not its radiance.
+ *   normal  ENCODED: e_c = 0.5f * n_c + 0.5f per component (one multiply, exact; one add, rounded) of the shading normal
+ *           n = its.shFrame.n (nori_intersection::sh_n).  Miss: (0.5, 0.5, 0.5).  Encoded because the film's isValid() guard
+ *           (src/block.cpp:63-67) gives weight 0 to a sample with a negative component: a signed normal would be dropped.
+ *   depth   hit: (t, float32(t * t), 1) with t = nori_intersection::t; miss: (0, 0, 0).  The third channel is coverage, the
+ *           second lets a consumer form the variance of the distance.
+ * No other special cases: a value the guard rejects (not finite, negative) is dropped like any radiance and counted in n_invalid.
+ *
+ * Each requested feature's samples are ADDED into that feature's frame, a DEVICE buffer with the RGBW layout and size of
+ * nori_hip_render's, by the fast film (film_order is not consulted: a feature frame has no reference order): (value w, w) per
+ * tap of weight w, so the W channel of every feature frame has the bits of the W channel nori_hip_render's megakernel engine
+ * gives with the same parameters (while no sample is rejected).  spp_begin, spp_count, tile_mod, tile_rem, stream and
+ * time_kernels mean what they mean to nori_hip_render; frames of disjoint shares add like RGBW frames.  count_traversal is
+ * ignored (n_node_tests = n_tri_tests = 0).  Asynchronous on params->stream unless `stats` is non-NULL.
+ * features: a mask of nori_feature; the frame of a feature that is not requested is not touched and may be NULL.
+ * Decode, per pixel, each quotient 0 where its divisor is <= 0:
+ *   albedo = rgb / W
+ *   normal = 2 * rgb / W - 1            (a filtered mean of unit vectors: NOT renormalised; normalise if unit length is wanted)
+ *   depth:  coverage c = B / W;  mean distance over the hits = R / B;  mean squared distance over the hits = G / B
+ * Errors: NORI_ERR_INVALID_ARGUMENT for features == 0, unknown bits or a requested frame that is NULL; NORI_ERR_UNSUPPORTED
+ * (with a message) for NORI_SEED_NORI_BLOCK and for a filter border above 8; NORI_ERR_NOT_READY without an acceleration
+ * structure.  Stats: n_camera_samples; n_closest_rays (one per camera sample inside the frame); n_shadow_rays = 0; n_invalid
+ * summed over the gathers that ran (one per requested feature); kernel_ms, trace_ms (the pass), film_ms as for the
+ * megakernel; engine = 3.  Limits: whole frames or tile_mod shares on one context -- no tile lists, no device groups.
+ * nori_hip_render_features_host: the requested frames to zeroed HOST buffers, as nori_hip_render_host. */
+typedef enum nori_feature { NORI_FEATURE_ALBEDO = 1, NORI_FEATURE_NORMAL = 2, NORI_FEATURE_DEPTH = 4 } nori_feature;
+int nori_hip_render_features(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t features,
+                             void *d_albedo, void *d_normal, void *d_depth, nori_render_stats *stats /* may be NULL */);
+int nori_hip_render_features_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t features,
+                                  float *albedo, float *normal, float *depth, nori_render_stats *stats /* may be NULL */);
 
 /* film_order = "reference" shared out over devices or ranks.  The reference adds a 32x32 block's samples consecutively
  * into the block's own ImageBlock (renderBlock, src/main.cpp:27-55) and the blocks into the frame in BlockGenerator's order

@@ -30,6 +30,7 @@ SEED_PER_SAMPLE, SEED_NORI_BLOCK = 0, 1
 MEASURE_UNKNOWN, MEASURE_SOLID_ANGLE, MEASURE_DISCRETE = 0, 1, 2
 NO_HIT = 0xFFFFFFFF
 TILE_SIZE = 16
+FEATURE_BITS = {"albedo": 1, "normal": 2, "depth": 4}      # nori_feature
 
 STATUS = {0: "NORI_OK", -1: "NORI_ERR_INVALID_ARGUMENT", -2: "NORI_ERR_NO_DEVICE",
           -3: "NORI_ERR_OUT_OF_MEMORY", -4: "NORI_ERR_NOT_READY",
@@ -179,6 +180,8 @@ HIP_PROTOTYPES = {
     "nori_hip_render_host": (C.c_int, [_P, C.POINTER(RenderParams), _P, C.POINTER(RenderStats)]),
     "nori_hip_render_moments": (C.c_int, [_P, C.POINTER(RenderParams), _P, _P, C.POINTER(RenderStats)]),
     "nori_hip_render_moments_host": (C.c_int, [_P, C.POINTER(RenderParams), _P, _P, C.POINTER(RenderStats)]),
+    "nori_hip_render_features": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, _P, _P, _P, C.POINTER(RenderStats)]),
+    "nori_hip_render_features_host": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, _P, _P, _P, C.POINTER(RenderStats)]),
     "nori_hip_error_map": (C.c_int, [_P, _P, _P, _P, C.c_float, C.POINTER(ErrorSummary), _P]),
     "nori_hip_error_map_host": (C.c_int, [_P, _P, _P, _P, C.c_float, C.POINTER(ErrorSummary)]),
     "nori_hip_render_to_error": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_float, _P, _P, C.POINTER(C.c_uint32),

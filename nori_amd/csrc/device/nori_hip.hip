@@ -36,6 +36,7 @@
 #include "../../../include/nori_hip.h"
 #include "film.h"
 #include "film_tiles.h"
+#include "features.h"
 #include "ktimer.h"
 #include "shade_tables.h"
 #include "rt_path.h"
@@ -495,6 +496,7 @@ struct nori_hip_ctx {
     FilmStore film;
     FilmMoments moments;      /* renders that keep second moments, nori_hip_error_map: a second set of tile accumulators, partial sums */
     FilmTiles tiles;          /* renders by tile list, tile selection, the adaptive loop: lists, inverse table, tile errors (film_tiles.h) */
+    FeatureStore features;    /* nori_hip_render_features: a sample plane and a set of tile accumulators per feature (features.h) */
 };
 
 static std::string g_create_error;
@@ -601,6 +603,7 @@ void nori_hip_destroy(nori_hip_ctx *ctx) {
     film_release(ctx->film);
     film_moments_release(ctx->moments);
     film_tiles_release(ctx->tiles);
+    feature_store_release(ctx->features);
     if (ctx->d_stats) (void) hipFree(ctx->d_stats);
     delete ctx;
 }
@@ -1767,6 +1770,125 @@ int nori_hip_render_adaptive_host(nori_hip_ctx *ctx, const nori_render_params *p
     HIP_TRY(ctx, hipMemcpy(rgbw, d_rgbw, fb, hipMemcpyDeviceToHost));
     if (m2) HIP_TRY(ctx, hipMemcpy(m2, d_m2, fb, hipMemcpyDeviceToHost));
     if (tile_spp) HIP_TRY(ctx, hipMemcpy(tile_spp, d_spp, tb, hipMemcpyDeviceToHost));
+    return NORI_OK;
+}
+
+/* ---- first-hit feature frames (features.h): one trace for all requested features, then the film once per feature ---- */
+
+int nori_hip_render_features(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t features,
+                             void *d_albedo, void *d_normal, void *d_depth, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params) return NORI_ERR_INVALID_ARGUMENT;
+    void *d_frame[kFeatureCount] = {d_albedo, d_normal, d_depth};
+    if (features == 0u || (features & ~kFeatureAll)) { ctx->error = "render_features: the mask must name at least one of NORI_FEATURE_ALBEDO | NORMAL | DEPTH and nothing else"; return NORI_ERR_INVALID_ARGUMENT; }
+    for (int f = 0; f < kFeatureCount; ++f)
+        if ((features & (1u << f)) && !d_frame[f]) { ctx->error = "render_features: a requested feature has no frame"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (params->tile_mod == 0 || params->tile_rem >= params->tile_mod) { ctx->error = "render: bad tile_mod/tile_rem"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (params->seed_mode != NORI_SEED_PER_SAMPLE && params->seed_mode != NORI_SEED_NORI_BLOCK) { ctx->error = "render: unknown seed_mode"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (params->seed_mode == NORI_SEED_NORI_BLOCK) {
+        ctx->error = "render_features: NORI_SEED_PER_SAMPLE only (a block's serial stream depends on the paths the beauty render traced: its camera samples cannot be drawn again without them)";
+        return NORI_ERR_UNSUPPORTED;
+    }
+    if (ctx->host.filter.border > 8) { ctx->error = "render: reconstruction filter radius too large for the LDS tile"; return NORI_ERR_UNSUPPORTED; }
+    DeviceGuard g(ctx->device);
+    hipStream_t s = (hipStream_t) params->stream;
+
+    RenderArgs a;      /* the tile / chunk geometry of the megakernel path (plan_chunks) */
+    a.spp_begin = params->spp_begin; a.spp_count = params->spp_count;
+    a.tile_mod = params->tile_mod; a.tile_rem = params->tile_rem;
+    a.tiles_x = (uint32_t) ((ctx->host.camera.width + kTile - 1) / kTile);
+    a.tiles_y = (uint32_t) ((ctx->host.camera.height + kTile - 1) / kTile);
+    const uint32_t n_tiles = a.tiles_x * a.tiles_y;
+    a.n_sel_tiles = n_tiles > a.tile_rem ? (n_tiles - a.tile_rem + a.tile_mod - 1) / a.tile_mod : 0;
+    a.tile_w = kTile + 2 * ctx->host.filter.border;
+    a.debug_flags = 0u; a.th_shade = a.th_inner = a.th_leaf = 1u;
+    plan_chunks(a);
+    const uint32_t need = ctx->bvh.max_depth + 1;
+    unsigned long long n_invalid = 0; uint32_t n_workgroups = 0;
+
+    struct EventPair {      /* destroyed on every return path */
+        hipEvent_t a = nullptr, b = nullptr;
+        ~EventPair() { if (a) (void) hipEventDestroy(a); if (b) (void) hipEventDestroy(b); }
+    } evp;
+    if (stats) {
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_stats, 0, 16 * sizeof(unsigned long long), s));
+        HIP_TRY(ctx, hipEventCreate(&evp.a)); HIP_TRY(ctx, hipEventCreate(&evp.b));
+        HIP_TRY(ctx, hipEventRecord(evp.a, s));
+    }
+    KernelTimer timer(stats && params->time_kernels != 0);
+    if (a.n_sel_tiles > 0 && a.spp_count > 0) {
+        /* as the megakernel path of render_impl: a call that produces more samples than the store budget is cut into launches
+           over sample sub-ranges, each followed by its gathers; the accumulators are carried from launch to launch */
+        size_t cap = (size_t) 1 << 29;
+        if (const char *e = getenv("NORI_HIP_FILM_SAMPLES")) cap = (size_t) std::max(256ll, atoll(e));
+        const uint32_t spp_per_launch = (uint32_t) std::max<size_t>(1, std::min<size_t>(a.spp_count, cap / ((size_t) a.n_sel_tiles * 256)));
+        const size_t n_samples = (size_t) a.n_sel_tiles * 256 * spp_per_launch;
+        FilmStore film;      /* pos, n_parts and the invalid counter are the film's own; always the fast film (no reference order of a feature frame exists) */
+        std::string ferr = film_prepare(ctx->film, n_samples, a.n_sel_tiles, a.tile_w, s, film);
+        if (ferr.empty()) ferr = feature_store_prepare(ctx->features, features, film, n_samples, a.n_sel_tiles, a.tile_w, s);
+        if (!ferr.empty()) { ctx->error = ferr; return NORI_ERR_OUT_OF_MEMORY; }
+        FilmLaunch fl;
+        fl.tile_first = 0; fl.store_tile_first = 0; fl.n_tiles = a.n_sel_tiles; fl.tile_mod = a.tile_mod; fl.tile_rem = a.tile_rem;
+        fl.tiles_x = a.tiles_x; fl.tiles_y = a.tiles_y; fl.tile_w = a.tile_w;
+        for (uint32_t sb = 0; sb < a.spp_count; sb += spp_per_launch) {
+            RenderArgs a2 = a;
+            a2.spp_begin = a.spp_begin + sb; a2.spp_count = std::min(spp_per_launch, a.spp_count - sb);
+            plan_chunks(a2);
+            FeatureLaunch pl;
+            pl.spp_begin = a2.spp_begin; pl.spp_count = a2.spp_count; pl.tile_mod = a2.tile_mod; pl.tile_rem = a2.tile_rem; pl.tiles_x = a2.tiles_x;
+            pl.n_sel_tiles = a2.n_sel_tiles; pl.n_chunks = a2.n_chunks; pl.chunk_spp = a2.chunk_spp; pl.mask = features;
+            timer.begin(KC_TRACE, s);
+            const hipError_t e = feature_pass_launch(ctx->dev, pl, need, film, ctx->features, ctx->d_stats, s);
+            timer.end(s);
+            HIP_TRY(ctx, e);
+            fl.n_spp = a2.spp_count;
+            timer.begin(KC_FILM, s);
+            for (int f = 0; f < kFeatureCount; ++f)      /* before the next launch overwrites the store */
+                if (features & (1u << f)) film_gather(ctx->dev, ctx->d_filter, feature_view(film, ctx->features, f), fl, s);
+            timer.end(s);
+            n_workgroups += a2.n_sel_tiles * a2.n_chunks;
+        }
+        timer.begin(KC_FILM, s);
+        for (int f = 0; f < kFeatureCount; ++f)
+            if (features & (1u << f)) film_resolve(ctx->dev, feature_view(film, ctx->features, f), fl, (float *) d_frame[f], s);
+        timer.end(s);
+        HIP_TRY(ctx, hipGetLastError());
+        if (stats) n_invalid = film_invalid_count(film, s);
+    }
+    if (stats) {
+        HIP_TRY(ctx, hipEventRecord(evp.b, s));
+        HIP_TRY(ctx, hipEventSynchronize(evp.b));
+        float ms = 0.0f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, evp.a, evp.b));
+        unsigned long long h[16];
+        HIP_TRY(ctx, hipMemcpy(h, ctx->d_stats, sizeof(h), hipMemcpyDeviceToHost));
+        memset(stats, 0, sizeof(*stats));
+        stats->n_camera_samples = h[0]; stats->n_closest_rays = h[1]; stats->n_invalid = n_invalid;
+        stats->kernel_ms = ms; stats->engine = 3u; stats->n_workgroups = n_workgroups;
+        float cms[KC_COUNT]; unsigned int cl[KC_COUNT];
+        timer.collect(cms, cl);
+        stats->trace_ms = cms[KC_TRACE]; stats->film_ms = cms[KC_FILM]; stats->n_trace_launches = cl[KC_TRACE];
+        stats->lds_bytes = feature_pass_lds_bytes(need);
+    }
+    return NORI_OK;
+}
+
+int nori_hip_render_features_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t features,
+                                  float *albedo, float *normal, float *depth, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params) return NORI_ERR_INVALID_ARGUMENT;
+    float *frame[kFeatureCount] = {albedo, normal, depth};
+    DeviceGuard g(ctx->device);
+    const size_t fb = frame_floats(ctx) * sizeof(float);
+    SCRATCH_OUT(ctx, df, kFeatureCount * fb);
+    HIP_TRY(ctx, hipMemset(df.p, 0, kFeatureCount * fb));
+    char *d[kFeatureCount];
+    for (int f = 0; f < kFeatureCount; ++f) d[f] = frame[f] ? (char *) df.p + f * fb : nullptr;
+    nori_render_stats local;
+    int rc = nori_hip_render_features(ctx, params, features, d[0], d[1], d[2], stats ? stats : &local);
+    if (rc) return rc;
+    for (int f = 0; f < kFeatureCount; ++f)
+        if ((features & (1u << f)) && frame[f]) HIP_TRY(ctx, hipMemcpy(frame[f], d[f], fb, hipMemcpyDeviceToHost));
     return NORI_OK;
 }
 

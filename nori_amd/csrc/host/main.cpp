@@ -1,5 +1,5 @@
 /*
- * main.cpp -- `nori <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]]`
+ * main.cpp -- `nori <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]]`
  * Command line of the reference (src/main.cpp:150-246).  There is no GUI on a
  * compute node: --no-gui is accepted and implied; --threads is accepted for
  * compatibility (the work runs on the GPU).  --seed block renders with the
@@ -13,7 +13,12 @@
  * being the most it spends; it prints where it stopped and writes the map as
  * <scene>.error.exr next to the frame (one device only).  With --adaptive a pass renders only
  * the 16x16 tiles whose mean error is still above E (nori_hip_render_adaptive); the samples
- * every pixel's tile received are written as <scene>.spp.exr.  A <test> root runs during parsing
+ * every pixel's tile received are written as <scene>.spp.exr.  --features runs, after the render and
+ * on the same context, the first-hit feature pass (nori_hip_render_features) over camera samples
+ * [0, K) of every pixel -- K = --feature-spp, default min(sampleCount, 16): the beauty frame's own
+ * first K sample positions -- and writes <scene>.albedo.exr, <scene>.normal.exr (decoded to
+ * [-1, 1], not renormalised) and <scene>.depth.exr (mean distance over the hits, coverage, mean
+ * squared distance), one device only.  A <test> root runs during parsing
  * (its activate()), as in the reference; failures exit with -1.
  */
 #include <nori/bitmap.h>
@@ -23,11 +28,12 @@ using namespace nori;
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        cerr << "Syntax: " << argv[0] << " <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]]" << endl;
+        cerr << "Syntax: " << argv[0] << " <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]]" << endl;
         return -1;
     }
     std::string sceneName;
-    bool toError = false, havePassSpp = false, adaptive = false;
+    bool toError = false, havePassSpp = false, adaptive = false, features = false, haveFeatureSpp = false;
+    long featureSpp = 16;
     float targetError = 0.0f;
     long passSpp = 16;
     int gpus = 1;
@@ -78,6 +84,18 @@ int main(int argc, char **argv) {
         } else if (token == "--adaptive") {
             adaptive = true;
             continue;
+        } else if (token == "--features") {
+            features = true;
+            continue;
+        } else if (token == "--feature-spp") {
+            char *end = nullptr;
+            if (i + 1 < argc) featureSpp = std::strtol(argv[i + 1], &end, 10);
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || featureSpp <= 0 || featureSpp > 0x7fffffffl) {
+                cerr << "Usage: \"--feature-spp\" expects a positive number of camera samples per pixel following it (with --features)." << endl;
+                return -1;
+            }
+            haveFeatureSpp = true; ++i;
+            continue;
         } else if (token == "--split" || token == "--merge" || token == "--film-order") {
             if (i + 1 >= argc) {
                 cerr << "\"" << token << "\" expects a value." << endl;
@@ -107,6 +125,14 @@ int main(int argc, char **argv) {
     }
     if (toError && gpus > 1) {
         cerr << "\"--target-error\" renders on one device: moment frames over several GPUs are not supported (got --gpus " << gpus << ")." << endl;
+        return -1;
+    }
+    if (haveFeatureSpp && !features) {
+        cerr << "Usage: \"--feature-spp\" goes with --features." << endl;
+        return -1;
+    }
+    if (features && gpus > 1) {
+        cerr << "Usage: \"--features\" renders on one device: feature frames over several GPUs are not supported (got --gpus " << gpus << ")." << endl;
         return -1;
     }
     if (sceneName.empty()) {
@@ -159,6 +185,32 @@ int main(int argc, char **argv) {
                     for (int x = 0; x < errorBitmap.cols(); ++x)
                         errorBitmap.set(y, x, Color3f(errorMap[(size_t) y * errorBitmap.cols() + x]));
                 errorBitmap.saveEXR(outputName + ".error");
+            }
+            if (features) {
+                const uint32_t spp = haveFeatureSpp ? (uint32_t) featureSpp : (uint32_t) std::min<size_t>(scene->getSampler()->getSampleCount(), 16);
+                std::vector<float> fa, fn, fd;
+                int border = 0;
+                nori_render_stats fst;
+                Timer ftimer;
+                renderSceneFeatures(scene, spp, fa, fn, fd, border, &fst);
+                cout << "Feature frames (albedo, normal, depth) of " << spp << " samples per pixel: took " << ftimer.elapsedString() << "; kernel "
+                     << timeString(fst.kernel_ms, true) << ", " << fst.n_closest_rays << " rays" << endl;
+                const Vector2i size = scene->getCamera()->getOutputSize();
+                Bitmap ba(size), bn(size), bd(size);
+                const int cols = size.x() + 2 * border;
+                /* the decode of include/nori_hip.h: each quotient 0 where its divisor is <= 0 */
+                auto quot = [](float a, float b) { return b > 0.0f ? a / b : 0.0f; };
+                for (int y = 0; y < size.y(); ++y)
+                    for (int x = 0; x < size.x(); ++x) {
+                        const size_t i = ((size_t) (y + border) * cols + (x + border)) * 4;
+                        ba.set(y, x, Color3f(quot(fa[i], fa[i + 3]), quot(fa[i + 1], fa[i + 3]), quot(fa[i + 2], fa[i + 3])));
+                        if (fn[i + 3] > 0.0f) bn.set(y, x, Color3f(2.0f * (fn[i] / fn[i + 3]) - 1.0f, 2.0f * (fn[i + 1] / fn[i + 3]) - 1.0f, 2.0f * (fn[i + 2] / fn[i + 3]) - 1.0f));
+                        else bn.set(y, x, Color3f(0.0f));
+                        bd.set(y, x, Color3f(quot(fd[i], fd[i + 2]), quot(fd[i + 2], fd[i + 3]), quot(fd[i + 1], fd[i + 2])));
+                    }
+                ba.saveEXR(outputName + ".albedo");
+                bn.saveEXR(outputName + ".normal");
+                bd.saveEXR(outputName + ".depth");
             }
         }
     } catch (const std::exception &e) {

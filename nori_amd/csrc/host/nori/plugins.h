@@ -307,5 +307,10 @@ std::unique_ptr<ImageBlock> renderSceneToError(Scene *scene, float targetError, 
    samples every 16x16 tile received (row-major tile grid) */
 std::unique_ptr<ImageBlock> renderSceneAdaptive(Scene *scene, float targetError, uint32_t passSpp, nori_adaptive_summary &summary,
                                                 std::vector<float> &errorMap, std::vector<uint32_t> &tileSpp, nori_render_stats *stats = nullptr);
+/* `--features`: nori_hip_render_features_host on the scene's device -- the first-hit albedo, shading-normal and depth frames of camera
+   samples [0, spp) of every pixel, RGBW frames with the layout of renderScene's block (`border` receives its border); decode as
+   include/nori_hip.h states */
+void renderSceneFeatures(Scene *scene, uint32_t spp, std::vector<float> &albedo, std::vector<float> &normal, std::vector<float> &depth,
+                         int &border, nori_render_stats *stats = nullptr);
 
 NORI_NAMESPACE_END

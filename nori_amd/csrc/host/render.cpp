@@ -132,4 +132,26 @@ std::unique_ptr<ImageBlock> renderSceneAdaptive(Scene *scene, float targetError,
     return result;
 }
 
+void renderSceneFeatures(Scene *scene, uint32_t spp, std::vector<float> &albedo, std::vector<float> &normal, std::vector<float> &depth,
+                         int &border, nori_render_stats *stats) {
+    const Camera *camera = scene->getCamera();
+    if (const char *gpus = std::getenv("NORI_GPUS"))
+        if (std::atoi(gpus) > 1) throw NoriException("--features renders on one device: feature frames over a device group are not supported (got --gpus %s)", gpus);
+    ImageBlock shape(camera->getOutputSize(), camera->getReconstructionFilter());      /* the frames' layout */
+    border = shape.getBorderSize();
+    const size_t n = (size_t) shape.rows() * shape.cols() * 4;
+    albedo.assign(n, 0.0f); normal.assign(n, 0.0f); depth.assign(n, 0.0f);
+
+    nori_render_params params;
+    std::memset(&params, 0, sizeof(params));
+    params.spp_begin = 0;
+    params.spp_count = spp;
+    params.tile_mod = 1; params.tile_rem = 0;
+    params.seed_mode = NORI_SEED_PER_SAMPLE;
+    nori_render_stats local;
+    Device &dev = scene->device();          /* the context of the beauty render: the scene is uploaded and the tree built */
+    dev.check(nori_hip_render_features_host(dev.ctx(), &params, NORI_FEATURE_ALBEDO | NORI_FEATURE_NORMAL | NORI_FEATURE_DEPTH, albedo.data(), normal.data(),
+                                            depth.data(), stats ? stats : &local), "nori_hip_render_features_host");
+}
+
 NORI_NAMESPACE_END

@@ -417,6 +417,43 @@ class Renderer:
                                                             ptr(tile_spp), C.byref(out), C.byref(st)), "render_adaptive_host")
         return rgbw, m2, err, tile_spp, out.as_dict(), st.as_dict()
 
+    # -- first-hit feature frames: albedo, shading normal, depth (include/nori_hip.h: nori_hip_render_features) --
+    def render_features_into(self, albedo=None, normal=None, depth=None, spp_count=None, spp_begin=0, tile_mod=1, tile_rem=0, stream=None,
+                             time_kernels=False, want_stats=True, seed_mode=capi.SEED_PER_SAMPLE, features=None):
+        """Accumulate the first-hit feature frames into the torch CUDA frame tensors given (shape and layout of render_into's): one
+        closest-hit ray per camera sample, the camera samples of render_into.  The mask follows from which tensors are given
+        (`features`, a nori_feature mask, overrides it: for the error paths).  Decode with develop_features_host."""
+        given = {"albedo": albedo, "normal": normal, "depth": depth}
+        mask = 0
+        for name, t in given.items():
+            if t is not None:
+                assert self._is_frame(t), name
+                mask |= capi.FEATURE_BITS[name]
+        if features is not None:
+            mask = int(features)
+        spp = self.scene.sample_count if spp_count is None else spp_count
+        raw = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        p = self._params(spp_begin, spp, tile_mod, tile_rem, False, raw, time_kernels, seed_mode)
+        st = capi.RenderStats() if want_stats else None
+        d = [C.c_void_p(t.data_ptr()) if t is not None else None for t in (albedo, normal, depth)]
+        self._check(self._lib.nori_hip_render_features(self._h, C.byref(p), mask, d[0], d[1], d[2], C.byref(st) if st is not None else None), "render_features")
+        return st.as_dict() if st is not None else None
+
+    def render_features_host(self, features=("albedo", "normal", "depth"), spp_count=None, spp_begin=0, tile_mod=1, tile_rem=0,
+                             time_kernels=False, seed_mode=capi.SEED_PER_SAMPLE):
+        """The named feature frames into fresh host frames; returns (dict name -> RGBW frame, stats dict)."""
+        names = [features] if isinstance(features, str) else list(features)
+        mask = 0
+        for name in names:
+            mask |= capi.FEATURE_BITS[name]
+        spp = self.scene.sample_count if spp_count is None else spp_count
+        p = self._params(spp_begin, spp, tile_mod, tile_rem, False, None, time_kernels, seed_mode)
+        frames = {name: np.zeros(self.frame_shape(), np.float32) for name in ("albedo", "normal", "depth") if name in names}
+        st = capi.RenderStats()
+        d = [ptr(frames[name]) if name in frames else None for name in ("albedo", "normal", "depth")]
+        self._check(self._lib.nori_hip_render_features_host(self._h, C.byref(p), mask, d[0], d[1], d[2], C.byref(st)), "render_features_host")
+        return frames, st.as_dict()
+
     # -- film_order = reference shared out: rows of 32x32 blocks (include/nori_hip.h: nori_hip_render_block_rows) --
     def block_rows(self) -> int:
         """rows of 32x32 blocks (NORI_BLOCK_SIZE) in the frame"""
@@ -544,3 +581,28 @@ def develop_host(rgbw: np.ndarray, border: int) -> np.ndarray:
     with np.errstate(divide="ignore", invalid="ignore"):
         rgb = np.where(wgt != 0, core[..., :3] / wgt, np.float32(0))
     return rgb.astype(np.float32)
+
+
+def develop_features_host(frames: dict, border: int) -> dict:
+    """The decode of include/nori_hip.h (nori_hip_render_features) for host feature frames, without the border, float32:
+    "albedo" (H, W, 3) = rgb / W; "normal" (H, W, 3) = 2 rgb / W - 1, not renormalised; "depth" (H, W, 3) = (mean distance over
+    the hits R / B, coverage B / W, mean squared distance over the hits G / B).  Each quotient is 0 where its divisor is <= 0."""
+    def core(a):
+        h, w = a.shape[0] - 2 * border, a.shape[1] - 2 * border
+        return np.asarray(a, np.float32)[border:border + h, border:border + w]
+
+    def quot(num, den):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(den > 0, num / den, np.float32(0)).astype(np.float32)
+
+    out = {}
+    if "albedo" in frames:
+        c = core(frames["albedo"])
+        out["albedo"] = quot(c[..., :3], c[..., 3:4])
+    if "normal" in frames:
+        c = core(frames["normal"])
+        out["normal"] = np.where(c[..., 3:4] > 0, np.float32(2) * quot(c[..., :3], c[..., 3:4]) - np.float32(1), np.float32(0)).astype(np.float32)
+    if "depth" in frames:
+        c = core(frames["depth"])
+        out["depth"] = np.stack([quot(c[..., 0], c[..., 2]), quot(c[..., 2], c[..., 3]), quot(c[..., 1], c[..., 2])], axis=-1)
+    return out
