@@ -694,6 +694,75 @@ int nori_hip_render_features(nori_hip_ctx *ctx, const nori_render_params *params
 int nori_hip_render_features_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t features,
                                   float *albedo, float *normal, float *depth, nori_render_stats *stats /* may be NULL */);
 
+/* ------------------------------------------- the denoiser: feature- and variance-guided NL-means
+ *
+ * No counterpart in the reference.  The consumer of the moment frame (nori_hip_render_moments) and of the feature frames
+ * (nori_hip_render_features): the NL-means of Rousselle et al. with variance cancellation, its patch distance formed from the
+ * per-pixel variance of the mean, with one cross-bilateral term per feature under a single exponential.  A translation unit
+ * of its own (denoise.h); the kernels of the renders are not involved and render the same bits before and after a call.
+ *
+ * All frames have the bordered RGBW layout of nori_hip_render; only the height x width pixels inside the border are read.
+ * Everything below is float32 without FMA contraction, every `/` an IEEE division, in the order written.
+ *
+ * Step A, the guide record of a frame pixel: 16 floats  mu[3], var[3], albedo[3], normal[3], z, cov, valid, 0.
+ * With S the RGBW pixel and M the moment pixel (the terms of nori_hip_error_map):
+ *   if !(S.w > 0): valid = 0, mu = var = 0; else valid = 1 and
+ *   r = 1 / S.w;  k = (M.w * r) * r
+ *   for c in r, g, b:  mu_c = S.c * r;  q = M.c * r;  v = q - mu_c * mu_c;  if !(v > 0) v = 0;  var_c = v * k
+ * (var is the plug-in variance of the pixel's mean.)  With A, N, D the pixels of the albedo, normal and depth frames -- the
+ * decode stated under nori_hip_render_features, a quotient a / b being 0 unless b > 0:
+ *   albedo_c = A.c / A.w;   normal_c = 2 * (N.c / N.w) - 1 (0 unless N.w > 0);   cov = D.b / D.w;   z = D.r / D.b
+ * whether or not the pixel is valid.  A feature frame passed as NULL leaves its fields 0 and switches its term off in step B.
+ *
+ * Step B, the filter (nori_denoise_params; min(a, b) below is a < b ? a : b).  Per pixel p:
+ *   if valid_p == 0: out = (0, 0, 0), wsum = 0.  Otherwise num = (0, 0, 0), wsum = 0 and, dy = -R .. R the outer and dx = -R .. R
+ *   the inner loop, q = p + (dx, dy); a tap with q outside the frame or valid_q == 0 contributes nothing; else
+ *   1  the colour distance of a pair (p', q'):  delta = 0;  for c in r, g, b:
+ *        t = mu_p'c - mu_q'c;  nume = t * t - alpha * (var_p'c + min(var_q'c, var_p'c))
+ *        deno = 1e-10f + (k_c * k_c) * (var_p'c + var_q'c);  delta = delta + nume / deno
+ *   2  the patch:  acc = 0, cnt = 0;  oy = -F .. F the outer and ox = -F .. F the inner loop, p' = p + o, q' = q + o: if both
+ *      are inside the frame and valid, acc = acc + delta(p', q') and cnt += 1 (o = 0 always qualifies).
+ *      d = acc / (3.0f * (float) cnt);  if !(d > 0) d = 0
+ *   3  the exponent:  e = d;  each sum s below starts at 0 and runs s = s + t * t over the three components in order
+ *        with albedo:  t = albedo_pc - albedo_qc;  e = e + s / tau_albedo
+ *        with normal:  t = normal_pc - normal_qc;  e = e + s / tau_normal
+ *        with depth:   t = z_p - z_q;  g = (k_depth * k_depth) * (z_p * z_p + z_q * z_q) + 1e-12f;  e = e + (t * t) / g
+ *                      u = cov_p - cov_q;  e = e + (u * u) / tau_cov
+ *   4  the weight:  w = exp(-e) if e <= 87.0f, else 0 -- exp as NORI_ARITH_EXP (nori_hip_debug_arith) evaluates it, the pinned
+ *      function of the render path; the cut-off keeps subnormal weights and a NaN exponent out
+ *   5  num_c = num_c + w * mu_qc;  wsum = wsum + w
+ *   and after the loop out_c = num_c / wsum (the centre tap has e = 0, w = 1: wsum >= 1).
+ *
+ * nori_hip_denoise_guides runs step A and writes height * width * 16 floats to d_guides; nori_hip_denoise runs both steps
+ * (its guide records live in a buffer of the context, one per stream) and writes d_rgb_out, height * width * 3 floats in the
+ * layout of nori_hip_develop, and -- unless NULL -- d_wsum, height * width floats.  params == NULL: the defaults.  d_albedo,
+ * d_normal, d_depth may each be NULL; d_rgbw and d_m2 may not.  All DEVICE memory.  Asynchronous on `stream`, nothing of the
+ * context's but the frame geometry is read, no atomics: the same frames give the same bytes, and calls on different streams
+ * may run at once.  Errors: NORI_ERR_NOT_READY without an uploaded scene; NORI_ERR_INVALID_ARGUMENT (with a message) for a
+ * NULL required pointer, radius outside 1 .. 8, patch outside 0 .. 2, k_c, tau_albedo, tau_normal, tau_cov or k_depth not above
+ * 0, alpha below 0.  The _host twins take HOST frames and buffers and are synchronous, as nori_hip_error_map_host.
+ * Limits: below about 16 samples per pixel the variance estimates are too noisy to guide the weights; a firefly has a large
+ * variance of its own and passes unchanged. */
+typedef struct nori_denoise_params {
+    uint32_t radius;         /* R: the window is (2R + 1)^2 taps, 1 .. 8 */
+    uint32_t patch;          /* F: patches are (2F + 1)^2 pixels, 0 .. 2 */
+    float k_c;               /* the colour distance's sensitivity */
+    float alpha;             /* strength of the variance cancellation */
+    float tau_albedo, tau_normal;
+    float k_depth;           /* relative depth tolerance */
+    float tau_cov;
+} nori_denoise_params;
+#define NORI_DENOISE_PARAMS_DEFAULT { 5u, 1u, 1.0f, 1.0f, 0.02f, 0.1f, 0.1f, 0.05f }
+int nori_hip_denoise_guides(nori_hip_ctx *ctx, const void *d_rgbw, const void *d_m2, const void *d_albedo /* may be NULL */,
+                            const void *d_normal /* may be NULL */, const void *d_depth /* may be NULL */, void *d_guides, void *stream);
+int nori_hip_denoise(nori_hip_ctx *ctx, const nori_denoise_params *params /* NULL: the defaults */, const void *d_rgbw, const void *d_m2,
+                     const void *d_albedo, const void *d_normal, const void *d_depth, void *d_rgb_out, void *d_wsum /* may be NULL */,
+                     void *stream);
+int nori_hip_denoise_guides_host(nori_hip_ctx *ctx, const float *rgbw, const float *m2, const float *albedo, const float *normal,
+                                 const float *depth, float *guides);
+int nori_hip_denoise_host(nori_hip_ctx *ctx, const nori_denoise_params *params, const float *rgbw, const float *m2, const float *albedo,
+                          const float *normal, const float *depth, float *rgb_out, float *wsum /* may be NULL */);
+
 /* film_order = "reference" shared out over devices or ranks.  The reference adds a 32x32 block's samples consecutively
  * into the block's own ImageBlock (renderBlock, src/main.cpp:27-55) and the blocks into the frame in BlockGenerator's order
  * (src/block.cpp:93-152): the smallest share that keeps the order is a block, the one handed out here is a ROW of blocks.

@@ -101,6 +101,25 @@ class RenderStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DenoiseParams(C.Structure):
+    """nori_denoise_params; a fresh one holds NORI_DENOISE_PARAMS_DEFAULT"""
+    _fields_ = [("radius", C.c_uint32), ("patch", C.c_uint32), ("k_c", C.c_float), ("alpha", C.c_float),
+                ("tau_albedo", C.c_float), ("tau_normal", C.c_float), ("k_depth", C.c_float), ("tau_cov", C.c_float)]
+    DEFAULTS = {"radius": 5, "patch": 1, "k_c": 1.0, "alpha": 1.0, "tau_albedo": 0.02, "tau_normal": 0.1, "k_depth": 0.1, "tau_cov": 0.05}
+
+    def __init__(self, **kw):
+        unknown = set(kw) - set(self.DEFAULTS)
+        if unknown:
+            raise TypeError(f"unknown denoise parameters: {sorted(unknown)}")
+        super().__init__(**{**self.DEFAULTS, **kw})
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+GUIDE_FLOATS = 16      # mu[3], var[3], albedo[3], normal[3], z, cov, valid, 0
+
+
 class ErrorSummary(C.Structure):
     """nori_error_summary"""
     _fields_ = [("sum_err", C.c_double), ("max_err", C.c_float), ("threshold", C.c_float),
@@ -182,6 +201,10 @@ HIP_PROTOTYPES = {
     "nori_hip_render_moments_host": (C.c_int, [_P, C.POINTER(RenderParams), _P, _P, C.POINTER(RenderStats)]),
     "nori_hip_render_features": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, _P, _P, _P, C.POINTER(RenderStats)]),
     "nori_hip_render_features_host": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, _P, _P, _P, C.POINTER(RenderStats)]),
+    "nori_hip_denoise_guides": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "nori_hip_denoise": (C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, _P, _P]),
+    "nori_hip_denoise_guides_host": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "nori_hip_denoise_host": (C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, _P]),
     "nori_hip_error_map": (C.c_int, [_P, _P, _P, _P, C.c_float, C.POINTER(ErrorSummary), _P]),
     "nori_hip_error_map_host": (C.c_int, [_P, _P, _P, _P, C.c_float, C.POINTER(ErrorSummary)]),
     "nori_hip_render_to_error": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_float, _P, _P, C.POINTER(C.c_uint32),

@@ -37,6 +37,7 @@
 #include "film.h"
 #include "film_tiles.h"
 #include "features.h"
+#include "denoise.h"
 #include "ktimer.h"
 #include "shade_tables.h"
 #include "rt_path.h"
@@ -497,6 +498,7 @@ struct nori_hip_ctx {
     FilmMoments moments;      /* renders that keep second moments, nori_hip_error_map: a second set of tile accumulators, partial sums */
     FilmTiles tiles;          /* renders by tile list, tile selection, the adaptive loop: lists, inverse table, tile errors (film_tiles.h) */
     FeatureStore features;    /* nori_hip_render_features: a sample plane and a set of tile accumulators per feature (features.h) */
+    DenoiseStore denoise;     /* nori_hip_denoise: the guide records between its two kernels, a buffer per stream (denoise.h) */
 };
 
 static std::string g_create_error;
@@ -604,6 +606,7 @@ void nori_hip_destroy(nori_hip_ctx *ctx) {
     film_moments_release(ctx->moments);
     film_tiles_release(ctx->tiles);
     feature_store_release(ctx->features);
+    denoise_store_release(ctx->denoise);
     if (ctx->d_stats) (void) hipFree(ctx->d_stats);
     delete ctx;
 }
@@ -1889,6 +1892,110 @@ int nori_hip_render_features_host(nori_hip_ctx *ctx, const nori_render_params *p
     if (rc) return rc;
     for (int f = 0; f < kFeatureCount; ++f)
         if ((features & (1u << f)) && frame[f]) HIP_TRY(ctx, hipMemcpy(frame[f], d[f], fb, hipMemcpyDeviceToHost));
+    return NORI_OK;
+}
+
+/* ---- the denoiser (denoise.h): guide records from the frames, then the NL-means filter over them ---- */
+
+static int denoise_frames_ok(nori_hip_ctx *ctx, const void *rgbw, const void *m2, const void *out, const char *what) {
+    if (!rgbw || !m2 || !out) { ctx->error = std::string(what) + ": needs the RGBW frame, the moment frame and a buffer to fill"; return NORI_ERR_INVALID_ARGUMENT; }
+    return NORI_OK;
+}
+
+/* the launch of step B from the public parameters (NULL: the defaults), or the message of the first one out of range */
+static std::string denoise_plan(const nori_denoise_params *params, DenoiseLaunch &dl) {
+    const nori_denoise_params def = NORI_DENOISE_PARAMS_DEFAULT;
+    const nori_denoise_params p = params ? *params : def;
+    if (p.radius < 1u || p.radius > (uint32_t) kDenoiseMaxRadius) return "denoise: the window radius must be 1 .. 8";
+    if (p.patch > (uint32_t) kDenoiseMaxPatch) return "denoise: the patch radius must be 0 .. 2";
+    if (!(p.k_c > 0.0f)) return "denoise: k_c must be positive";
+    if (!(p.alpha >= 0.0f)) return "denoise: alpha must not be negative";
+    if (!(p.tau_albedo > 0.0f) || !(p.tau_normal > 0.0f) || !(p.tau_cov > 0.0f)) return "denoise: tau_albedo, tau_normal and tau_cov must be positive";
+    if (!(p.k_depth > 0.0f)) return "denoise: k_depth must be positive";
+    dl.radius = (int32_t) p.radius; dl.patch = (int32_t) p.patch;
+    dl.kc2 = p.k_c * p.k_c; dl.alpha = p.alpha;
+    dl.tau_albedo = p.tau_albedo; dl.tau_normal = p.tau_normal;
+    dl.kd2 = p.k_depth * p.k_depth; dl.tau_cov = p.tau_cov;
+    return std::string();
+}
+
+int nori_hip_denoise_guides(nori_hip_ctx *ctx, const void *d_rgbw, const void *d_m2, const void *d_albedo, const void *d_normal,
+                            const void *d_depth, void *d_guides, void *stream) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (int rc = denoise_frames_ok(ctx, d_rgbw, d_m2, d_guides, "denoise_guides")) return rc;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(ctx, denoise_guides_launch(ctx->host.camera.width, ctx->host.camera.height, ctx->host.filter.border, (const float *) d_rgbw, (const float *) d_m2,
+                                       (const float *) d_albedo, (const float *) d_normal, (const float *) d_depth, (float *) d_guides, stream));
+    return NORI_OK;
+}
+
+int nori_hip_denoise(nori_hip_ctx *ctx, const nori_denoise_params *params, const void *d_rgbw, const void *d_m2, const void *d_albedo,
+                     const void *d_normal, const void *d_depth, void *d_rgb_out, void *d_wsum, void *stream) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (int rc = denoise_frames_ok(ctx, d_rgbw, d_m2, d_rgb_out, "denoise")) return rc;
+    DenoiseLaunch dl;
+    const std::string bad = denoise_plan(params, dl);
+    if (!bad.empty()) { ctx->error = bad; return NORI_ERR_INVALID_ARGUMENT; }
+    dl.width = ctx->host.camera.width; dl.height = ctx->host.camera.height;
+    dl.terms = (d_albedo ? kDenoiseAlbedo : 0u) | (d_normal ? kDenoiseNormal : 0u) | (d_depth ? kDenoiseDepth : 0u);
+    DeviceGuard g(ctx->device);
+    float *d_guides = nullptr;
+    const std::string err = denoise_store_guides(ctx->denoise, stream, (size_t) dl.width * (size_t) dl.height, &d_guides);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_OUT_OF_MEMORY; }
+    HIP_TRY(ctx, denoise_guides_launch(dl.width, dl.height, ctx->host.filter.border, (const float *) d_rgbw, (const float *) d_m2, (const float *) d_albedo,
+                                       (const float *) d_normal, (const float *) d_depth, d_guides, stream));
+    HIP_TRY(ctx, denoise_filter_launch(dl, d_guides, (float *) d_rgb_out, (float *) d_wsum, stream));
+    return NORI_OK;
+}
+
+/* the host twins: the frames that are given go to one scratch buffer, in the order rgbw, m2, albedo, normal, depth */
+struct DenoiseHostFrames {
+    char *d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+};
+static hipError_t denoise_upload(const float *const frame[5], char *base, size_t fb, DenoiseHostFrames &out) {
+    for (int f = 0; f < 5; ++f) {
+        if (!frame[f]) continue;
+        out.d[f] = base + (size_t) f * fb;
+        const hipError_t e = hipMemcpy(out.d[f], frame[f], fb, hipMemcpyHostToDevice);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+int nori_hip_denoise_guides_host(nori_hip_ctx *ctx, const float *rgbw, const float *m2, const float *albedo, const float *normal,
+                                 const float *depth, float *guides) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (int rc = denoise_frames_ok(ctx, rgbw, m2, guides, "denoise_guides")) return rc;
+    DeviceGuard g(ctx->device);
+    const size_t fb = frame_floats(ctx) * sizeof(float);
+    const size_t gb = (size_t) ctx->host.camera.width * (size_t) ctx->host.camera.height * kGuideFloats * sizeof(float);
+    SCRATCH_OUT(ctx, df, 5 * fb + gb);
+    const float *const frame[5] = {rgbw, m2, albedo, normal, depth};
+    DenoiseHostFrames d;
+    HIP_TRY(ctx, denoise_upload(frame, (char *) df.p, fb, d));
+    char *d_guides = (char *) df.p + 5 * fb;
+    int rc = nori_hip_denoise_guides(ctx, d.d[0], d.d[1], d.d[2], d.d[3], d.d[4], d_guides, nullptr);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(guides, d_guides, gb, hipMemcpyDeviceToHost));      /* (a blocking copy: behind the kernel on the default stream) */
+    return NORI_OK;
+}
+
+int nori_hip_denoise_host(nori_hip_ctx *ctx, const nori_denoise_params *params, const float *rgbw, const float *m2, const float *albedo,
+                          const float *normal, const float *depth, float *rgb_out, float *wsum) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (int rc = denoise_frames_ok(ctx, rgbw, m2, rgb_out, "denoise")) return rc;
+    DeviceGuard g(ctx->device);
+    const size_t fb = frame_floats(ctx) * sizeof(float);
+    const size_t pb = (size_t) ctx->host.camera.width * (size_t) ctx->host.camera.height * sizeof(float);
+    SCRATCH_OUT(ctx, df, 5 * fb + 4 * pb);
+    const float *const frame[5] = {rgbw, m2, albedo, normal, depth};
+    DenoiseHostFrames d;
+    HIP_TRY(ctx, denoise_upload(frame, (char *) df.p, fb, d));
+    char *d_out = (char *) df.p + 5 * fb, *d_wsum = d_out + 3 * pb;
+    int rc = nori_hip_denoise(ctx, params, d.d[0], d.d[1], d.d[2], d.d[3], d.d[4], d_out, wsum ? d_wsum : nullptr, nullptr);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpy(rgb_out, d_out, 3 * pb, hipMemcpyDeviceToHost));
+    if (wsum) HIP_TRY(ctx, hipMemcpy(wsum, d_wsum, pb, hipMemcpyDeviceToHost));
     return NORI_OK;
 }
 

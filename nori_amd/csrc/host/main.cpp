@@ -1,5 +1,5 @@
 /*
- * main.cpp -- `nori <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]]`
+ * main.cpp -- `nori <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]] [--denoise [--denoise-radius R] [--denoise-patch F]]`
  * Command line of the reference (src/main.cpp:150-246).  There is no GUI on a
  * compute node: --no-gui is accepted and implied; --threads is accepted for
  * compatibility (the work runs on the GPU).  --seed block renders with the
@@ -18,7 +18,11 @@
  * [0, K) of every pixel -- K = --feature-spp, default min(sampleCount, 16): the beauty frame's own
  * first K sample positions -- and writes <scene>.albedo.exr, <scene>.normal.exr (decoded to
  * [-1, 1], not renormalised) and <scene>.depth.exr (mean distance over the hits, coverage, mean
- * squared distance), one device only.  A <test> root runs during parsing
+ * squared distance), one device only.  --denoise renders through nori_hip_render_moments, renders the
+ * three feature frames with the scene's sample count (or --feature-spp), runs nori_hip_denoise over
+ * them -- window radius --denoise-radius (1..8, default 5), patch radius --denoise-patch (0..2,
+ * default 1) -- and writes <scene>.denoised.exr beside the usual output; one device only, not
+ * together with --target-error.  A <test> root runs during parsing
  * (its activate()), as in the reference; failures exit with -1.
  */
 #include <nori/bitmap.h>
@@ -28,12 +32,14 @@ using namespace nori;
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        cerr << "Syntax: " << argv[0] << " <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]]" << endl;
+        cerr << "Syntax: " << argv[0] << " <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]] [--denoise [--denoise-radius R] [--denoise-patch F]]" << endl;
         return -1;
     }
     std::string sceneName;
     bool toError = false, havePassSpp = false, adaptive = false, features = false, haveFeatureSpp = false;
     long featureSpp = 16;
+    bool denoise = false, haveDenoiseRadius = false, haveDenoisePatch = false;
+    long denoiseRadius = 5, denoisePatch = 1;
     float targetError = 0.0f;
     long passSpp = 16;
     int gpus = 1;
@@ -96,6 +102,22 @@ int main(int argc, char **argv) {
             }
             haveFeatureSpp = true; ++i;
             continue;
+        } else if (token == "--denoise") {
+            denoise = true;
+            continue;
+        } else if (token == "--denoise-radius" || token == "--denoise-patch") {
+            const bool radius = token == "--denoise-radius";
+            const long lo = radius ? 1 : 0, hi = radius ? 8 : 2;
+            char *end = nullptr;
+            long v = -1;
+            if (i + 1 < argc) v = std::strtol(argv[i + 1], &end, 10);
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || v < lo || v > hi) {
+                cerr << "Usage: \"" << token << "\" expects a " << (radius ? "window radius 1 .. 8" : "patch radius 0 .. 2") << " following it (with --denoise)." << endl;
+                return -1;
+            }
+            (radius ? denoiseRadius : denoisePatch) = v;
+            (radius ? haveDenoiseRadius : haveDenoisePatch) = true; ++i;
+            continue;
         } else if (token == "--split" || token == "--merge" || token == "--film-order") {
             if (i + 1 >= argc) {
                 cerr << "\"" << token << "\" expects a value." << endl;
@@ -127,8 +149,20 @@ int main(int argc, char **argv) {
         cerr << "\"--target-error\" renders on one device: moment frames over several GPUs are not supported (got --gpus " << gpus << ")." << endl;
         return -1;
     }
-    if (haveFeatureSpp && !features) {
-        cerr << "Usage: \"--feature-spp\" goes with --features." << endl;
+    if (haveFeatureSpp && !features && !denoise) {
+        cerr << "Usage: \"--feature-spp\" goes with --features (or --denoise)." << endl;
+        return -1;
+    }
+    if ((haveDenoiseRadius || haveDenoisePatch) && !denoise) {
+        cerr << "Usage: \"" << (haveDenoiseRadius ? "--denoise-radius" : "--denoise-patch") << "\" goes with --denoise." << endl;
+        return -1;
+    }
+    if (denoise && gpus > 1) {
+        cerr << "Usage: \"--denoise\" renders on one device: moment and feature frames over several GPUs are not supported (got --gpus " << gpus << ")." << endl;
+        return -1;
+    }
+    if (denoise && toError) {
+        cerr << "Usage: \"--denoise\" renders the scene's sample count and does not go with --target-error." << endl;
         return -1;
     }
     if (features && gpus > 1) {
@@ -152,7 +186,12 @@ int main(int argc, char **argv) {
             std::vector<float> errorMap;
             nori_adaptive_summary adaptiveSummary;
             std::vector<uint32_t> tileSpp;
-            std::unique_ptr<ImageBlock> result = adaptive ? renderSceneAdaptive(scene, targetError, (uint32_t) passSpp, adaptiveSummary, errorMap, tileSpp, &st)
+            std::vector<float> denoised;
+            nori_denoise_params dn = NORI_DENOISE_PARAMS_DEFAULT;
+            dn.radius = (uint32_t) denoiseRadius; dn.patch = (uint32_t) denoisePatch;
+            const uint32_t denoiseFeatureSpp = haveFeatureSpp ? (uint32_t) featureSpp : (uint32_t) scene->getSampler()->getSampleCount();
+            std::unique_ptr<ImageBlock> result = denoise ? renderSceneDenoised(scene, dn, denoiseFeatureSpp, denoised, &st)
+                                                 : adaptive ? renderSceneAdaptive(scene, targetError, (uint32_t) passSpp, adaptiveSummary, errorMap, tileSpp, &st)
                                                  : toError ? renderSceneToError(scene, targetError, (uint32_t) passSpp, sppDone, summary, errorMap, &st)
                                                          : renderScene(scene, &st);
             cout << "done. (took " << timer.elapsedString() << "; kernel " << timeString(st.kernel_ms, true) << ", "
@@ -185,6 +224,17 @@ int main(int argc, char **argv) {
                     for (int x = 0; x < errorBitmap.cols(); ++x)
                         errorBitmap.set(y, x, Color3f(errorMap[(size_t) y * errorBitmap.cols() + x]));
                 errorBitmap.saveEXR(outputName + ".error");
+            }
+            if (denoise) {
+                Bitmap db(scene->getCamera()->getOutputSize());
+                for (int y = 0; y < db.rows(); ++y)
+                    for (int x = 0; x < db.cols(); ++x) {
+                        const float *p = &denoised[((size_t) y * db.cols() + x) * 3];
+                        db.set(y, x, Color3f(p[0], p[1], p[2]));
+                    }
+                db.saveEXR(outputName + ".denoised");
+                cout << "Denoised (window radius " << denoiseRadius << ", patch radius " << denoisePatch << ", features of " << denoiseFeatureSpp
+                     << " samples per pixel) to " << outputName << ".denoised.exr" << endl;
             }
             if (features) {
                 const uint32_t spp = haveFeatureSpp ? (uint32_t) featureSpp : (uint32_t) std::min<size_t>(scene->getSampler()->getSampleCount(), 16);

@@ -313,4 +313,10 @@ std::unique_ptr<ImageBlock> renderSceneAdaptive(Scene *scene, float targetError,
 void renderSceneFeatures(Scene *scene, uint32_t spp, std::vector<float> &albedo, std::vector<float> &normal, std::vector<float> &depth,
                          int &border, nori_render_stats *stats = nullptr);
 
+/* `--denoise`: the scene's samples through nori_hip_render_moments_host (the returned block is the beauty frame, as renderScene's),
+   the three feature frames of camera samples [0, featureSpp) through renderSceneFeatures, then nori_hip_denoise_host:
+   `denoised` receives height * width * 3 floats, row-major RGB */
+std::unique_ptr<ImageBlock> renderSceneDenoised(Scene *scene, const nori_denoise_params &dn, uint32_t featureSpp, std::vector<float> &denoised,
+                                                nori_render_stats *stats = nullptr);
+
 NORI_NAMESPACE_END

@@ -154,4 +154,34 @@ void renderSceneFeatures(Scene *scene, uint32_t spp, std::vector<float> &albedo,
                                             depth.data(), stats ? stats : &local), "nori_hip_render_features_host");
 }
 
+std::unique_ptr<ImageBlock> renderSceneDenoised(Scene *scene, const nori_denoise_params &dn, uint32_t featureSpp, std::vector<float> &denoised,
+                                                nori_render_stats *stats) {
+    const Camera *camera = scene->getCamera();
+    scene->getIntegrator()->preprocess(scene);
+    if (const char *gpus = std::getenv("NORI_GPUS"))
+        if (std::atoi(gpus) > 1) throw NoriException("--denoise renders on one device: moment and feature frames over a device group are not supported (got --gpus %s)", gpus);
+    if (const char *seed = std::getenv("NORI_SEED"))
+        if (std::string(seed) == "block") throw NoriException("--denoise needs the feature frames, which --seed block cannot give (a block's stream is serial)");
+    std::unique_ptr<ImageBlock> result(new ImageBlock(camera->getOutputSize(), camera->getReconstructionFilter()));
+    result->clear();
+    std::vector<float> m2((size_t) result->rows() * result->cols() * 4, 0.0f);
+
+    nori_render_params params;
+    std::memset(&params, 0, sizeof(params));
+    params.spp_begin = 0;
+    params.spp_count = (uint32_t) scene->getSampler()->getSampleCount();
+    params.tile_mod = 1; params.tile_rem = 0;
+    params.seed_mode = NORI_SEED_PER_SAMPLE;
+    nori_render_stats local;
+    Device &dev = scene->device();
+    dev.check(nori_hip_render_moments_host(dev.ctx(), &params, result->data(), m2.data(), stats ? stats : &local), "nori_hip_render_moments_host");
+    std::vector<float> fa, fn, fd;
+    int border = 0;
+    renderSceneFeatures(scene, featureSpp, fa, fn, fd, border);
+    const size_t n = (size_t) camera->getOutputSize().x() * camera->getOutputSize().y();
+    denoised.assign(n * 3, 0.0f);
+    dev.check(nori_hip_denoise_host(dev.ctx(), &dn, result->data(), m2.data(), fa.data(), fn.data(), fd.data(), denoised.data(), nullptr), "nori_hip_denoise_host");
+    return result;
+}
+
 NORI_NAMESPACE_END

@@ -454,6 +454,55 @@ class Renderer:
         self._check(self._lib.nori_hip_render_features_host(self._h, C.byref(p), mask, d[0], d[1], d[2], C.byref(st)), "render_features_host")
         return frames, st.as_dict()
 
+    # -- the denoiser: guide records, NL-means filter (include/nori_hip.h: nori_hip_denoise) --
+    def _host_frames(self, rgbw, m2, albedo, normal, depth):
+        frames = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (rgbw, m2, albedo, normal, depth)]
+        assert frames[0] is not None and frames[1] is not None, "the RGBW frame and the moment frame are required"
+        for a in frames:
+            assert a is None or a.shape == tuple(self.frame_shape())
+        return frames
+
+    def denoise_guides_host(self, rgbw, m2, albedo=None, normal=None, depth=None):
+        """Step A for host frames: (height, width, 16) float32 -- mu[3], var[3], albedo[3], normal[3], z, cov, valid, 0 per pixel."""
+        frames = self._host_frames(rgbw, m2, albedo, normal, depth)
+        c = self.scene.camera
+        guides = np.zeros((c.height, c.width, capi.GUIDE_FLOATS), np.float32)
+        self._check(self._lib.nori_hip_denoise_guides_host(self._h, *[ptr(a) for a in frames], ptr(guides)), "denoise_guides_host")
+        return guides
+
+    def denoise_host(self, rgbw, m2, albedo=None, normal=None, depth=None, **params):
+        """Steps A and B for host frames: (rgb (height, width, 3), wsum (height, width)).  params: the fields of nori_denoise_params
+        (radius, patch, k_c, alpha, tau_albedo, tau_normal, k_depth, tau_cov), each defaulting to the header's default."""
+        frames = self._host_frames(rgbw, m2, albedo, normal, depth)
+        c = self.scene.camera
+        rgb, wsum = np.zeros((c.height, c.width, 3), np.float32), np.zeros((c.height, c.width), np.float32)
+        p = capi.DenoiseParams(**params)
+        self._check(self._lib.nori_hip_denoise_host(self._h, C.byref(p), *[ptr(a) for a in frames], ptr(rgb), ptr(wsum)), "denoise_host")
+        return rgb, wsum
+
+    def denoise_into(self, rgb_out, rgbw, m2, albedo=None, normal=None, depth=None, wsum=None, stream=None, **params):
+        """Steps A and B on torch CUDA tensors: the frames have frame_shape(), rgb_out is (height, width, 3) and wsum, if given,
+        (height, width), all float32 and contiguous.  Asynchronous on `stream` (a torch.cuda.Stream, or None for the default one)."""
+        c = self.scene.camera
+        assert self._is_frame(rgbw) and self._is_frame(m2)
+        for t in (albedo, normal, depth):
+            assert t is None or self._is_frame(t)
+        for t, shape in ((rgb_out, (c.height, c.width, 3)), (wsum, (c.height, c.width))):
+            assert t is None or (t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape and str(t.dtype) == "torch.float32")
+        p = capi.DenoiseParams(**params)
+        raw = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        d = [C.c_void_p(t.data_ptr()) if t is not None else None for t in (rgbw, m2, albedo, normal, depth, rgb_out, wsum)]
+        self._check(self._lib.nori_hip_denoise(self._h, C.byref(p), *d, raw), "denoise")
+
+    def denoise_guides_into(self, guides, rgbw, m2, albedo=None, normal=None, depth=None, stream=None):
+        """Step A on torch CUDA tensors: guides is (height, width, 16) float32."""
+        c = self.scene.camera
+        assert self._is_frame(rgbw) and self._is_frame(m2)
+        assert guides.is_cuda and guides.is_contiguous() and tuple(guides.shape) == (c.height, c.width, capi.GUIDE_FLOATS) and str(guides.dtype) == "torch.float32"
+        raw = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        d = [C.c_void_p(t.data_ptr()) if t is not None else None for t in (rgbw, m2, albedo, normal, depth, guides)]
+        self._check(self._lib.nori_hip_denoise_guides(self._h, *d, raw), "denoise_guides")
+
     # -- film_order = reference shared out: rows of 32x32 blocks (include/nori_hip.h: nori_hip_render_block_rows) --
     def block_rows(self) -> int:
         """rows of 32x32 blocks (NORI_BLOCK_SIZE) in the frame"""
