@@ -304,7 +304,15 @@ typedef struct nori_render_stats {
     float tail_ms;           /* time_kernels != 0: summed durations of the wf_finish launches that ran BESIDE the next batch's kernels, on
                                 their own `tail_cus` CUs (wavefront engine, calls of two or more batches); not part of shade_ms */
     uint32_t tail_cus;
+    uint32_t wf_record;      /* NORI_WF_RECORD_*: the per-path record the wavefront engine kept this call's paths in -- the compact one
+                                (88 B: no pcg32 state, no eta, L + Ld summed by the storing pass) for all-diffuse scenes under
+                                path_mats / path_ems / path_mis, the full one (100 B) otherwise and for every scene with
+                                NORI_HIP_WF_RECORD=full; 0: another engine.  (Appended in the struct's tail padding: its size and the
+                                offsets of the fields before it are those of before.) */
 } nori_render_stats;
+#define NORI_WF_RECORD_NONE 0
+#define NORI_WF_RECORD_FULL 1
+#define NORI_WF_RECORD_COMPACT 2
 
 typedef struct nori_accel_info {
     uint32_t n_triangles;

@@ -1451,7 +1451,7 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
             stats->n_node_tests = wst.n_nodes; stats->n_tri_tests = wst.n_tris; stats->n_invalid = wst.n_invalid;
             stats->n_workgroups = wst.n_launches;
             stats->trace_cus = wst.trace_cus;
-            stats->tail_ms = wst.class_ms[KC_TAIL]; stats->tail_cus = wst.tail_cus;
+            stats->tail_ms = wst.class_ms[KC_TAIL]; stats->tail_cus = wst.tail_cus; stats->wf_record = wst.record;
             if (getenv("NORI_HIP_CENSUS")) fprintf(stderr, "[wavefront] batches %u iterations %u launches %u state %.1f MB\n", wst.n_batches, wst.n_iterations, wst.n_launches, wst.state_bytes / 1048576.0);
         }
         const uint32_t need = ctx->bvh.max_depth + 1;
@@ -1538,7 +1538,7 @@ int nori_hip_render_to_error(nori_hip_ctx *ctx, const nori_render_params *params
         total.n_node_tests += st.n_node_tests; total.n_tri_tests += st.n_tri_tests; total.n_invalid += st.n_invalid;
         total.kernel_ms += st.kernel_ms; total.trace_ms += st.trace_ms; total.shade_ms += st.shade_ms; total.film_ms += st.film_ms; total.tail_ms += st.tail_ms;
         total.n_workgroups += st.n_workgroups; total.n_trace_launches += st.n_trace_launches;
-        total.lds_bytes = st.lds_bytes; total.engine = st.engine; total.trace_cus = st.trace_cus; total.tail_cus = st.tail_cus;
+        total.lds_bytes = st.lds_bytes; total.engine = st.engine; total.trace_cus = st.trace_cus; total.tail_cus = st.tail_cus; total.wf_record = st.wf_record;
         done += p.spp_count; ++passes;
         evaluated = false;
         if (passes >= 2) {      /* (one pass of few samples has no variance to speak of) */
@@ -1612,7 +1612,7 @@ static void add_stats(nori_render_stats &total, const nori_render_stats &st) {
     total.n_node_tests += st.n_node_tests; total.n_tri_tests += st.n_tri_tests; total.n_invalid += st.n_invalid;
     total.kernel_ms += st.kernel_ms; total.trace_ms += st.trace_ms; total.shade_ms += st.shade_ms; total.film_ms += st.film_ms; total.tail_ms += st.tail_ms;
     total.n_workgroups += st.n_workgroups; total.n_trace_launches += st.n_trace_launches;
-    total.lds_bytes = st.lds_bytes; total.engine = st.engine; total.trace_cus = st.trace_cus; total.tail_cus = st.tail_cus;
+    total.lds_bytes = st.lds_bytes; total.engine = st.engine; total.trace_cus = st.trace_cus; total.tail_cus = st.tail_cus; total.wf_record = st.wf_record;
 }
 
 int nori_hip_render_tiles(nori_hip_ctx *ctx, const nori_render_params *params, const uint32_t *tiles, uint32_t n_tiles,

@@ -43,6 +43,25 @@ NORI_HD void rng_advance(Rng &r, uint64_t delta) {
     }
     r.state = acc_mult * r.state + acc_plus;
 }
+/* The state of a seeded stream after n draws, without drawing: the LCG is affine, so with (A, G) = (a^n, (a^n - 1) / (a - 1)) --
+   what rng_advance accumulates for delta = n and an increment of 1 -- state_n = A * state_0 + inc * G, and rng_seed leaves
+   state_0 = (inc + initstate) * a + inc.  (A, G) depends on n alone: one pair serves every stream (wf_records.h: paths whose draw
+   count follows from their depth keep no state). */
+struct RngSkip { uint64_t A, G; };
+NORI_HD RngSkip rng_skip_pair(uint64_t n) {
+    uint64_t cur_mult = 0x5851f42d4c957f2dULL, cur_plus = 1u;
+    RngSkip k; k.A = 1u; k.G = 0u;
+    while (n > 0) {
+        if (n & 1u) { k.A *= cur_mult; k.G = k.G * cur_mult + cur_plus; }
+        cur_plus = (cur_mult + 1u) * cur_plus;
+        cur_mult *= cur_mult;
+        n >>= 1u;
+    }
+    return k;
+}
+NORI_HD uint64_t rng_state_derived(uint64_t initstate, uint64_t inc, uint64_t A, uint64_t G) {
+    return A * ((inc + initstate) * 0x5851f42d4c957f2dULL + inc) + inc * G;
+}
 /* Independent::next1D -> pcg32::nextFloat: [0,1) from the top 23 bits */
 NORI_HD float rng_next_float(Rng &r) {
     return u2f((rng_next_uint(r) >> 9) | 0x3f800000u) - 1.0f;

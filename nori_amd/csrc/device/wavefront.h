@@ -35,6 +35,7 @@ struct WfStats {
     uint32_t class_launches[4] = {0, 0, 0, 0};
     uint32_t trace_cus = 0;                      /* CUs wf_extend's stream owned (fewer than the device has: shading, or the tails of earlier batches, ran beside it) */
     uint32_t tail_cus = 0;                       /* CUs set aside for the tails of the batches (0: tails run on the bulk's stream) */
+    uint32_t record = 0;                         /* NORI_WF_RECORD_*: the path record this call's kernels used (wf_records.h) */
 };
 
 /* The engine's per-context resources (path-state pool, pipe streams / events, device properties);

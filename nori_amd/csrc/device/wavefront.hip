@@ -711,243 +711,63 @@ template <> struct ShadeTab<true> { typedef LdsTables type; static __device__ __
 #ifndef NORI_SHADE_WGS
 #define NORI_SHADE_WGS 4      /* workgroups per SIMD wf_shade is compiled for (variant builds: 5, 6) */
 #endif
-template <int INTEG, int MODE, bool LDSTAB, int MATSET>
-__global__ __launch_bounds__(kSB, NORI_SHADE_WGS) void wf_shade(DevScene sc, WfBuf b, int cur, WfBatch bt) {
-    NORI_LAB_SHADE_PAD
-    const WfState S = b.st[cur], D = b.st[cur ^ 1];
-    const uint32_t s_first = bt.s_first, n_spp = bt.n_spp;
-    __shared__ uint4 s_tab[LDSTAB ? kShadeTabWords / 4 : 1];
-    const typename ShadeTab<LDSTAB>::type tab = ShadeTab<LDSTAB>::make(sc, s_tab);      /* mesh / emitter tables: LDS instead of L2 round trips */
-    constexpr bool kFresh = MODE != kStoredOnly, kStored = MODE != kFreshOnly;
-    const PassShape shape = pass_shape<MODE>(b.ctr, cur, bt);      /* the pass wf_extend just traced: the same counters */
-    const uint32_t n = shape.n, n_s = shape.n_s;
-    const uint32_t rounds_total = (n + kSB - 1) / kSB;
-    const uint32_t rounds_per_block = (rounds_total + gridDim.x - 1) / gridDim.x;
-    const uint32_t r0 = blockIdx.x * rounds_per_block, r1 = min(rounds_total, r0 + rounds_per_block);
-    /* rounds below r_mid hold stored paths, rounds from r_mid on new ones (pass_shape: the new paths start at a multiple of kSB) */
-    const uint32_t r_mid = kStored ? min(r1, max(r0, shape.n_f0 / kSB)) : r0;
-    __shared__ uint32_t s_wcnt[2][4], s_newbase;
-    uint32_t out_base = 0u, out_used = 0u, out_len = 0u;     /* workgroup-uniform */
-    bool overflow = false;
-    const int wave = (int) (threadIdx.x >> 6), lane = lane_id();
-    const uint32_t per_tile = 256u * n_spp;
-    uint32_t pf_sidx = 0u; f4 pf_d, pf_L, pf_h;
-    pf_d.x = pf_d.y = pf_d.z = pf_d.w = 0.0f; pf_L = pf_h = pf_d;
-    /* One round: 256 paths, one vertex each.  FRESH rounds hold new paths -- camera sample s0 + (i - n_f0), nothing stored: the
-       first vertex is recomputed from the sample index --, the others stored ones, whose record head was requested a round ahead.
-       Two instantiations in two loops (a workgroup's range of rounds is stored rounds, then new ones): in ONE loop body the
-       camera code and the prefetched head compete for registers and the kernel spills. */
-    auto round = [&](auto fresh_tag, uint32_t r, uint32_t r_end) {
-        constexpr bool FRESH = decltype(fresh_tag)::value;
-        const uint32_t i = r * kSB + threadIdx.x;
-        bool survive = false;
-        const uint32_t c_sidx = pf_sidx; const f4 c_d = pf_d, c_L = pf_L, c_h = pf_h;
-        if (!FRESH && r + 1u < r_end && i + kSB < n_s) {
-            pf_d = ld_f4<2>(&S.dA[i + kSB]); pf_sidx = ld_w<2>(&S.sidx[i + kSB]); pf_L = ld_f4<2>(&S.L_pdf[i + kSB]); pf_h = ld_f4<1>(&b.hit[i + kSB]);
-        }
-        f4 n_o, n_dA, n_dB, n_T, n_L, n_Ld;
-        uint32_t n_fl = 0u, sidx = 0u;
-        unsigned long long n_rng = 0ull;
-        if (FRESH ? i < n : i < n_s) {
-            /* the path's state: from HBM, or -- first vertex -- recomputed from the sample index */
-            uint32_t fl; f4 L4, d4, t4; Rng rng0; rng0.state = 0; rng0.inc = 0;
-            if (FRESH) {
-                f2 ps; RayIn cam;
-                sidx = shape.s0 + (i - shape.n_f0);
-                fl = first_vertex(sc, bt, sidx, ps, cam, rng0) ? (F_HAS_A | (2u << 4)) : 0u;      /* prev_measure = discrete, depth 0 */
-                L4.x = L4.y = L4.z = L4.w = 0.0f;                  /* L = 0, pdf_mat = 0 */
-                t4.x = t4.y = t4.z = t4.w = 1.0f;                  /* T = 1, eta = 1 */
-                d4.x = cam.d.x; d4.y = cam.d.y; d4.z = cam.d.z; d4.w = 0.0f;
-            } else {
-                d4 = c_d;               /* the continuation direction and, in its w, the flags (wf_records.h) */
-                fl = state_flags(d4);
-            }
-            if (fl & (F_HAS_A | F_HAS_B)) {
-                if (!FRESH) { sidx = c_sidx; L4 = c_L; }
-                const f4 h = FRESH ? ld_f4<1>(&b.hit[i]) : c_h;
-                const uint32_t hw = __float_as_uint(h.w);
-                bool done = false;
-                NORI_LAB_SHADE_VERTEX
-                if (fl & F_HAS_B) {                       /* path_on_shadow: add the emitter sample if unoccluded */
-                    if (!(hw & kOccludedB)) {
-                        const P3 ld = ld_p3<2>(&S.Ld[i]);
-                        L4.x = L4.x + ld.x; L4.y = L4.y + ld.y; L4.z = L4.z + ld.z;
-                    }
-                    if (fl & F_END_AFTER_B) done = true;
-                }
-                PathState st;
-                st.L = mk3(L4.x, L4.y, L4.z);
-                if (!done) {
-                    if (!FRESH) t4 = ld_f4<2>(&S.T_eta[i]);
-                    Hit hit; bool found;
-                    hit_unpack(sc, h, hit, found);
-                    /* pcg32 stream of this camera sample: inc from the sample index, state from HBM */
-                    const uint32_t sl = (sidx % per_tile) >> 8;
-                    uint64_t rng_state = rng0.state;
-                    if (!FRESH) rng_state = ld_w<2>(&S.rng[i]);
-                    vertex_unpack(st, fl, L4, t4, rng_state, ((uint64_t) (s_first + sl) << 1u) | 1u);
-                    done = path_on_closest<INTEG, typename ShadeTab<LDSTAB>::type, MATSET>(sc, tab, st, hit, found, mk3(d4.x, d4.y, d4.z));
-                    if (!done) {
-                        survive = true;
-                        vertex_pack(st, n_o, n_dA, n_dB, n_T, n_L, n_Ld, n_fl);
-                        n_rng = st.rng.state;
-                    }
-                }
-                if (done) {
-                    P3 out; out.x = st.L.x; out.y = st.L.y; out.z = st.L.z;
-                    st_p3<2>(&b.samp_L[sidx], out);
-                }
-            }
-        }
-        /* compaction: rank of this survivor among the workgroup's survivors of the round */
-        const unsigned long long mask = __ballot(survive);
-        if (lane == 0) s_wcnt[r & 1u][wave] = (uint32_t) __popcll(mask);
-        shade_barrier();
-        const uint32_t c0 = s_wcnt[r & 1u][0], c1 = kSB > 64 ? s_wcnt[r & 1u][1] : 0u, c2 = kSB > 128 ? s_wcnt[r & 1u][2] : 0u, c3 = kSB > 192 ? s_wcnt[r & 1u][3] : 0u;
-        const uint32_t c = c0 + c1 + c2 + c3;
-        uint32_t off = (uint32_t) __popcll(mask & ((1ull << lane) - 1ull));
-        off += wave > 0 ? c0 : 0u; off += wave > 1 ? c1 : 0u; off += wave > 2 ? c2 : 0u;
-        /* the round's survivors fill what is left of the current chunk, the rest opens a new one */
-        const uint32_t room = out_len - out_used;
-        uint32_t new_base = 0u, want = 0u;
-        if (c > room) {                                  /* workgroup-uniform: reserve the next chunk */
-            const uint32_t expect = c * (r1 - r);        /* survivors from here to the end of the range, at this round's rate */
-            want = r + 1u == r1 ? c - room : min(kShadeChunk, max(c - room, ((expect + expect / 8u + 63u) & ~63u) - min(room, expect)));
-            if (threadIdx.x == 0) s_newbase = atomicAdd(&b.ctr[C_N + (cur ^ 1)], want);
-            shade_barrier();
-            new_base = s_newbase;
-            if (new_base + want > b.capacity) overflow = true;
-        }
-        if (survive && !overflow) {
-            /* the record as it lies in HBM (wf_records.h): 100 B; the flags ride with the continuation direction, which is
-               therefore always written */
-            const uint32_t j = off < room ? out_base + out_used + off : new_base + (off - room);
-            st_p3<2>(&D.o[j], p3_of(n_o)); st_f4<2>(&D.T_eta[j], n_T); st_f4<2>(&D.L_pdf[j], n_L);
-            st_f4<2>(&D.dA[j], state_dA(n_dA, n_fl, (n_fl & F_HAS_A) != 0u)); st_w<2>(&D.rng[j], n_rng); st_w<2>(&D.sidx[j], sidx);
-            if (n_fl & F_HAS_B) { st_f4<2>(&D.dB[j], n_dB); st_p3<2>(&D.Ld[j], p3_of(n_Ld)); }
-            NORI_LAB_SHADE_STORE
-        }
-        if (c > room) { out_base = new_base; out_used = c - room; out_len = want; }
-        else out_used += c;
-    };
-    if (kStored) {
-        if (r0 < r_mid && r0 * kSB + threadIdx.x < n_s) {
-            const uint32_t i0 = r0 * kSB + threadIdx.x;
-            pf_d = ld_f4<2>(&S.dA[i0]); pf_sidx = ld_w<2>(&S.sidx[i0]); pf_L = ld_f4<2>(&S.L_pdf[i0]); pf_h = ld_f4<1>(&b.hit[i0]);
-        }
-        for (uint32_t r = r0; r < r_mid; ++r) round(std::false_type(), r, r_mid);
+/* COMPACT: the compact record of all-diffuse scenes (wf_records.h).  How much of it the kernels use is a build constant, so that each
+   step can be measured alone (variant builds): 1 = the pcg32 state is derived, 2 = and no eta: (T, pdf_mat) quad, 12-B L, 3 = and Lsum
+   in the place of Ld.  The steps are cumulative. */
+#ifndef NORI_WF_COMPACT_LEVEL
+#define NORI_WF_COMPACT_LEVEL 3
+#endif
+static_assert(NORI_WF_COMPACT_LEVEL >= 1 && NORI_WF_COMPACT_LEVEL <= 3, "NORI_WF_COMPACT_LEVEL: 1, 2 or 3");
+/* (A_n, G_n) of rng_skip_pair for the draw counts of depths below this, in LDS, filled once per workgroup.  The headline's batches
+   reach wf_finish after twelve passes, so wf_shade sees depths up to ~12 there; 32 entries are 512 B, which leaves the workgroups per
+   CU as they are.  A deeper path (and every path wf_finish takes) runs rng_skip_pair's loop itself. */
+constexpr uint32_t kSkipDepths = 32u;
+typedef __attribute__((address_space(3))) const unsigned long long *lds_u64_t;
+template <int INTEG> __device__ __forceinline__ void skip_table_fill(unsigned long long *s_skip) {
+    if (threadIdx.x < kSkipDepths) {
+        const RngSkip k = rng_skip_pair(path_draws_diffuse<INTEG>(threadIdx.x));
+        s_skip[2u * threadIdx.x] = k.A; s_skip[2u * threadIdx.x + 1u] = k.G;
     }
-    if (kFresh) for (uint32_t r = r_mid; r < r1; ++r) round(std::true_type(), r, r1);
-    /* what is left of the last chunk holds no path: flags 0 */
-    for (uint32_t k = out_used + threadIdx.x; k < out_len; k += kSB) { f4 z; z.x = z.y = z.z = z.w = 0.0f; D.dA[out_base + k] = z; }
-    if (overflow && threadIdx.x == 0) b.ctr[C_OVERFLOW] = 1u;
+    __syncthreads();
 }
-
-/* The long tail of a batch: once only a few thousand paths are alive, every wf_extend / wf_shade pair
-   is a launch that lasts as long as ONE path vertex takes (~0.1 ms) however few paths there are.
-   wf_finish ends it with one launch: each lane takes a path and walks it to its end -- shadow ray,
-   continuation ray, Li vertex, repeat -- the megakernel's loop started from stored path state.
-   (On a device of its own the launch lasts as long as the LONGEST path, ~1300 vertices through glass at p = 0.99, one after the
-   other, however its lanes are used: a kernel that re-compacts a workgroup's paths after every vertex keeps the lanes dense and
-   is no faster, profiles/r4_04_tail_per_vertex_ab.txt.  Nor does walking through
-   the LDS image of the hot records help here -- pa5 table, 64 spp: 44.9 against 42.0 ms of shade time, a 1/8 share of the Cornell
-   box 3.99 against 3.56: 2048 workgroups each copy 12 KB for a few hundred paths, and the C++ form of the 32-B node step pays 24
-   instructions per step for the ray's plane coefficients.  Round 6, on the small persistent grid, through the image of the 64-B nodes:
-   bit-identical and no faster either -- a path inside the glass sphere walks the BOTTOM of the tree --, profiles/r6_06_finish_image_ab.txt.) */
-/* The lanes of a small persistent grid pull paths one by one -- a lane whose path has ended takes the next unclaimed one at the top
-   of the vertex loop (one atomic per wave and refill), so a wave's lanes stay busy while paths are left and all of them are at the
-   same stage of a vertex.  (Round 4's form -- one lane per path, a grid of finish_paths lanes -- ran at 6.5 of 64 lanes: pa5 table
-   scene 22 -> 19 ms per tail on all CUs, 223 -> 80 ms on 16 CUs, where the tail of a batch runs when the NEXT batch runs beside it:
-   what it costs there is CU time, not the length of the longest path.  profiles/r5_06_tail_probe_c4.txt.)  Same arithmetic per
-   path, hence the same radiance; which lane walks a path is not observable. */
-template <int INTEG, int MATSET = kAnyBsdf>      /* kAnyBsdf | kTextured: scenes with textured albedos (rt_path.h) */
-__global__ __launch_bounds__(kB) void wf_finish(DevScene sc, WfBuf b, int cur, WfBatch bt, int count) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    LdsStackW<16, true> stack;
-    stack.init(smem, b.stack_spill, gridDim.x * kB);
-    __shared__ uint4 s_tab[kShadeTabWords / 4];
-    shade_tables_to_lds(sc, s_tab);
-    const WfState S = b.st[cur];
-    const uint32_t n = b.ctr[C_N + cur];
+/* The pcg32 state of the stored path of camera sample `sidx` at `depth` (compact record): the sample index is split as first_vertex
+   splits it -- tile ordinal, sample in the pixel, pixel in the tile -- which gives the stream's seed; the depth gives the draws.
+   s_skip: the workgroup's table, or null (the loop for every depth). */
+template <int INTEG> __device__ __forceinline__ uint64_t derived_rng_state(const DevScene &sc, const WfBatch &bt, uint32_t sidx, uint32_t depth, const unsigned long long *s_skip) {
     const uint32_t per_tile = 256u * bt.n_spp;
-    uint32_t nClosest = 0, nShadow = 0;
-    TraversalCounters tc; tc.nodes = 0; tc.tris = 0;
-    bool have = false, dry = false;      /* this lane walks a path / the paths have run out */
-    uint32_t sidx = 0u, fl = 0u;
-    f4 o, dA, dB, T, L, Ld;
-    o.x = o.y = o.z = o.w = 0.0f; dA = dB = T = L = Ld = o;
-    unsigned long long rng_state = 0ull;
-    while (true) {
-        const unsigned long long want = __ballot(!have && !dry);
-        if (want != 0ull) {
-            uint32_t base = 0u;
-            if (lane_id() == 0) base = atomicAdd(&b.ctr[C_TAIL_HEAD], (uint32_t) __popcll(want));
-            base = (uint32_t) __builtin_amdgcn_readfirstlane((int) base);
-            const uint32_t i = base + __builtin_amdgcn_mbcnt_hi((uint32_t) (want >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) want, 0u));
-            if (!have && !dry) {
-                if (i >= n) dry = true;
-                else {
-                    dA = S.dA[i];
-                    fl = state_flags(dA);
-                    if (fl & (F_HAS_A | F_HAS_B)) {      /* (else: an empty slot -- the lane asks again in the next trip) */
-                        have = true;
-                        sidx = S.sidx[i]; dB = S.dB[i]; T = S.T_eta[i]; L = S.L_pdf[i];
-                        const P3 o3 = S.o[i], l3 = S.Ld[i];
-                        o.x = o3.x; o.y = o3.y; o.z = o3.z; o.w = kStoredMint; Ld.x = l3.x; Ld.y = l3.y; Ld.z = l3.z; Ld.w = 0.0f;
-                        dA.w = kInf;
-                        rng_state = S.rng[i];
-                    }
-                }
-            }
-        }
-        if (__ballot(have) == 0ull) { if (__ballot(!dry) == 0ull) break; continue; }
-        if (have) {      /* one vertex */
-            bool fin = false;
-            if (fl & F_HAS_B) {
-                RayIn ray; ray.o = mk3(o.x, o.y, o.z); ray.d = mk3(dB.x, dB.y, dB.z); ray.mint = kEpsilon; ray.maxt = dB.w;
-                Hit sh; ++nShadow;
-                if (!traverse<true>(sc, ray, true, stack, sh, tc)) { L.x = L.x + Ld.x; L.y = L.y + Ld.y; L.z = L.z + Ld.z; }
-                fin = (fl & F_END_AFTER_B) != 0u;
-            }
-            if (!fin) {
-                RayIn ray; ray.o = mk3(o.x, o.y, o.z); ray.d = mk3(dA.x, dA.y, dA.z); ray.mint = o.w; ray.maxt = dA.w;
-                Hit hit; ++nClosest;
-                const bool found = traverse<true>(sc, ray, false, stack, hit, tc);
-                if (found) hit.mesh = f2u(sc.shade_tris[(size_t) hit.tri * kShadeQuads].w);
-                PathState st;
-                vertex_unpack(st, fl, L, T, rng_state, ((uint64_t) (bt.s_first + ((sidx % per_tile) >> 8)) << 1u) | 1u);
-                fin = path_on_closest<INTEG, MATSET>(sc, st, hit, found, ray.d);
-                L.x = st.L.x; L.y = st.L.y; L.z = st.L.z;
-                if (!fin) { vertex_pack(st, o, dA, dB, T, L, Ld, fl); rng_state = st.rng.state; }
-            }
-            if (fin) { P3 out; out.x = L.x; out.y = L.y; out.z = L.z; b.samp_L[sidx] = out; have = false; }
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        nClosest += (uint32_t) __shfl_down((int) nClosest, off);
-        nShadow += (uint32_t) __shfl_down((int) nShadow, off);
-        tc.nodes += (uint32_t) __shfl_down((int) tc.nodes, off); tc.tris += (uint32_t) __shfl_down((int) tc.tris, off);
-    }
-    /* one atomic per workgroup and counter (as wf_extend) */
-    __shared__ uint32_t s_sum[4];
-    __syncthreads();
-    if (threadIdx.x < 4u) s_sum[threadIdx.x] = 0u;
-    __syncthreads();
-    if (lane_id() == 0) {
-        if (nClosest) atomicAdd(&s_sum[0], nClosest);
-        if (nShadow) atomicAdd(&s_sum[1], nShadow);
-        if (count) { atomicAdd(&s_sum[2], tc.nodes); atomicAdd(&s_sum[3], tc.tris); }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (s_sum[0]) atomicAdd(&b.stats[S_CLOSEST], (unsigned long long) s_sum[0]);
-        if (s_sum[1]) atomicAdd(&b.stats[S_SHADOW], (unsigned long long) s_sum[1]);
-        if (count) { atomicAdd(&b.stats[S_NODES], (unsigned long long) s_sum[2]); atomicAdd(&b.stats[S_TRIS], (unsigned long long) s_sum[3]); }
-    }
+    const uint32_t tsel = sidx / per_tile, rem = sidx - tsel * per_tile;
+    const uint32_t sl = rem >> 8, pix = rem & 255u;
+    const uint32_t tile_id = bt.tile_list ? bt.tile_list[bt.tile_first + tsel] : bt.tile_rem + (bt.tile_first + tsel) * bt.tile_mod;
+    const int x0 = (int) (tile_id % bt.tiles_x) * kTile, y0 = (int) (tile_id / bt.tiles_x) * kTile;
+    int px, py; film_tile_pixel((int) pix, x0, y0, px, py);
+    RngSkip k;
+    if (s_skip != nullptr && depth < kSkipDepths) {
+        const lds_u64_t t = (lds_u64_t) s_skip;
+        k.A = t[2u * depth]; k.G = t[2u * depth + 1u];
+    } else k = rng_skip_pair(path_draws_diffuse<INTEG>(depth));
+    return rng_state_derived((uint64_t) py * (uint64_t) sc.camera.width + (uint64_t) px, ((uint64_t) (bt.s_first + sl) << 1u) | 1u, k.A, k.G);
 }
+/* wf_shade<INTEG, MODE, LDSTAB, MATSET> and wf_finish<INTEG, MATSET> (the full record), wf_shade_compact and wf_finish_compact (the
+   compact one): the text of wf_path_kernels.h, twice. */
+#define NORI_WF_SHADE_KERNEL wf_shade
+#define NORI_WF_FINISH_KERNEL wf_finish
+#define NORI_WF_KERNELS_COMPACT false
+#include "wf_path_kernels.h"
+#undef NORI_WF_SHADE_KERNEL
+#undef NORI_WF_FINISH_KERNEL
+#undef NORI_WF_KERNELS_COMPACT
+#define NORI_WF_SHADE_KERNEL wf_shade_compact
+#define NORI_WF_FINISH_KERNEL wf_finish_compact
+#define NORI_WF_KERNELS_COMPACT true
+#include "wf_path_kernels.h"
+#undef NORI_WF_SHADE_KERNEL
+#undef NORI_WF_FINISH_KERNEL
+#undef NORI_WF_KERNELS_COMPACT
 
 /* Tail overlap (wavefront_render): the records of a batch's last live paths move out of the state pool -- which the next batch
-   is about to overwrite -- into the engine's side copy, where wf_finish walks them on its own CUs. */
+   is about to overwrite -- into the engine's side copy, where wf_finish walks them on its own CUs.
+   (Compact records, wf_records.h: L lies at a 12-byte stride in the L_pdf allocation -- the first 16 n bytes copied here hold the 12 n
+   in use; the rng array is idle and copied all the same.) */
 __global__ __launch_bounds__(kB) void wf_tail_copy(WfBuf b, int cur, WfState D, uint32_t *d_ctr) {
     const WfState S = b.st[cur];
     const uint32_t n = b.ctr[C_N + cur];
@@ -1065,7 +885,15 @@ void launch_extend_dyn(const DevScene &sc, const WfBuf &b, int cur, int refill, 
 #undef G
 }
 
-void launch_shade(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt, int mode, int grid_, hipStream_t s) {
+/* Which record a render's paths are kept in (wf_records.h): the compact one where the scene is all-diffuse and the integrator one of
+   path_mats / path_ems / path_mis -- the scenes whose wf_shade is the diffuse-only kernel, textured or not; every other scene, and
+   every scene with NORI_HIP_WF_RECORD=full (read once per process), the full one and the kernels of before. */
+bool record_compact(const DevScene &sc) {
+    static const bool full = [] { const char *e = getenv("NORI_HIP_WF_RECORD"); return e && std::string(e) == "full"; }();
+    return !full && sc.integrator.type >= INT_MATS && sc.bsdf_mask == 1u && !getenv("NORI_HIP_SHADE_ANY_BSDF");
+}
+
+void launch_shade(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt, int mode, int grid_, bool compact, hipStream_t s) {
     const dim3 grid(grid_ * (kB / kSB)), block(kSB);
     const bool lds_tables = shade_tables_fit(sc);
     /* the material set the kernel is compiled for: all-diffuse scenes (the Cornell box of the headline), scenes without a
@@ -1079,24 +907,34 @@ void launch_shade(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt
 #define SH2(I, F) if (matset == 1) { SH3(I, F, 1); } else if (matset == 7) { SH3(I, F, 7); } else if (matset == kAnyBsdf) { SH3(I, F, kAnyBsdf); } \
                   else { SH3(I, F, kAnyBsdf | kTextured); }
 #define SH1(I, F) SH3(I, F, kAnyBsdf)
+        /* the compact record: the diffuse-only kernel, or the textured one (which an all-diffuse scene with textures runs) */
+#define SH3C(I, F, M) if (lds_tables) hipLaunchKernelGGL((wf_shade_compact<I, F, true, M>), grid, block, 0, s, sc, b, cur, bt); \
+                      else hipLaunchKernelGGL((wf_shade_compact<I, F, false, M>), grid, block, 0, s, sc, b, cur, bt)
+#define SHC(I, F) if (!compact) { SH2(I, F); } else if (matset == 1) { SH3C(I, F, 1); } else { SH3C(I, F, kAnyBsdf | kTextured); }
 #define SH(I, W) case I: if (mode == kFreshOnly) { W(I, kFreshOnly); } else if (mode == kMixed) { W(I, kMixed); } else { W(I, kStoredOnly); } break;
-        SH(0, SH1) SH(1, SH1) SH(2, SH1) SH(3, SH2) SH(4, SH2) SH(5, SH2) SH(6, SH2)
+        SH(0, SH1) SH(1, SH1) SH(2, SH1) SH(3, SH2) SH(4, SHC) SH(5, SHC) SH(6, SHC)
 #undef SH
+#undef SHC
+#undef SH3C
 #undef SH1
 #undef SH2
 #undef SH3
     }
 }
 
-void launch_finish(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt, bool count, int grid_, hipStream_t s) {
+void launch_finish(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt, bool count, int grid_, bool compact, hipStream_t s) {
     const dim3 grid(grid_), block(kB);
     const size_t lds = (size_t) LdsStackW<16, true>::kLdsEntries * kB * sizeof(int);
     switch (sc.integrator.type) {
 #define FN(I) case I: hipLaunchKernelGGL((wf_finish<I>), grid, block, lds, s, sc, b, cur, bt, (int) count); break;
-#define FNT(I) case I: if (sc.textured) { hipLaunchKernelGGL((wf_finish<I, kAnyBsdf | kTextured>), grid, block, lds, s, sc, b, cur, bt, (int) count); } \
-                       else { hipLaunchKernelGGL((wf_finish<I>), grid, block, lds, s, sc, b, cur, bt, (int) count); } break;
-        FN(0) FN(1) FN(2) FNT(3) FNT(4) FNT(5) FNT(6)
+#define FNT2(I, K) if (sc.textured) { hipLaunchKernelGGL((K<I, kAnyBsdf | kTextured>), grid, block, lds, s, sc, b, cur, bt, (int) count); } \
+                   else { hipLaunchKernelGGL((K<I>), grid, block, lds, s, sc, b, cur, bt, (int) count); }
+#define FNT(I) case I: FNT2(I, wf_finish) break;
+#define FNC(I) case I: if (compact) { FNT2(I, wf_finish_compact) } else { FNT2(I, wf_finish) } break;
+        FN(0) FN(1) FN(2) FNT(3) FNC(4) FNC(5) FNC(6)
+#undef FNC
 #undef FNT
+#undef FNT2
 #undef FN
     }
 }
@@ -1492,6 +1330,8 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
     const int extend_grid_first = extend_cus * (sc.wide ? std::min(per_cu, kExtendWgsWideFirst) : per_cu);
     const int extend_grid = extend_cus * per_cu;
     stats.trace_cus = (uint32_t) extend_cus; stats.tail_cus = (uint32_t) tail_cus;
+    const bool compact = record_compact(sc);
+    stats.record = compact ? NORI_WF_RECORD_COMPACT : NORI_WF_RECORD_FULL;
     if (L.stack_depth > 16) {      /* wf_finish keeps 16 entries in LDS */
         const size_t per_pipe_ints = (size_t) (L.stack_depth - 16) * std::max(extend_grid * extend_block, finish_grid * kB), ints = per_pipe_ints * n_pipes;
         if (g_pool.spill_ints < ints) {
@@ -1589,7 +1429,7 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
                 }
                 if (split) { WF_TRY(hipEventRecord(P.ev_extend, P.extend_stream)); WF_TRY(hipStreamWaitEvent(P.stream, P.ev_extend, 0)); }
                 timer.begin(KC_SHADE, P.stream);
-                launch_shade(sc, P.b, P.cur, P.bt, P.mode, sh_grid, P.stream);
+                launch_shade(sc, P.b, P.cur, P.bt, P.mode, sh_grid, compact, P.stream);
                 timer.end(P.stream);
                 if (split) WF_TRY(hipEventRecord(P.ev_shade, P.stream));
                 /* the first pass started min(pool, samples) camera samples: a batch that fits the pool has none left */
@@ -1637,7 +1477,7 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
                     WfBuf tb = P.b;
                     tb.st[0] = eng.tail.st; tb.ctr = eng.tail.ctr; tb.stack_spill = eng.tail.spill; tb.capacity = (uint32_t) eng.tail.capacity;
                     timer.begin(KC_TAIL, tail_stream);
-                    launch_finish(sc, tb, 0, P.bt, false, finish_grid_side, tail_stream);
+                    launch_finish(sc, tb, 0, P.bt, false, finish_grid_side, compact, tail_stream);
                     timer.end(tail_stream);
                     WF_TRY(hipEventRecord(eng.tail_events[1], tail_stream));
                     pend.active = true; pend.film = P.film;
@@ -1646,7 +1486,7 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
                     stats.n_launches += 2;
                 } else {
                     timer.begin(KC_SHADE, P.stream);
-                    launch_finish(sc, P.b, P.cur, P.bt, L.count_traversal, finish_grid_main, P.stream);
+                    launch_finish(sc, P.b, P.cur, P.bt, L.count_traversal, finish_grid_main, compact, P.stream);
                     timer.end(P.stream);
                     stats.n_launches++;
                 }

@@ -83,4 +83,33 @@ NORI_HD f4 state_dA(const f4 &dA, uint32_t fl, bool has_a) {      /* what is sto
 NORI_HD uint32_t state_flags(const f4 &stored_dA) { return f2u(stored_dA.w); }
 constexpr float kStoredMint = kEpsilon;      /* of every stored ray */
 
+/* ---- the compact record of all-diffuse scenes under path_mats / path_ems / path_mis: 88 B written, 64 / 76 B read.  Three parts of
+   the record above carry nothing there:
+     rng    with only diffuse BSDFs the draws a stored path has consumed follow from its depth (path_on_closest, rt_path.h): 4 for the
+            camera sample; per vertex 2 for bsdf_sample and, under path_ems / path_mis, the 4 sample_direct draws before any early
+            return; 1 for Russian roulette at the vertices of depth >= 3.  The stream is (pixel, sample), which the sample index
+            gives -- so the state is rng_state_derived (rt_sampling.h) and is neither stored nor loaded.
+     eta    is 1.0f for ever: its word of the T quad carries pdf_mat, and L is three floats.
+     Ld     the storing pass writes Lsum = L + Ld in its place -- the three additions path_on_shadow would perform on the same
+            operands -- and the next pass loads ONE of L / Lsum, chosen by the shadow ray's answer.
+   (A record with F_END_AFTER_B keeps the depth of the vertex it was stored at; it draws nothing any more.) */
+template <int INTEG> NORI_HD uint32_t path_draws_diffuse(uint32_t depth) {
+    constexpr uint32_t per_vertex = (INTEG == INT_EMS || INTEG == INT_MIS) ? 6u : 2u;
+    return 4u + depth * per_vertex + (depth > 3u ? depth - 3u : 0u);
+}
+/* T_pdf = (T.xyz, pdf_mat) */
+NORI_HD void vertex_unpack_diffuse(PathState &st, uint32_t fl, const P3 &L, const f4 &T_pdf, uint64_t rng_state, uint64_t rng_inc) {
+    f4 L4; L4.x = L.x; L4.y = L.y; L4.z = L.z; L4.w = T_pdf.w;
+    f4 t4 = T_pdf; t4.w = 1.0f;
+    vertex_unpack(st, fl, L4, t4, rng_state, rng_inc);
+}
+/* Lsum: written only for a record with a shadow ray (F_HAS_B), as vertex_pack's Ld */
+NORI_HD void vertex_pack_diffuse(const PathState &st, f4 &o, f4 &dA, f4 &dB, f4 &T_pdf, P3 &L, P3 &Lsum, uint32_t &fl) {
+    f4 L4, Ld4;
+    vertex_pack(st, o, dA, dB, T_pdf, L4, Ld4, fl);
+    T_pdf.w = L4.w;
+    L = p3_of(L4);
+    if (fl & F_HAS_B) { Lsum.x = L4.x + Ld4.x; Lsum.y = L4.y + Ld4.y; Lsum.z = L4.z + Ld4.z; }
+}
+
 } // namespace nrt
