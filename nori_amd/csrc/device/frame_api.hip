@@ -1,0 +1,465 @@
+/* frame_api.hip -- the frame-level half of the C ABI of include/nori_hip.h: nori_hip_render and what is built on it (moments, error map,
+ * render to an error, tile lists, selection, the adaptive loop, feature frames, the denoiser, block rows) and the _host twins.  No kernel
+ * lives here: every render ends in render_impl (nori_hip.hip), everything else in film.hip / film_tiles.hip / features.hip / denoise.hip. */
+#include <cstring>
+#include <initializer_list>
+#include "ctx.h"      /* (the HIP runtime, <algorithm>, <string>, <vector>) */
+#include "ktimer.h"
+
+#define RC_TRY(expr) do { if (int rc__ = (expr)) return rc__; } while (0)
+
+/* The device side of a _host twin: ONE allocation per call (hipMalloc is slow, and the adaptive CLI path calls these per frame), cut
+   into the parts in order (at most 8) and freed on every return path; call(d) gets their device addresses.  A render ADDS into its
+   frames, so the render twins ask for zero; the twins that upload zero nothing.  The downloads are blocking copies: behind the
+   kernels of the default stream -- a call that queued work on another stream synchronises it itself. */
+struct HostPart { size_t bytes; const void *in; void *out; };      /* in: uploaded before the call, out: downloaded after it; NULL: not */
+template <class Call>
+static int host_twin(nori_hip_ctx *ctx, bool zero, std::initializer_list<HostPart> parts, Call call) {
+    DeviceGuard g(ctx->device);
+    size_t total = 0;
+    for (const HostPart &p : parts) total += p.bytes;
+    Scratch buf;
+    HIP_TRY(ctx, hipMalloc(&buf.p, std::max<size_t>(total, 16)));
+    if (zero) HIP_TRY(ctx, hipMemset(buf.p, 0, total));
+    char *d[8], *at = (char *) buf.p;
+    int n = 0;
+    for (const HostPart &p : parts) { d[n++] = at; if (p.in) HIP_TRY(ctx, hipMemcpy(at, p.in, p.bytes, hipMemcpyHostToDevice)); at += p.bytes; }
+    RC_TRY(call(d));
+    n = 0;
+    for (const HostPart &p : parts) { if (p.out) HIP_TRY(ctx, hipMemcpy(p.out, d[n], p.bytes, hipMemcpyDeviceToHost)); ++n; }
+    return NORI_OK;
+}
+static size_t frame_bytes(const nori_hip_ctx *ctx) { return frame_floats(ctx) * sizeof(float); }
+static size_t pixel_bytes(const nori_hip_ctx *ctx) { return (size_t) ctx->host.camera.width * (size_t) ctx->host.camera.height * sizeof(float); }
+
+extern "C" {
+
+int nori_hip_render(nori_hip_ctx *ctx, const nori_render_params *params, void *d_rgbw, nori_render_stats *stats) {
+    return render_impl(ctx, params, d_rgbw, stats, nullptr);
+}
+
+int nori_hip_render_host(nori_hip_ctx *ctx, const nori_render_params *params, float *rgbw, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;
+    nori_render_stats local;
+    return host_twin(ctx, true, {{frame_bytes(ctx), nullptr, rgbw}}, [&](char **d) { return nori_hip_render(ctx, params, d[0], stats ? stats : &local); });
+}
+
+int nori_hip_render_moments(nori_hip_ctx *ctx, const nori_render_params *params, void *d_rgbw, void *d_m2, nori_render_stats *stats) {
+    if (ctx && (!d_rgbw || !d_m2)) { ctx->error = "render_moments: needs an RGBW frame and a moment frame"; return NORI_ERR_INVALID_ARGUMENT; }
+    return render_impl(ctx, params, d_rgbw, stats, nullptr, (float *) d_m2);
+}
+
+int nori_hip_render_moments_host(nori_hip_ctx *ctx, const nori_render_params *params, float *rgbw, float *m2, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !rgbw || !m2) return NORI_ERR_INVALID_ARGUMENT;
+    nori_render_stats local;
+    const size_t fb = frame_bytes(ctx);
+    return host_twin(ctx, true, {{fb, nullptr, rgbw}, {fb, nullptr, m2}}, [&](char **d) { return nori_hip_render_moments(ctx, params, d[0], d[1], stats ? stats : &local); });
+}
+
+int nori_hip_error_map(nori_hip_ctx *ctx, const void *d_rgbw, const void *d_m2, void *d_err, float threshold, nori_error_summary *out, void *stream) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (!d_rgbw || !d_m2 || (!d_err && !out)) { ctx->error = "error_map: needs both frames and a map or a summary to fill"; return NORI_ERR_INVALID_ARGUMENT; }
+    DeviceGuard g(ctx->device);
+    FilmErrorSummary sum;
+    const std::string err = film_error_map(ctx->moments, ctx->dev, (const float *) d_rgbw, (const float *) d_m2, (float *) d_err, threshold, out ? &sum : nullptr, stream);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        out->sum_err = sum.sum_err; out->max_err = sum.max_err; out->threshold = threshold;
+        out->n_pixels = sum.n_pixels; out->n_empty = sum.n_empty; out->n_above = sum.n_above;
+    }
+    return NORI_OK;
+}
+
+int nori_hip_error_map_host(nori_hip_ctx *ctx, const float *rgbw, const float *m2, float *err, float threshold, nori_error_summary *out) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (!rgbw || !m2 || (!err && !out)) { ctx->error = "error_map: needs both frames and a map or a summary to fill"; return NORI_ERR_INVALID_ARGUMENT; }
+    const size_t fb = frame_bytes(ctx);
+    return host_twin(ctx, false, {{fb, rgbw, nullptr}, {fb, m2, nullptr}, {pixel_bytes(ctx), nullptr, err}},
+                     [&](char **d) { return nori_hip_error_map(ctx, d[0], d[1], err ? d[2] : nullptr, threshold, out, nullptr); });
+}
+
+static void add_stats(nori_render_stats &total, const nori_render_stats &st) {
+    total.n_camera_samples += st.n_camera_samples; total.n_closest_rays += st.n_closest_rays; total.n_shadow_rays += st.n_shadow_rays;
+    total.n_node_tests += st.n_node_tests; total.n_tri_tests += st.n_tri_tests; total.n_invalid += st.n_invalid;
+    total.kernel_ms += st.kernel_ms; total.trace_ms += st.trace_ms; total.shade_ms += st.shade_ms; total.film_ms += st.film_ms; total.tail_ms += st.tail_ms;
+    total.n_workgroups += st.n_workgroups; total.n_trace_launches += st.n_trace_launches;
+    total.lds_bytes = st.lds_bytes; total.engine = st.engine; total.trace_cus = st.trace_cus; total.tail_cus = st.tail_cus; total.wf_record = st.wf_record;
+}
+
+int nori_hip_render_to_error(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_mean_err,
+                             void *d_rgbw, void *d_m2, uint32_t *spp_done, nori_error_summary *last, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !d_rgbw || !d_m2) return NORI_ERR_INVALID_ARGUMENT;
+    if (pass_spp == 0) { ctx->error = "render_to_error: pass_spp must be at least 1"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (!(target_mean_err >= 0.0f)) { ctx->error = "render_to_error: the target error must be a number >= 0"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (params->tile_mod != 1) { ctx->error = "render_to_error: renders whole frames (tile_mod 1): the error of a share says nothing about the frame"; return NORI_ERR_INVALID_ARGUMENT; }
+    nori_render_stats total; memset(&total, 0, sizeof(total));
+    nori_error_summary sum; memset(&sum, 0, sizeof(sum));
+    bool evaluated = false;
+    uint32_t done = 0, passes = 0;
+    while (done < params->spp_count) {
+        nori_render_params p = *params;
+        p.spp_begin = params->spp_begin + done; p.spp_count = std::min(pass_spp, params->spp_count - done);
+        nori_render_stats st;
+        RC_TRY(nori_hip_render_moments(ctx, &p, d_rgbw, d_m2, &st));
+        add_stats(total, st);
+        done += p.spp_count; ++passes;
+        evaluated = false;
+        if (passes >= 2) {      /* (one pass of few samples has no variance to speak of) */
+            RC_TRY(nori_hip_error_map(ctx, d_rgbw, d_m2, nullptr, target_mean_err, &sum, params->stream));
+            evaluated = true;
+            if (sum.sum_err / (double) sum.n_pixels <= (double) target_mean_err) break;
+        }
+    }
+    if (last) {
+        if (!evaluated) RC_TRY(nori_hip_error_map(ctx, d_rgbw, d_m2, nullptr, target_mean_err, &sum, params->stream));
+        *last = sum;
+    }
+    if (spp_done) *spp_done = done;
+    if (stats) *stats = total;
+    return NORI_OK;
+}
+
+/* the error map of the two loops' twins (parts 0, 1, 2 = rgbw, m2, err), if it is asked for: queued on the caller's stream, hence
+   the synchronisation before the blocking copies */
+static int error_map_for_download(nori_hip_ctx *ctx, char **d, bool wanted, float target, void *stream) {
+    if (wanted) { RC_TRY(nori_hip_error_map(ctx, d[0], d[1], d[2], target, nullptr, stream)); HIP_TRY(ctx, hipStreamSynchronize((hipStream_t) stream)); }
+    return NORI_OK;
+}
+
+int nori_hip_render_to_error_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_mean_err,
+                                  float *rgbw, float *m2, float *err, uint32_t *spp_done, nori_error_summary *last, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;
+    const size_t fb = frame_bytes(ctx);
+    return host_twin(ctx, true, {{fb, nullptr, rgbw}, {fb, nullptr, m2}, {pixel_bytes(ctx), nullptr, err}}, [&](char **d) {
+        RC_TRY(nori_hip_render_to_error(ctx, params, pass_spp, target_mean_err, d[0], d[1], spp_done, last, stats));
+        return error_map_for_download(ctx, d, err != nullptr, target_mean_err, params->stream);
+    });
+}
+
+/* ---- tile lists, tile errors, selection, the adaptive loop (film_tiles.h) ---- */
+
+/* a host list: strictly ascending raster ids of tiles of the frame */
+static int check_tile_list(nori_hip_ctx *ctx, const char *what, const uint32_t *tiles, uint32_t n) {
+    const uint32_t n_frame = frame_tiles(ctx);
+    if (n && !tiles) { ctx->error = std::string(what) + ": no tile list"; return NORI_ERR_INVALID_ARGUMENT; }
+    for (uint32_t i = 0; i < n; ++i) {
+        if (tiles[i] >= n_frame) { ctx->error = std::string(what) + ": tile " + std::to_string(tiles[i]) + " (entry " + std::to_string(i) + ") is out of range: the frame has " + std::to_string(n_frame) + " tiles"; return NORI_ERR_INVALID_ARGUMENT; }
+        if (i && tiles[i] <= tiles[i - 1]) { ctx->error = std::string(what) + ": the tile list must be strictly ascending (entry " + std::to_string(i) + ": " + std::to_string(tiles[i]) + " after " + std::to_string(tiles[i - 1]) + ")"; return NORI_ERR_INVALID_ARGUMENT; }
+    }
+    return NORI_OK;
+}
+
+int nori_hip_render_tiles(nori_hip_ctx *ctx, const nori_render_params *params, const uint32_t *tiles, uint32_t n_tiles,
+                          void *d_rgbw, void *d_m2, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !d_rgbw) return NORI_ERR_INVALID_ARGUMENT;
+    RC_TRY(check_tiles_params(ctx, params, nullptr));      /* before the list is looked at: an empty list is refused the same way */
+    RC_TRY(check_tile_list(ctx, "render_tiles", tiles, n_tiles));
+    if (n_tiles == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return NORI_OK; }      /* nothing is touched */
+    DeviceGuard g(ctx->device);
+    const std::string err = film_tiles_upload(ctx->tiles, tiles, n_tiles, frame_tiles(ctx), params->stream);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    return render_impl(ctx, params, d_rgbw, stats, nullptr, (float *) d_m2, &ctx->tiles);
+}
+
+int nori_hip_render_tiles_host(nori_hip_ctx *ctx, const nori_render_params *params, const uint32_t *tiles, uint32_t n_tiles,
+                               float *rgbw, float *m2, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;
+    nori_render_stats local;
+    const size_t fb = frame_bytes(ctx);
+    return host_twin(ctx, true, {{fb, nullptr, rgbw}, {fb, nullptr, m2}},
+                     [&](char **d) { return nori_hip_render_tiles(ctx, params, tiles, n_tiles, d[0], m2 ? d[1] : nullptr, stats ? stats : &local); });
+}
+
+int nori_hip_tile_errors(nori_hip_ctx *ctx, const void *d_rgbw, const void *d_m2, void *d_tile_err, void *stream) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (!d_rgbw || !d_m2 || !d_tile_err) { ctx->error = "tile_errors: needs both frames and an array to fill"; return NORI_ERR_INVALID_ARGUMENT; }
+    DeviceGuard g(ctx->device);
+    const std::string err = film_tile_errors(ctx->dev, (const float *) d_rgbw, (const float *) d_m2, (float *) d_tile_err, stream);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    return NORI_OK;
+}
+
+int nori_hip_tile_errors_host(nori_hip_ctx *ctx, const float *rgbw, const float *m2, float *tile_err) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (!rgbw || !m2 || !tile_err) { ctx->error = "tile_errors: needs both frames and an array to fill"; return NORI_ERR_INVALID_ARGUMENT; }
+    const size_t fb = frame_bytes(ctx);
+    return host_twin(ctx, false, {{fb, rgbw, nullptr}, {fb, m2, nullptr}, {(size_t) frame_tiles(ctx) * sizeof(float), nullptr, tile_err}},
+                     [&](char **d) { return nori_hip_tile_errors(ctx, d[0], d[1], d[2], nullptr); });
+}
+
+int nori_hip_select_tiles(nori_hip_ctx *ctx, const void *d_tile_err, float target, const uint32_t *tiles_in, uint32_t n_in,
+                          uint32_t *tiles_out, uint32_t *n_out) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (!d_tile_err || !n_out || (n_in && !tiles_out)) { ctx->error = "select_tiles: needs the tile errors, a list to fill and its length"; return NORI_ERR_INVALID_ARGUMENT; }
+    RC_TRY(check_tile_list(ctx, "select_tiles", tiles_in, n_in));
+    DeviceGuard g(ctx->device);
+    std::string err = film_tiles_upload(ctx->tiles, tiles_in, n_in, frame_tiles(ctx), nullptr);
+    if (err.empty()) err = film_tiles_select(ctx->tiles, (const float *) d_tile_err, target, frame_tiles(ctx), nullptr);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    *n_out = ctx->tiles.n;
+    if (ctx->tiles.n) HIP_TRY(ctx, hipMemcpy(tiles_out, ctx->tiles.list[ctx->tiles.cur], (size_t) ctx->tiles.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return NORI_OK;
+}
+
+int nori_hip_render_adaptive(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_tile_err,
+                             void *d_rgbw, void *d_m2, void *d_tile_spp, nori_adaptive_summary *out, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !d_rgbw || !d_m2) return NORI_ERR_INVALID_ARGUMENT;
+    if (pass_spp == 0) { ctx->error = "render_adaptive: pass_spp must be at least 1"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (!(target_tile_err >= 0.0f)) { ctx->error = "render_adaptive: the target error must be a number >= 0"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (params->tile_mod != 1) { ctx->error = "render_adaptive: renders whole frames (tile_mod 1): the loop shares the tiles out itself"; return NORI_ERR_INVALID_ARGUMENT; }
+    RC_TRY(check_tiles_params(ctx, params, nullptr));
+    DeviceGuard g(ctx->device);
+    hipStream_t s = (hipStream_t) params->stream;
+    FilmTiles &T = ctx->tiles;
+    const uint32_t n_frame = frame_tiles(ctx);
+    {      /* the active set starts as all tiles */
+        std::vector<uint32_t> all(n_frame);
+        for (uint32_t i = 0; i < n_frame; ++i) all[i] = i;
+        const std::string err = film_tiles_upload(T, all.data(), n_frame, n_frame, s);
+        if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    }
+    HIP_TRY(ctx, hipMemsetAsync(T.tile_spp, 0, (size_t) n_frame * sizeof(uint32_t), s));
+    nori_render_stats total; memset(&total, 0, sizeof(total));
+    uint32_t done = 0, passes = 0;
+    bool evaluated = false;
+    while (done < params->spp_count && T.n > 0) {
+        nori_render_params p = *params;
+        p.spp_begin = params->spp_begin + done; p.spp_count = std::min(pass_spp, params->spp_count - done);
+        nori_render_stats st;
+        RC_TRY(render_impl(ctx, &p, d_rgbw, &st, nullptr, (float *) d_m2, &T));
+        add_stats(total, st);
+        film_tiles_add_spp(T, T.tile_spp, p.spp_count, s);
+        done += p.spp_count; ++passes;
+        evaluated = false;
+        if (passes >= 2) {      /* (one pass of few samples has no variance to speak of) */
+            std::string err = film_tile_errors(ctx->dev, (const float *) d_rgbw, (const float *) d_m2, T.tile_err, s);
+            if (err.empty()) err = film_tiles_select(T, T.tile_err, target_tile_err, n_frame, s);
+            if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+            evaluated = true;
+        }
+    }
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        uint32_t n_unconverged = T.n;
+        if (!evaluated) {      /* the samples were spent in one pass: the frames as they are left are measured once, without retiring anything */
+            std::string err = film_tile_errors(ctx->dev, (const float *) d_rgbw, (const float *) d_m2, T.tile_err, s);
+            if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+            std::vector<float> te(n_frame);
+            HIP_TRY(ctx, hipMemcpyAsync(te.data(), T.tile_err, (size_t) n_frame * sizeof(float), hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, hipStreamSynchronize(s));
+            n_unconverged = 0;
+            for (uint32_t i = 0; i < n_frame; ++i) n_unconverged += !(te[i] <= target_tile_err) ? 1u : 0u;
+        }
+        std::vector<uint32_t> spp(n_frame);
+        HIP_TRY(ctx, hipMemcpyAsync(spp.data(), T.tile_spp, (size_t) n_frame * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        out->passes = passes; out->n_tiles = n_frame; out->n_unconverged = n_unconverged;
+        out->spp_min = *std::min_element(spp.begin(), spp.end()); out->spp_max = *std::max_element(spp.begin(), spp.end());
+        RC_TRY(nori_hip_error_map(ctx, d_rgbw, d_m2, nullptr, target_tile_err, &out->frame, params->stream));
+    }
+    if (d_tile_spp) HIP_TRY(ctx, hipMemcpyAsync(d_tile_spp, T.tile_spp, (size_t) n_frame * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    if (stats) *stats = total;
+    return NORI_OK;
+}
+
+int nori_hip_render_adaptive_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_tile_err,
+                                  float *rgbw, float *m2, float *err, uint32_t *tile_spp, nori_adaptive_summary *out, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;
+    const size_t fb = frame_bytes(ctx);
+    return host_twin(ctx, true, {{fb, nullptr, rgbw}, {fb, nullptr, m2}, {pixel_bytes(ctx), nullptr, err}, {(size_t) frame_tiles(ctx) * sizeof(uint32_t), nullptr, tile_spp}}, [&](char **d) {
+        RC_TRY(nori_hip_render_adaptive(ctx, params, pass_spp, target_tile_err, d[0], d[1], d[3], out, stats));
+        return error_map_for_download(ctx, d, err != nullptr, target_tile_err, params->stream);
+    });
+}
+
+/* ---- first-hit feature frames (features.h): one trace for all requested features, then the film once per feature ---- */
+
+int nori_hip_render_features(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t features,
+                             void *d_albedo, void *d_normal, void *d_depth, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params) return NORI_ERR_INVALID_ARGUMENT;
+    void *d_frame[kFeatureCount] = {d_albedo, d_normal, d_depth};
+    if (features == 0u || (features & ~kFeatureAll)) { ctx->error = "render_features: the mask must name at least one of NORI_FEATURE_ALBEDO | NORMAL | DEPTH and nothing else"; return NORI_ERR_INVALID_ARGUMENT; }
+    for (int f = 0; f < kFeatureCount; ++f)
+        if ((features & (1u << f)) && !d_frame[f]) { ctx->error = "render_features: a requested feature has no frame"; return NORI_ERR_INVALID_ARGUMENT; }
+    RC_TRY(check_render_params(ctx, params, nullptr, nullptr, nullptr, true));
+    DeviceGuard g(ctx->device);
+    hipStream_t s = (hipStream_t) params->stream;
+
+    /* the tile / chunk geometry of the megakernel path */
+    const render_plan::TileGeometry geo = render_plan::tile_geometry(ctx->host.camera.width, ctx->host.camera.height, params->tile_mod, params->tile_rem);
+    const int32_t tile_w = render_plan::tile_width(ctx->host.filter.border);
+    const uint32_t need = ctx->bvh.max_depth + 1, spp_count = params->spp_count;
+    unsigned long long n_invalid = 0; uint32_t n_workgroups = 0;
+
+    StatsScope scope{ctx, s, stats != nullptr};
+    RC_TRY(scope.begin());
+    KernelTimer timer(stats && params->time_kernels != 0);
+    if (geo.n_sel_tiles > 0 && spp_count > 0) {
+        /* as the megakernel path of render_impl: a call that produces more samples than the store budget is cut into launches
+           over sample sub-ranges, each followed by its gathers; the accumulators are carried from launch to launch */
+        const uint32_t spp_per_launch = render_plan::spp_per_launch(spp_count, geo.n_sel_tiles, env_film_samples());
+        const size_t n_samples = (size_t) geo.n_sel_tiles * 256 * spp_per_launch;
+        FilmStore film;      /* pos, n_parts and the invalid counter are the film's own; always the fast film (no reference order of a feature frame exists) */
+        std::string ferr = film_prepare(ctx->film, n_samples, geo.n_sel_tiles, tile_w, s, film);
+        if (ferr.empty()) ferr = feature_store_prepare(ctx->features, features, film, n_samples, geo.n_sel_tiles, tile_w, s);
+        if (!ferr.empty()) { ctx->error = ferr; return NORI_ERR_OUT_OF_MEMORY; }
+        FilmLaunch fl = film_launch_for(geo.tiles_x, geo.tiles_y, geo.n_sel_tiles, params->tile_mod, params->tile_rem, tile_w, 0);
+        for (uint32_t sb = 0; sb < spp_count; sb += spp_per_launch) {
+            FeatureLaunch pl;
+            pl.spp_begin = params->spp_begin + sb; pl.spp_count = std::min(spp_per_launch, spp_count - sb);
+            pl.tile_mod = params->tile_mod; pl.tile_rem = params->tile_rem; pl.tiles_x = geo.tiles_x; pl.n_sel_tiles = geo.n_sel_tiles;
+            const render_plan::ChunkPlan chunks = render_plan::plan_chunks(geo.n_sel_tiles, pl.spp_count, env_target_wgs());
+            pl.n_chunks = chunks.n_chunks; pl.chunk_spp = chunks.chunk_spp; pl.mask = features;
+            timer.begin(KC_TRACE, s);
+            const hipError_t e = feature_pass_launch(ctx->dev, pl, need, film, ctx->features, ctx->d_stats, s);
+            timer.end(s);
+            HIP_TRY(ctx, e);
+            fl.n_spp = pl.spp_count;
+            timer.begin(KC_FILM, s);
+            for (int f = 0; f < kFeatureCount; ++f)      /* before the next launch overwrites the store */
+                if (features & (1u << f)) film_gather(ctx->dev, ctx->d_filter, feature_view(film, ctx->features, f), fl, s);
+            timer.end(s);
+            n_workgroups += pl.n_sel_tiles * pl.n_chunks;
+        }
+        timer.begin(KC_FILM, s);
+        for (int f = 0; f < kFeatureCount; ++f)
+            if (features & (1u << f)) film_resolve(ctx->dev, feature_view(film, ctx->features, f), fl, (float *) d_frame[f], s);
+        timer.end(s);
+        HIP_TRY(ctx, hipGetLastError());
+        if (stats) n_invalid = film_invalid_count(film, s);
+    }
+    if (stats) {
+        float ms = 0.0f; unsigned long long h[16];
+        RC_TRY(scope.end(ms, h));
+        memset(stats, 0, sizeof(*stats));
+        stats->n_camera_samples = h[0]; stats->n_closest_rays = h[1]; stats->n_invalid = n_invalid;
+        stats->kernel_ms = ms; stats->engine = 3u; stats->n_workgroups = n_workgroups;
+        float cms[KC_COUNT]; unsigned int cl[KC_COUNT];
+        timer.collect(cms, cl);
+        stats->trace_ms = cms[KC_TRACE]; stats->film_ms = cms[KC_FILM]; stats->n_trace_launches = cl[KC_TRACE];
+        stats->lds_bytes = feature_pass_lds_bytes(need);
+    }
+    return NORI_OK;
+}
+
+int nori_hip_render_features_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t features,
+                                  float *albedo, float *normal, float *depth, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params) return NORI_ERR_INVALID_ARGUMENT;
+    nori_render_stats local;
+    const size_t fb = frame_bytes(ctx);
+    /* (a frame that is absent gets a NULL device pointer; one that is given but not requested comes back as it went) */
+    return host_twin(ctx, true, {{fb, nullptr, (features & 1u) ? albedo : nullptr}, {fb, nullptr, (features & 2u) ? normal : nullptr}, {fb, nullptr, (features & 4u) ? depth : nullptr}}, [&](char **d) {
+        return nori_hip_render_features(ctx, params, features, albedo ? d[0] : nullptr, normal ? d[1] : nullptr, depth ? d[2] : nullptr, stats ? stats : &local);
+    });
+}
+
+/* ---- the denoiser (denoise.h): guide records from the frames, then the NL-means filter over them ---- */
+
+static int denoise_frames_ok(nori_hip_ctx *ctx, const void *rgbw, const void *m2, const void *out, const char *what) {
+    if (!rgbw || !m2 || !out) { ctx->error = std::string(what) + ": needs the RGBW frame, the moment frame and a buffer to fill"; return NORI_ERR_INVALID_ARGUMENT; }
+    return NORI_OK;
+}
+
+/* the launch of step B from the public parameters (NULL: the defaults), or the message of the first one out of range */
+static std::string denoise_plan(const nori_denoise_params *params, DenoiseLaunch &dl) {
+    const nori_denoise_params def = NORI_DENOISE_PARAMS_DEFAULT;
+    const nori_denoise_params p = params ? *params : def;
+    if (p.radius < 1u || p.radius > (uint32_t) kDenoiseMaxRadius) return "denoise: the window radius must be 1 .. 8";
+    if (p.patch > (uint32_t) kDenoiseMaxPatch) return "denoise: the patch radius must be 0 .. 2";
+    if (!(p.k_c > 0.0f)) return "denoise: k_c must be positive";
+    if (!(p.alpha >= 0.0f)) return "denoise: alpha must not be negative";
+    if (!(p.tau_albedo > 0.0f) || !(p.tau_normal > 0.0f) || !(p.tau_cov > 0.0f)) return "denoise: tau_albedo, tau_normal and tau_cov must be positive";
+    if (!(p.k_depth > 0.0f)) return "denoise: k_depth must be positive";
+    dl.radius = (int32_t) p.radius; dl.patch = (int32_t) p.patch;
+    dl.kc2 = p.k_c * p.k_c; dl.alpha = p.alpha;
+    dl.tau_albedo = p.tau_albedo; dl.tau_normal = p.tau_normal;
+    dl.kd2 = p.k_depth * p.k_depth; dl.tau_cov = p.tau_cov;
+    return std::string();
+}
+
+int nori_hip_denoise_guides(nori_hip_ctx *ctx, const void *d_rgbw, const void *d_m2, const void *d_albedo, const void *d_normal,
+                            const void *d_depth, void *d_guides, void *stream) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    RC_TRY(denoise_frames_ok(ctx, d_rgbw, d_m2, d_guides, "denoise_guides"));
+    DeviceGuard g(ctx->device);
+    HIP_TRY(ctx, denoise_guides_launch(ctx->host.camera.width, ctx->host.camera.height, ctx->host.filter.border, (const float *) d_rgbw, (const float *) d_m2,
+                                       (const float *) d_albedo, (const float *) d_normal, (const float *) d_depth, (float *) d_guides, stream));
+    return NORI_OK;
+}
+
+int nori_hip_denoise(nori_hip_ctx *ctx, const nori_denoise_params *params, const void *d_rgbw, const void *d_m2, const void *d_albedo,
+                     const void *d_normal, const void *d_depth, void *d_rgb_out, void *d_wsum, void *stream) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    RC_TRY(denoise_frames_ok(ctx, d_rgbw, d_m2, d_rgb_out, "denoise"));
+    DenoiseLaunch dl;
+    const std::string bad = denoise_plan(params, dl);
+    if (!bad.empty()) { ctx->error = bad; return NORI_ERR_INVALID_ARGUMENT; }
+    dl.width = ctx->host.camera.width; dl.height = ctx->host.camera.height;
+    dl.terms = (d_albedo ? kDenoiseAlbedo : 0u) | (d_normal ? kDenoiseNormal : 0u) | (d_depth ? kDenoiseDepth : 0u);
+    DeviceGuard g(ctx->device);
+    float *d_guides = nullptr;
+    const std::string err = denoise_store_guides(ctx->denoise, stream, (size_t) dl.width * (size_t) dl.height, &d_guides);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_OUT_OF_MEMORY; }
+    HIP_TRY(ctx, denoise_guides_launch(dl.width, dl.height, ctx->host.filter.border, (const float *) d_rgbw, (const float *) d_m2, (const float *) d_albedo,
+                                       (const float *) d_normal, (const float *) d_depth, d_guides, stream));
+    HIP_TRY(ctx, denoise_filter_launch(dl, d_guides, (float *) d_rgb_out, (float *) d_wsum, stream));
+    return NORI_OK;
+}
+
+/* the host twins: parts 0 .. 4 = rgbw, m2, albedo, normal, depth; the frames that are given are uploaded, the others are NULL to the call */
+#define DENOISE_IN {fb, rgbw, nullptr}, {fb, m2, nullptr}, {fb, albedo, nullptr}, {fb, normal, nullptr}, {fb, depth, nullptr}
+#define DENOISE_ARGS d[0], d[1], albedo ? d[2] : nullptr, normal ? d[3] : nullptr, depth ? d[4] : nullptr
+
+int nori_hip_denoise_guides_host(nori_hip_ctx *ctx, const float *rgbw, const float *m2, const float *albedo, const float *normal,
+                                 const float *depth, float *guides) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    RC_TRY(denoise_frames_ok(ctx, rgbw, m2, guides, "denoise_guides"));
+    const size_t fb = frame_bytes(ctx);
+    return host_twin(ctx, false, {DENOISE_IN, {pixel_bytes(ctx) * kGuideFloats, nullptr, guides}}, [&](char **d) { return nori_hip_denoise_guides(ctx, DENOISE_ARGS, d[5], nullptr); });
+}
+
+int nori_hip_denoise_host(nori_hip_ctx *ctx, const nori_denoise_params *params, const float *rgbw, const float *m2, const float *albedo,
+                          const float *normal, const float *depth, float *rgb_out, float *wsum) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    RC_TRY(denoise_frames_ok(ctx, rgbw, m2, rgb_out, "denoise"));
+    const size_t fb = frame_bytes(ctx);
+    return host_twin(ctx, false, {DENOISE_IN, {3 * pixel_bytes(ctx), nullptr, rgb_out}, {pixel_bytes(ctx), nullptr, wsum}},
+                     [&](char **d) { return nori_hip_denoise(ctx, params, DENOISE_ARGS, d[5], wsum ? d[6] : nullptr, nullptr); });
+}
+
+int nori_hip_block_acc_floats(nori_hip_ctx *ctx, size_t *n_floats) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (!n_floats) return NORI_ERR_INVALID_ARGUMENT;
+    *n_floats = film_block_acc_floats(ctx->dev);
+    return NORI_OK;
+}
+
+int nori_hip_render_block_rows(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t row_begin, uint32_t row_count,
+                               void *d_block_acc, nori_render_stats *stats) {
+    FilmBlockRows share;
+    share.row_begin = row_begin; share.row_count = row_count; share.block_acc = (float *) d_block_acc;
+    return render_impl(ctx, params, nullptr, stats, &share);
+}
+
+int nori_hip_resolve_blocks(nori_hip_ctx *ctx, const void *d_block_acc, void *d_rgbw, void *stream) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (!d_block_acc || !d_rgbw) return NORI_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    const std::string err = film_resolve_blocks(ctx->film, ctx->dev, (const float *) d_block_acc, (float *) d_rgbw, (hipStream_t) stream);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    return NORI_OK;
+}
+
+} // extern "C"

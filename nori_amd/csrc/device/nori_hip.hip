@@ -23,29 +23,20 @@
  *                  and for the host-side plugin classes.
  *
  * No MFMA anywhere: there is no dense contraction on this path.
+ *
+ * What lives where:  this unit      the kernels above, context / scene / accel, the batch twins, render_impl and its three engines
+ *                    ctx.h          nori_hip_ctx, HIP_TRY, DeviceGuard, Scratch, the stats scope (this unit and frame_api.hip only)
+ *                    render_plan.h  tile geometry, chunk plan, sample cut, wavefront budget and out-of-memory ladder: plain C++
+ *                    frame_api.hip  nori_hip_render and every frame-level entry point behind it, the _host twins (no kernel)
  */
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <string>
-#include <vector>
 
-#include "../../../include/nori_hip.h"
-#include "film.h"
-#include "film_tiles.h"
-#include "features.h"
-#include "denoise.h"
+#include "ctx.h"      /* (the HIP runtime, <algorithm>, <cstdlib>, <string>, <vector>) */
 #include "ktimer.h"
 #include "shade_tables.h"
 #include "rt_path.h"
-#include "scene_prep.h"
 #include "lbvh.h"
-#include "wavefront.h"
-
-using namespace nrt;
 
 /* ------------------------------------------------------------ LDS stack */
 template <int DEPTH, int STRIDE>
@@ -461,57 +452,7 @@ __global__ void develop_kernel(const float4 *rgbw, float *rgb, int width, int he
 }
 
 /* ---------------------------------------------------------------- context */
-struct nori_hip_ctx {
-    int device = 0;
-    std::string error;
-    bool have_scene = false, have_accel = false;
-    HostScene host;
-    HostBvh bvh;
-    DevScene dev;
-    std::vector<void *> allocs_scene, allocs_accel;
-    float *d_filter = nullptr;
-    const uint32_t *d_tri_mesh = nullptr;
-    unsigned long long *d_stats = nullptr;
-    nori_accel_info info;
-    int stack_depth = 32;
-    uint64_t lbvh_bytes = 0;
-    uint32_t lbvh_refs = 0;      /* references the device builder built the tree over (0: the host built it) */
-    int engine = -1;                /* -1 auto, 0 megakernel, 1 wavefront */
-    int accel_layout = -1;          /* -1 auto (wide from 2^20 triangles), 0 bvh2, 1 bvh4q (wide nodes) */
-    bool film_reference = false;    /* film_order = reference: samples added in the reference's own order (film.h) */
-    /* 216 B of state each (two copies of the 100-B record + the hit record) + 20 B of film, twice when a call has several batches (the
-       sample store's two halves, wavefront.hip "tail overlap"): 2^29 paths = 137 GB of the 288 GB.
-       A batch ends with a tail that lasts as long as its longest path (wf_finish: ~19 ms on the pa5 table scene), so fewer,
-       bigger batches are cheaper: the table scene at 2048^2 x 1024 spp is 8 batches instead of the 16 of 2^28 */
-    size_t wavefront_paths = (size_t) 1 << 29;
-    /* camera samples per batch (0: as many as the pool holds paths -- every batch starts all its samples in its first pass, the
-       fastest schedule: profiles/r6_12_pool_sweep_two_launches.txt): 20 B each in the film's sample store, twice when a call has several
-       batches.  A batch bigger than the pool starts its samples pass by pass in the slots finished paths leave (regeneration,
-       wavefront.hip): the pool bounds the STATE, this bounds the film store.  What it is for: a context short of memory keeps its
-       batches -- hence the bits of its frame -- on a smaller pool (the out-of-memory retry below), and film_order = reference,
-       which needs the frame in ONE batch, runs on any pool */
-    size_t wavefront_samples = 0;
-    /* render-time resources of THIS context (never shared, freed in nori_hip_destroy): the wavefront
-       engine's state pool / streams / events and the film's sample store + tile accumulators */
-    WfEngine *wf = nullptr;
-    FilmStore film;
-    FilmMoments moments;      /* renders that keep second moments, nori_hip_error_map: a second set of tile accumulators, partial sums */
-    FilmTiles tiles;          /* renders by tile list, tile selection, the adaptive loop: lists, inverse table, tile errors (film_tiles.h) */
-    FeatureStore features;    /* nori_hip_render_features: a sample plane and a set of tile accumulators per feature (features.h) */
-    DenoiseStore denoise;     /* nori_hip_denoise: the guide records between its two kernels, a buffer per stream (denoise.h) */
-};
-
 static std::string g_create_error;
-
-#define HIP_TRY(ctx, expr)                                                                         \
-    do {                                                                                           \
-        hipError_t e__ = (expr);                                                                   \
-        if (e__ != hipSuccess) {                                                                   \
-            (ctx)->error = std::string(#expr) + ": " + hipGetErrorString(e__);                     \
-            return e__ == hipErrorOutOfMemory ? NORI_ERR_OUT_OF_MEMORY :                          \
-                   (e__ == hipErrorNoDevice || e__ == hipErrorInvalidDevice) ? NORI_ERR_NO_DEVICE : NORI_ERR_INTERNAL; \
-        }                                                                                          \
-    } while (0)
 
 template <class T>
 static int upload(nori_hip_ctx *ctx, std::vector<void *> &pool, const std::vector<T> &v, const T **out) {
@@ -564,12 +505,6 @@ static void free_pool(std::vector<void *> &pool) {
     for (void *p : pool) (void) hipFree(p);
     pool.clear();
 }
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void) hipSetDevice(dev); }
-    ~DeviceGuard() { if (prev >= 0) (void) hipSetDevice(prev); }
-};
 
 extern "C" {
 
@@ -676,21 +611,19 @@ int nori_hip_build_accel(nori_hip_ctx *ctx, int builder) {
     const bool want_wide = layout == 1 || (layout < 0 && ctx->dev.n_triangles >= (1u << 20));
     if (builder != NORI_ACCEL_HOST_SAH && ctx->dev.n_triangles > 0) {
         LbvhDeviceResult res;
+        auto drop_tree = [&res]() { if (res.d_nodes) (void) hipFree(res.d_nodes); if (res.d_tris) (void) hipFree(res.d_tris); };      /* before a tree is built again */
         uint32_t ploc_radius = builder == NORI_ACCEL_GPU_PLOC ? 8u : 0u;      /* 8, 16, 32 give the same trees within 1 % (tools/builder_probe.py); 8 builds fastest */
         if (const char *e = getenv("NORI_HIP_PLOC_RADIUS")) if (ploc_radius) ploc_radius = (uint32_t) std::min(256, std::max(1, atoi(e)));
         std::string err = build_bvh_lbvh_device(ctx->dev, ctx->d_tri_mesh, res, want_wide, ploc_radius);
         if (err.empty() && res.wide && res.max_depth + 1 > 64) {      /* wide tree needs more stack than the kernels have: BVH2 nodes */
-            if (res.d_nodes) (void) hipFree(res.d_nodes);
-            if (res.d_tris) (void) hipFree(res.d_tris);
+            drop_tree();
             err = build_bvh_lbvh_device(ctx->dev, ctx->d_tri_mesh, res, false, ploc_radius);
         }
         if (err.empty() && ploc_radius && res.max_depth + 1 > 64) {   /* a clustering of near-identical boxes can degenerate into a chain: the radix tree instead */
-            if (res.d_nodes) (void) hipFree(res.d_nodes);
-            if (res.d_tris) (void) hipFree(res.d_tris);
+            drop_tree();
             err = build_bvh_lbvh_device(ctx->dev, ctx->d_tri_mesh, res, want_wide, 0u);
             if (err.empty() && res.wide && res.max_depth + 1 > 64) {
-                if (res.d_nodes) (void) hipFree(res.d_nodes);
-                if (res.d_tris) (void) hipFree(res.d_tris);
+                drop_tree();
                 err = build_bvh_lbvh_device(ctx->dev, ctx->d_tri_mesh, res, false, 0u);
             }
         }
@@ -853,12 +786,6 @@ int nori_hip_border_size(const nori_hip_ctx *ctx) {
     return ctx->host.filter.border;
 }
 
-#define REQUIRE_ACCEL(ctx)                                                                 \
-    do {                                                                                   \
-        if (!(ctx)) return NORI_ERR_INVALID_ARGUMENT;                                      \
-        if (!(ctx)->have_accel) { (ctx)->error = "no acceleration structure built"; return NORI_ERR_NOT_READY; } \
-    } while (0)
-
 static int grid_for(size_t n) { return (int) std::min<size_t>((n + kBlock - 1) / kBlock, 8192); }
 
 int nori_hip_intersect_device(nori_hip_ctx *ctx, const void *d_rays, void *d_its, size_t n, int shadow_ray, void *stream) {
@@ -875,19 +802,6 @@ int nori_hip_intersect_device(nori_hip_ctx *ctx, const void *d_rays, void *d_its
     HIP_TRY(ctx, hipGetLastError());
     return NORI_OK;
 }
-
-/* small RAII device buffer for the host-buffer convenience entry points */
-struct Scratch {
-    void *p = nullptr;
-    ~Scratch() { if (p) (void) hipFree(p); }
-};
-#define SCRATCH_IN(ctx, var, host, bytes)                                           \
-    Scratch var;                                                                    \
-    HIP_TRY(ctx, hipMalloc(&var.p, std::max<size_t>((bytes), 16)));                 \
-    if (host) HIP_TRY(ctx, hipMemcpy(var.p, host, (bytes), hipMemcpyHostToDevice))
-#define SCRATCH_OUT(ctx, var, bytes)                                                \
-    Scratch var;                                                                    \
-    HIP_TRY(ctx, hipMalloc(&var.p, std::max<size_t>((bytes), 16)))
 
 int nori_hip_intersect(nori_hip_ctx *ctx, const nori_ray *rays, nori_intersection *its, size_t n, int shadow_ray) {
     REQUIRE_ACCEL(ctx);
@@ -1018,29 +932,21 @@ int nori_hip_texture_eval(nori_hip_ctx *ctx, uint32_t texture, const float *uv, 
     return NORI_OK;
 }
 
-int nori_hip_warp(nori_hip_ctx *ctx, int warp, float param, const float *sample, size_t n, float *out) {
-    if (!ctx || !sample || !out || warp < 0 || warp > 6) return NORI_ERR_INVALID_ARGUMENT;
+/* Warp::squareTo* (pdf 0: n 2-d samples -> n 3-d points) and their densities (pdf 1: n 3-d points -> n values) */
+static int warp_call(nori_hip_ctx *ctx, int warp, float param, int pdf, const float *in, size_t n, float *out) {
+    if (!ctx || !in || !out || warp < 0 || warp > 6) return NORI_ERR_INVALID_ARGUMENT;
     if (n == 0) return NORI_OK;
     DeviceGuard g(ctx->device);
-    SCRATCH_IN(ctx, din, sample, n * 2 * sizeof(float));
-    SCRATCH_OUT(ctx, dout, n * 3 * sizeof(float));
-    hipLaunchKernelGGL(warp_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, warp, param, 0, (const float *) din.p, n, (float *) dout.p);
+    const size_t out_bytes = n * (pdf ? 1 : 3) * sizeof(float);
+    SCRATCH_IN(ctx, din, in, n * (pdf ? 3 : 2) * sizeof(float));
+    SCRATCH_OUT(ctx, dout, out_bytes);
+    hipLaunchKernelGGL(warp_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, warp, param, pdf, (const float *) din.p, n, (float *) dout.p);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpy(out, dout.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
     return NORI_OK;
 }
-
-int nori_hip_warp_pdf(nori_hip_ctx *ctx, int warp, float param, const float *points, size_t n, float *pdf) {
-    if (!ctx || !points || !pdf || warp < 0 || warp > 6) return NORI_ERR_INVALID_ARGUMENT;
-    if (n == 0) return NORI_OK;
-    DeviceGuard g(ctx->device);
-    SCRATCH_IN(ctx, din, points, n * 3 * sizeof(float));
-    SCRATCH_OUT(ctx, dout, n * sizeof(float));
-    hipLaunchKernelGGL(warp_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, warp, param, 1, (const float *) din.p, n, (float *) dout.p);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpy(pdf, dout.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    return NORI_OK;
-}
+int nori_hip_warp(nori_hip_ctx *ctx, int warp, float param, const float *sample, size_t n, float *out) { return warp_call(ctx, warp, param, 0, sample, n, out); }
+int nori_hip_warp_pdf(nori_hip_ctx *ctx, int warp, float param, const float *points, size_t n, float *pdf) { return warp_call(ctx, warp, param, 1, points, n, pdf); }
 
 int nori_hip_debug_arith(nori_hip_ctx *ctx, int op, const float *a, const float *b, size_t n, float *out) {
     if (!ctx) return NORI_ERR_INVALID_ARGUMENT;
@@ -1127,11 +1033,6 @@ int nori_hip_pcg32_floats_at(nori_hip_ctx *ctx, const uint64_t *seed_state, cons
     return NORI_OK;
 }
 
-static size_t frame_floats(const nori_hip_ctx *ctx) {
-    const int b = ctx->host.filter.border;
-    return (size_t) (ctx->host.camera.width + 2 * b) * (size_t) (ctx->host.camera.height + 2 * b) * 4;
-}
-
 int nori_hip_splat(nori_hip_ctx *ctx, const float *positions, const float *values, size_t n, float *rgbw) {
     if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
     if (!positions || !values || !rgbw) return NORI_ERR_INVALID_ARGUMENT;
@@ -1172,19 +1073,6 @@ static hipError_t launch_render_one(nori_hip_ctx *ctx, const RenderArgs &a, cons
     return hipGetLastError();
 }
 
-/* spp chunking: one workgroup per (tile, chunk of samples); enough workgroups for the dispatcher
-   to balance load (measured best around 16 k), at least 8 spp per chunk */
-static void plan_chunks(RenderArgs &a) {
-    uint32_t target_wgs = 16384;
-    if (const char *e = getenv("NORI_HIP_TARGET_WGS")) target_wgs = (uint32_t) std::max(1, atoi(e));
-    uint32_t n_chunks = 1;
-    if (a.n_sel_tiles > 0 && a.n_sel_tiles < target_wgs) n_chunks = (target_wgs + a.n_sel_tiles - 1) / a.n_sel_tiles;
-    n_chunks = std::max(1u, std::min(n_chunks, std::max(1u, a.spp_count / 8)));
-    a.chunk_spp = (a.spp_count + n_chunks - 1) / std::max(1u, n_chunks);
-    if (a.chunk_spp == 0) a.chunk_spp = 1;
-    a.n_chunks = std::max(1u, (a.spp_count + a.chunk_spp - 1) / a.chunk_spp);
-}
-
 template <int STACK, bool COUNT>
 static hipError_t launch_render(nori_hip_ctx *ctx, const RenderArgs &a, const FilmStore &d_rgbw, hipStream_t s) {
     switch (ctx->dev.integrator.type) {
@@ -1198,13 +1086,21 @@ static hipError_t launch_render(nori_hip_ctx *ctx, const RenderArgs &a, const Fi
     }
 }
 
-/* nori_hip_render, and nori_hip_render_block_rows (share != nullptr: the block rows of a reference-order film; the accumulators
-   of their blocks go to share->block_acc instead of a frame) */
-static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void *d_rgbw, nori_render_stats *stats, const FilmBlockRows *share,
-                       float *d_m2 = nullptr /* nori_hip_render_moments: the same samples' second moments are added here */,
-                       const FilmTiles *tiles = nullptr /* nori_hip_render_tiles: exactly the tiles of its current list */) {
-    REQUIRE_ACCEL(ctx);
-    if (!params || (!d_rgbw && !share)) return NORI_ERR_INVALID_ARGUMENT;
+static void plan_chunks(RenderArgs &a) {
+    const render_plan::ChunkPlan p = render_plan::plan_chunks(a.n_sel_tiles, a.spp_count, env_target_wgs());
+    a.n_chunks = p.n_chunks; a.chunk_spp = p.chunk_spp;
+}
+
+int check_tiles_params(nori_hip_ctx *ctx, const nori_render_params *params, const FilmBlockRows *share) {
+    if (ctx->film_reference || share || params->seed_mode == NORI_SEED_NORI_BLOCK) {
+        ctx->error = "render_tiles: a tile list is rendered by the fast film with NORI_SEED_PER_SAMPLE only (reference order and the block-serial sampler render whole frames)";
+        return NORI_ERR_UNSUPPORTED;
+    }
+    if (params->tile_mod != 1 || params->tile_rem != 0) { ctx->error = "render_tiles: the list names the tiles (tile_mod 1, tile_rem 0)"; return NORI_ERR_INVALID_ARGUMENT; }
+    return NORI_OK;
+}
+
+int check_render_params(nori_hip_ctx *ctx, const nori_render_params *params, const FilmBlockRows *share, const float *d_m2, const FilmTiles *tiles, bool features) {
     if (d_m2 && (ctx->film_reference || share)) {
         ctx->error = "render_moments: second moments are kept by the fast film only (film_order = fast, no block rows)";
         return NORI_ERR_UNSUPPORTED;
@@ -1215,58 +1111,196 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
         return NORI_ERR_INVALID_ARGUMENT;
     }
     if (params->seed_mode != NORI_SEED_PER_SAMPLE && params->seed_mode != NORI_SEED_NORI_BLOCK) { ctx->error = "render: unknown seed_mode"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (features && params->seed_mode == NORI_SEED_NORI_BLOCK) {
+        ctx->error = "render_features: NORI_SEED_PER_SAMPLE only (a block's serial stream depends on the paths the beauty render traced: its camera samples cannot be drawn again without them)";
+        return NORI_ERR_UNSUPPORTED;
+    }
     if (params->seed_mode == NORI_SEED_NORI_BLOCK && (params->tile_mod != 1 || params->spp_begin != 0)) {
         ctx->error = "render: NORI_SEED_NORI_BLOCK renders whole frames from sample 0 (a block's stream is serial: src/independent.cpp:36-41)";
         return NORI_ERR_UNSUPPORTED;
     }
     if (ctx->host.filter.border > 8) { ctx->error = "render: reconstruction filter radius too large for the LDS tile"; return NORI_ERR_UNSUPPORTED; }
+    if (features) return NORI_OK;      /* (always the fast film, whole frames or shares) */
     if (ctx->film_reference && params->tile_mod != 1) { ctx->error = "render: film_order = reference renders whole frames (a block's samples are added consecutively)"; return NORI_ERR_UNSUPPORTED; }
-    if (tiles && (ctx->film_reference || share || params->seed_mode == NORI_SEED_NORI_BLOCK)) {
-        ctx->error = "render_tiles: a tile list is rendered by the fast film with NORI_SEED_PER_SAMPLE only (reference order and the block-serial sampler render whole frames)";
-        return NORI_ERR_UNSUPPORTED;
-    }
-    if (tiles && (params->tile_mod != 1 || params->tile_rem != 0)) { ctx->error = "render_tiles: the list names the tiles (tile_mod 1, tile_rem 0)"; return NORI_ERR_INVALID_ARGUMENT; }
-    DeviceGuard g(ctx->device);
-    hipStream_t s = (hipStream_t) params->stream;
+    return tiles ? check_tiles_params(ctx, params, share) : NORI_OK;
+}
 
-    RenderArgs a;
+/* what render_impl hands its engines: the geometry and samples of the call (a), where the frame and its moments go, the tile list's
+   inverse, stream and timer; an engine leaves its counts here */
+struct RenderCall {
+    const nori_render_params *params; RenderArgs a;
+    void *d_rgbw; float *d_m2; const FilmBlockRows *share; const uint32_t *tile_inverse = nullptr;
+    hipStream_t s; bool stats; KernelTimer *timer;
+    unsigned long long n_invalid = 0; uint32_t n_workgroups = 0; WfStats wst;
+};
+
+/* the end of a render through the film store: the gathers of its launch if they are still to do (the block-serial sampler's one
+   launch), then the frame -- and its moments -- from the accumulators, and the count of the samples the film dropped */
+static int film_finish(nori_hip_ctx *ctx, RenderCall &c, const FilmStore &film, const FilmLaunch &fl, bool gather) {
+    hipStream_t s = c.s;
+    c.timer->begin(KC_FILM, s);
+    if (gather && !ctx->film_reference) film_gather(ctx->dev, ctx->d_filter, film, fl, s);
+    if (gather && c.d_m2) film_gather_moments(ctx->dev, ctx->d_filter, film, ctx->moments, fl, s);
+    if (ctx->film_reference) {
+        std::string rerr = film_reference_order(ctx->film, film, ctx->dev, ctx->d_filter, c.a.spp_count, c.a.tiles_x, c.share, (float *) c.d_rgbw, s);
+        if (!rerr.empty()) { ctx->error = rerr; return NORI_ERR_INTERNAL; }
+    } else film_resolve(ctx->dev, film, fl, (float *) c.d_rgbw, s);
+    if (c.d_m2) film_resolve_moments(ctx->dev, film, ctx->moments, fl, c.d_m2, s);
+    c.timer->end(s);
+    HIP_TRY(ctx, hipGetLastError());
+    if (c.stats) c.n_invalid = film_invalid_count(film, s);
+    return NORI_OK;
+}
+
+/* NORI_SEED_NORI_BLOCK: one lane per 32x32 block, the block's own pcg32 stream (render_block_serial_kernel) */
+static int render_block_serial(nori_hip_ctx *ctx, RenderCall &c) {
+    const RenderArgs &a = c.a; hipStream_t s = c.s; KernelTimer &timer = *c.timer; float *d_m2 = c.d_m2;
+    const size_t n_samples = (size_t) a.n_sel_tiles * 256 * a.spp_count;
+    if (n_samples > ((size_t) 1 << 30)) { ctx->error = "render: NORI_SEED_NORI_BLOCK keeps the whole frame's samples in the film store (limit 2^30)"; return NORI_ERR_UNSUPPORTED; }
+    FilmStore film;
+    std::string ferr = film_prepare(ctx->film, n_samples, a.n_sel_tiles, a.tile_w, s, film);
+    if (ferr.empty() && d_m2) ferr = film_moments_prepare(ctx->moments, film, a.n_sel_tiles, a.tile_w, s);
+    if (!ferr.empty()) { ctx->error = ferr; return NORI_ERR_OUT_OF_MEMORY; }
+    /* (slots of edge-tile pixels outside the image stay unwritten: film_gather never reads them) */
+    const uint32_t bx = (uint32_t) ((ctx->host.camera.width + kNoriBlock - 1) / kNoriBlock), by = (uint32_t) ((ctx->host.camera.height + kNoriBlock - 1) / kNoriBlock);
+    const uint32_t n_blocks = bx * by;
+    const uint32_t need = ctx->bvh.max_depth + 1;
+    timer.begin(KC_TRACE, s);
+    switch (ctx->dev.integrator.type) {
+#define SB2(I, M) if (need <= 32) hipLaunchKernelGGL((render_block_serial_kernel<I, 32, M>), dim3((n_blocks + 63) / 64), dim3(64), 32 * 64 * sizeof(int), s, ctx->dev, bx, n_blocks, a.spp_count, a.tiles_x, film, ctx->d_stats); \
+                      else hipLaunchKernelGGL((render_block_serial_kernel<I, 64, M>), dim3((n_blocks + 63) / 64), dim3(64), 64 * 64 * sizeof(int), s, ctx->dev, bx, n_blocks, a.spp_count, a.tiles_x, film, ctx->d_stats);
+#define SB(I) case I: SB2(I, kAnyBsdf) break;
+#define SBT(I) case I: if (ctx->dev.textured) { SB2(I, kAnyBsdf | kTextured) } else { SB2(I, kAnyBsdf) } break;
+        SB(0) SB(1) SB(2) SBT(3) SBT(4) SBT(5) SBT(6)
+#undef SBT
+#undef SB
+#undef SB2
+    }
+    timer.end(s);
+    HIP_TRY(ctx, hipGetLastError());
+    return film_finish(ctx, c, film, film_launch_for(a.tiles_x, a.tiles_y, a.n_sel_tiles, 1, 0, a.tile_w, a.spp_count), true);
+}
+
+static bool out_of_memory(const std::string &err) { return err.find("out of memory") != std::string::npos; }
+/* the wavefront engine (wavefront.hip): its launch, the sizes of its pool and sample store, the retry with less */
+static int render_wavefront(nori_hip_ctx *ctx, RenderCall &c) {
+    const RenderArgs &a = c.a; hipStream_t s = c.s; float *d_m2 = c.d_m2;
+    WfLaunch wl;
+    wl.spp_begin = a.spp_begin; wl.spp_count = a.spp_count; wl.tile_mod = a.tile_mod; wl.tile_rem = a.tile_rem;
+    wl.tiles_x = a.tiles_x; wl.tiles_y = a.tiles_y; wl.n_sel_tiles = a.n_sel_tiles; wl.tile_w = a.tile_w;
+    const uint32_t need = ctx->bvh.max_depth + 1;
+    wl.stack_depth = (int) need;
+    wl.count_traversal = c.params->count_traversal != 0;
+    wl.time_kernels = c.stats && c.params->time_kernels != 0;
+    wl.film_reference = ctx->film_reference; wl.film_share = c.share;
+    wl.d_m2 = d_m2; wl.moments = d_m2 ? &ctx->moments : nullptr;
+    wl.tile_list = a.tile_list; wl.tile_inverse = c.tile_inverse;
+    /* paths in flight: the option, bounded by what this GPU has free right now (state already held by
+       this context counts as free) -- a second context or another process may own part of the HBM */
+    const size_t call_samples = (size_t) a.n_sel_tiles * 256 * a.spp_count;
+    const size_t per_path = wavefront_bytes_per_path(), per_sample = wavefront_bytes_per_sample();
+    size_t usable = render_plan::kUsableUnknown, free_b = 0, total_b = 0;
+    if (!getenv("NORI_HIP_WF_IGNORE_FREE") /* test hook: as if the free figure were stale */ && hipMemGetInfo(&free_b, &total_b) == hipSuccess)
+        usable = (size_t) ((double) (free_b + wavefront_held_bytes(ctx->wf, ctx->film)) * 0.85);
+    render_plan::WfBudget b = render_plan::wavefront_budget(call_samples, ctx->wavefront_paths, ctx->wavefront_samples, ctx->film_reference, per_path, per_sample, usable);
+    wl.max_paths = b.max_paths; wl.max_samples = b.max_samples;
+    std::string err = wavefront_render(*ctx->wf, ctx->film, ctx->dev, ctx->d_filter, wl, (float *) c.d_rgbw, s, c.wst);
+    /* The free figure above is a snapshot: another context on this device -- a group with a duplicated device list rendering
+       in parallel threads, a second process -- may have claimed the same bytes in the meantime.  Nothing has been accumulated
+       yet when the pool or the sample store cannot be allocated (they are allocated before the first launch), so the call is
+       simply made again with less: what this context holds is given back first (a pool that fitted while the sample store did
+       not must not survive the retry), then the bigger of the two is halved -- the POOL while it is, which leaves the batches,
+       hence the bits of the frame, as they were (render_plan::wavefront_oom_step). */
+    while (!err.empty() && out_of_memory(err)) {
+        (void) hipGetLastError();
+        wavefront_release_pool(ctx->wf);
+        film_release(ctx->film);
+        if (d_m2) film_moments_release(ctx->moments);
+        if (!render_plan::wavefront_oom_step(b, ctx->film_reference, per_path, per_sample)) break;
+        wl.max_paths = b.max_paths; wl.max_samples = b.max_samples;
+        err = wavefront_render(*ctx->wf, ctx->film, ctx->dev, ctx->d_filter, wl, (float *) c.d_rgbw, s, c.wst);
+    }
+    if (!err.empty()) {
+        ctx->error = err;
+        return out_of_memory(err) ? NORI_ERR_OUT_OF_MEMORY : NORI_ERR_INTERNAL;
+    }
+    return NORI_OK;
+}
+
+/* the megakernel (render_kernel).  Samples go to the film store (24 B each); if a call produces more than the store
+   budget it is cut into launches over sample sub-ranges, each followed by its splat. */
+static int render_megakernel(nori_hip_ctx *ctx, RenderCall &c) {
+    const RenderArgs &a = c.a; hipStream_t s = c.s; KernelTimer &timer = *c.timer; float *d_m2 = c.d_m2;
+    const uint32_t spp_per_launch = render_plan::spp_per_launch(a.spp_count, a.n_sel_tiles, env_film_samples());
+    if (ctx->film_reference && spp_per_launch != a.spp_count) { ctx->error = "render: film_order = reference needs all samples of the frame in the film store at once"; return NORI_ERR_UNSUPPORTED; }
+    FilmStore film;
+    std::string ferr = film_prepare(ctx->film, (size_t) a.n_sel_tiles * 256 * spp_per_launch, a.n_sel_tiles, a.tile_w, s, film);
+    if (ferr.empty() && d_m2) ferr = film_moments_prepare(ctx->moments, film, a.n_sel_tiles, a.tile_w, s);
+    if (!ferr.empty()) { ctx->error = ferr; return NORI_ERR_OUT_OF_MEMORY; }
+    FilmLaunch fl = film_launch_for(a.tiles_x, a.tiles_y, a.n_sel_tiles, a.tile_mod, a.tile_rem, a.tile_w, 0, a.tile_list, c.tile_inverse);
+    const bool count = c.params->count_traversal != 0;
+    const uint32_t need = ctx->bvh.max_depth + 1;
+    for (uint32_t sb = 0; sb < a.spp_count; sb += spp_per_launch) {
+        RenderArgs a2 = a;
+        a2.spp_begin = a.spp_begin + sb; a2.spp_count = std::min(spp_per_launch, a.spp_count - sb);
+        plan_chunks(a2);
+        hipError_t e;
+        timer.begin(KC_TRACE, s);
+        /* the LDS stack is sized to the tree: fewer entries -> more workgroups per CU */
+        if (need <= 16) e = count ? launch_render<16, true>(ctx, a2, film, s) : launch_render<16, false>(ctx, a2, film, s);
+        else if (need <= 24) e = count ? launch_render<24, true>(ctx, a2, film, s) : launch_render<24, false>(ctx, a2, film, s);
+        else if (need <= 32) e = count ? launch_render<32, true>(ctx, a2, film, s) : launch_render<32, false>(ctx, a2, film, s);
+        else e = count ? launch_render<64, true>(ctx, a2, film, s) : launch_render<64, false>(ctx, a2, film, s);
+        timer.end(s);
+        HIP_TRY(ctx, e);
+        fl.n_spp = a2.spp_count;
+        timer.begin(KC_FILM, s);
+        if (!(a.debug_flags & 1u) && !ctx->film_reference) film_gather(ctx->dev, ctx->d_filter, film, fl, s);
+        if (d_m2 && !(a.debug_flags & 1u)) film_gather_moments(ctx->dev, ctx->d_filter, film, ctx->moments, fl, s);      /* before the next launch overwrites the store */
+        timer.end(s);
+        c.n_workgroups += a2.n_sel_tiles * a2.n_chunks;
+    }
+    return film_finish(ctx, c, film, fl, false);
+}
+
+/* every render of the frame API (frame_api.hip) ends here: refusals, geometry, the choice of the engine, the stats (ctx.h has the arguments) */
+int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void *d_rgbw, nori_render_stats *stats, const FilmBlockRows *share, float *d_m2,
+                const FilmTiles *tiles) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || (!d_rgbw && !share)) return NORI_ERR_INVALID_ARGUMENT;
+    if (int rc = check_render_params(ctx, params, share, d_m2, tiles)) return rc;
+    DeviceGuard g(ctx->device);
+    RenderCall c;
+    c.params = params; c.d_rgbw = d_rgbw; c.d_m2 = d_m2; c.share = share; c.s = (hipStream_t) params->stream; c.stats = stats != nullptr;
+    hipStream_t s = c.s;
+
+    RenderArgs &a = c.a;
     a.spp_begin = params->spp_begin; a.spp_count = params->spp_count;
     a.tile_mod = params->tile_mod; a.tile_rem = params->tile_rem;
-    a.tiles_x = (uint32_t) ((ctx->host.camera.width + kTile - 1) / kTile);
-    a.tiles_y = (uint32_t) ((ctx->host.camera.height + kTile - 1) / kTile);
-    const uint32_t n_tiles = a.tiles_x * a.tiles_y;
-    a.n_sel_tiles = n_tiles > a.tile_rem ? (n_tiles - a.tile_rem + a.tile_mod - 1) / a.tile_mod : 0;
+    const render_plan::TileGeometry geo = render_plan::tile_geometry(ctx->host.camera.width, ctx->host.camera.height, a.tile_mod, a.tile_rem);
+    a.tiles_x = geo.tiles_x; a.tiles_y = geo.tiles_y; a.n_sel_tiles = geo.n_sel_tiles;
     if (share) {
         /* whole rows of 32x32 blocks = a contiguous range of tiles: tile_id = tile_rem + ordinal * 1 with tile_rem = the range's
            first tile (every kernel derives a tile from its ordinal this way) */
+        const uint32_t n_tiles = a.tiles_x * a.tiles_y;
         const uint32_t byn = (uint32_t) ((ctx->host.camera.height + kNoriBlock - 1) / kNoriBlock);
         const uint32_t row0 = std::min(share->row_begin, byn), row1 = row0 + std::min(share->row_count, byn - row0);
         const uint32_t t0 = std::min(film_block_rows_first_tile(row0, a.tiles_x), n_tiles), t1 = std::min(film_block_rows_first_tile(row1, a.tiles_x), n_tiles);
         a.tile_rem = t0; a.n_sel_tiles = t1 - t0;
     }
-    const uint32_t *tile_inverse = nullptr;
-    if (tiles) { a.n_sel_tiles = tiles->n; a.tile_list = tiles->list[tiles->cur]; tile_inverse = tiles->inverse; }
-    a.tile_w = kTile + 2 * ctx->host.filter.border;
+    if (tiles) { a.n_sel_tiles = tiles->n; a.tile_list = tiles->list[tiles->cur]; c.tile_inverse = tiles->inverse; }
+    a.tile_w = render_plan::tile_width(ctx->host.filter.border);
     a.th_shade = 44; a.th_inner = 1; a.th_leaf = 1;
     a.debug_flags = getenv("NORI_HIP_NOSPLAT") ? 1u : 0u;
     if (const char *e = getenv("NORI_HIP_TH_SHADE")) a.th_shade = (uint32_t) std::min(64, std::max(1, atoi(e)));
     if (const char *e = getenv("NORI_HIP_TH_INNER")) a.th_inner = (uint32_t) std::min(64, std::max(1, atoi(e)));
     if (const char *e = getenv("NORI_HIP_TH_LEAF")) a.th_leaf = (uint32_t) std::min(64, std::max(1, atoi(e)));
     plan_chunks(a);
-    unsigned long long n_invalid = 0; uint32_t n_workgroups = 0;
 
-    struct EventPair {      /* destroyed on every return path */
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EventPair() { if (a) (void) hipEventDestroy(a); if (b) (void) hipEventDestroy(b); }
-    } evp;
-    hipEvent_t &ev0 = evp.a, &ev1 = evp.b;
-    if (stats) {
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_stats, 0, 16 * sizeof(unsigned long long), s));
-        HIP_TRY(ctx, hipEventCreate(&ev0)); HIP_TRY(ctx, hipEventCreate(&ev1));
-        HIP_TRY(ctx, hipEventRecord(ev0, s));
-    }
-    WfStats wst;
+    StatsScope scope{ctx, s, stats != nullptr};
+    if (int rc = scope.begin()) return rc;
     KernelTimer timer(stats && params->time_kernels != 0);
+    c.timer = &timer;
     int engine = ctx->engine;
     if (const char *e = getenv("NORI_HIP_ENGINE")) engine = std::string(e) == "wavefront" ? 1 : (std::string(e) == "megakernel" ? 0 : -1);
     /* auto: the wavefront engine wins once there are enough paths to keep its kernels full; small jobs avoid its launch train.
@@ -1279,172 +1313,27 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
         engine = samples >= ((size_t) 1 << (ctx->dev.integrator.type == 0 ? 24 : 19)) ? 1 : 0;
     }
     if (ctx->dev.wide) engine = 1;      /* wide nodes are walked by the wavefront engine (and the batch twins) only */
-    if (params->seed_mode == NORI_SEED_NORI_BLOCK && a.n_sel_tiles > 0 && a.spp_count > 0) {
-        /* one lane per 32x32 block, the block's own pcg32 stream (render_block_serial_kernel) */
-        const size_t n_samples = (size_t) a.n_sel_tiles * 256 * a.spp_count;
-        if (n_samples > ((size_t) 1 << 30)) { ctx->error = "render: NORI_SEED_NORI_BLOCK keeps the whole frame's samples in the film store (limit 2^30)"; return NORI_ERR_UNSUPPORTED; }
-        FilmStore film;
-        std::string ferr = film_prepare(ctx->film, n_samples, a.n_sel_tiles, a.tile_w, s, film);
-        if (ferr.empty() && d_m2) ferr = film_moments_prepare(ctx->moments, film, a.n_sel_tiles, a.tile_w, s);
-        if (!ferr.empty()) { ctx->error = ferr; return NORI_ERR_OUT_OF_MEMORY; }
-        /* (slots of edge-tile pixels outside the image stay unwritten: film_gather never reads them) */
-        const uint32_t bx = (uint32_t) ((ctx->host.camera.width + kNoriBlock - 1) / kNoriBlock), by = (uint32_t) ((ctx->host.camera.height + kNoriBlock - 1) / kNoriBlock);
-        const uint32_t n_blocks = bx * by;
-        const uint32_t need = ctx->bvh.max_depth + 1;
-        timer.begin(KC_TRACE, s);
-        switch (ctx->dev.integrator.type) {
-#define SB2(I, M) if (need <= 32) hipLaunchKernelGGL((render_block_serial_kernel<I, 32, M>), dim3((n_blocks + 63) / 64), dim3(64), 32 * 64 * sizeof(int), s, ctx->dev, bx, n_blocks, a.spp_count, a.tiles_x, film, ctx->d_stats); \
-                          else hipLaunchKernelGGL((render_block_serial_kernel<I, 64, M>), dim3((n_blocks + 63) / 64), dim3(64), 64 * 64 * sizeof(int), s, ctx->dev, bx, n_blocks, a.spp_count, a.tiles_x, film, ctx->d_stats);
-#define SB(I) case I: SB2(I, kAnyBsdf) break;
-#define SBT(I) case I: if (ctx->dev.textured) { SB2(I, kAnyBsdf | kTextured) } else { SB2(I, kAnyBsdf) } break;
-            SB(0) SB(1) SB(2) SBT(3) SBT(4) SBT(5) SBT(6)
-#undef SBT
-#undef SB
-#undef SB2
-        }
-        timer.end(s);
-        HIP_TRY(ctx, hipGetLastError());
-        FilmLaunch fl;
-        fl.tile_first = 0; fl.store_tile_first = 0; fl.n_tiles = a.n_sel_tiles; fl.tile_mod = 1; fl.tile_rem = 0;
-        fl.tiles_x = a.tiles_x; fl.tiles_y = a.tiles_y; fl.tile_w = a.tile_w; fl.n_spp = a.spp_count;
-        timer.begin(KC_FILM, s);
-        if (ctx->film_reference) {
-            std::string rerr = film_reference_order(ctx->film, film, ctx->dev, ctx->d_filter, a.spp_count, a.tiles_x, nullptr, (float *) d_rgbw, s);
-            if (!rerr.empty()) { ctx->error = rerr; return NORI_ERR_INTERNAL; }
-        } else {
-            film_gather(ctx->dev, ctx->d_filter, film, fl, s);
-            film_resolve(ctx->dev, film, fl, (float *) d_rgbw, s);
-            if (d_m2) {
-                film_gather_moments(ctx->dev, ctx->d_filter, film, ctx->moments, fl, s);
-                film_resolve_moments(ctx->dev, film, ctx->moments, fl, d_m2, s);
-            }
-        }
-        timer.end(s);
-        HIP_TRY(ctx, hipGetLastError());
-        if (stats) n_invalid = film_invalid_count(film, s);
-        engine = 2;      /* stats come from ctx->d_stats like the megakernel's */
-    } else
-    if (engine == 1 && a.n_sel_tiles > 0 && a.spp_count > 0) {
-        WfLaunch wl;
-        wl.spp_begin = a.spp_begin; wl.spp_count = a.spp_count; wl.tile_mod = a.tile_mod; wl.tile_rem = a.tile_rem;
-        wl.tiles_x = a.tiles_x; wl.tiles_y = a.tiles_y; wl.n_sel_tiles = a.n_sel_tiles; wl.tile_w = a.tile_w;
-        const uint32_t need = ctx->bvh.max_depth + 1;
-        wl.stack_depth = (int) need;
-        wl.count_traversal = params->count_traversal != 0;
-        wl.time_kernels = stats && params->time_kernels != 0;
-        /* paths in flight: the option, bounded by what this GPU has free right now (state already held by
-           this context counts as free) -- a second context or another process may own part of the HBM */
-        wl.film_reference = ctx->film_reference; wl.film_share = share;
-        wl.d_m2 = d_m2; wl.moments = d_m2 ? &ctx->moments : nullptr;
-        wl.tile_list = a.tile_list; wl.tile_inverse = tile_inverse;
-        /* what the call can use at all: a batch never holds more samples than the call has, the pool never more paths than a batch */
-        const size_t call_samples = (size_t) a.n_sel_tiles * 256 * a.spp_count;
-        /* (reference film order: the frame is one batch whatever the options say -- the pool need not hold it) */
-        const size_t opt_samples = ctx->film_reference ? call_samples : ctx->wavefront_samples ? ctx->wavefront_samples : ctx->wavefront_paths;
-        wl.max_samples = std::max<size_t>(256, std::min(opt_samples, call_samples));
-        wl.max_paths = std::max<size_t>(256, std::min(ctx->wavefront_paths, wl.max_samples));
-        const size_t per_path = wavefront_bytes_per_path(), per_sample = wavefront_bytes_per_sample();
-        size_t free_b = 0, total_b = 0;
-        if (!getenv("NORI_HIP_WF_IGNORE_FREE") /* test hook: as if the free figure were stale */ && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const size_t usable = (size_t) ((double) (free_b + wavefront_held_bytes(ctx->wf, ctx->film)) * 0.85);
-            if (wl.max_paths * per_path + wl.max_samples * per_sample > usable) {
-                /* reference film order: the batch is the frame, the pool takes what is left.  Else the pool keeps its size while the
-                   sample store can still hold four pools' worth of samples; else both shrink */
-                if (ctx->film_reference) wl.max_paths = std::max<size_t>(256, usable > wl.max_samples * per_sample ? (usable - wl.max_samples * per_sample) / per_path : 0);
-                else if (usable >= wl.max_paths * (per_path + 4 * per_sample)) wl.max_samples = (usable - wl.max_paths * per_path) / per_sample;
-                else { wl.max_paths = std::max<size_t>(256, usable / (per_path + 4 * per_sample)); wl.max_samples = std::min(wl.max_samples, 4 * wl.max_paths); }
-            }
-        }
-        std::string err = wavefront_render(*ctx->wf, ctx->film, ctx->dev, ctx->d_filter, wl, (float *) d_rgbw, s, wst);
-        /* The free figure above is a snapshot: another context on this device -- a group with a duplicated device list rendering
-           in parallel threads, a second process -- may have claimed the same bytes in the meantime.  Nothing has been accumulated
-           yet when the pool or the sample store cannot be allocated (they are allocated before the first launch), so the call is
-           simply made again with less: what this context holds is given back first (a pool that fitted while the sample store did
-           not must not survive the retry), then the bigger of the two is halved -- the POOL while it is, which leaves the batches,
-           hence the bits of the frame, as they were. */
-        while (!err.empty() && err.find("out of memory") != std::string::npos) {
-            (void) hipGetLastError();
-            wavefront_release_pool(ctx->wf);
-            film_release(ctx->film);
-            if (d_m2) film_moments_release(ctx->moments);
-            const bool pool_bigger = wl.max_paths * per_path >= wl.max_samples * per_sample || ctx->film_reference;
-            if (pool_bigger && wl.max_paths > ((size_t) 1 << 20)) wl.max_paths /= 2;
-            else if (ctx->film_reference) break;      /* (its one batch cannot shrink) */
-            else if (wl.max_samples > ((size_t) 1 << 20)) { wl.max_samples /= 2; wl.max_paths = std::min(wl.max_paths, wl.max_samples); }
-            else if (wl.max_paths > ((size_t) 1 << 20)) wl.max_paths /= 2;
-            else break;
-            err = wavefront_render(*ctx->wf, ctx->film, ctx->dev, ctx->d_filter, wl, (float *) d_rgbw, s, wst);
-        }
-        if (!err.empty()) {
-            ctx->error = err;
-            return err.find("out of memory") != std::string::npos ? NORI_ERR_OUT_OF_MEMORY : NORI_ERR_INTERNAL;
-        }
-    } else
-    if (a.n_sel_tiles > 0 && a.spp_count > 0) {
-        /* Samples go to the film store (24 B each); if a call produces more than the store
-           budget it is cut into launches over sample sub-ranges, each followed by its splat. */
-        size_t cap = (size_t) 1 << 29;
-        if (const char *e = getenv("NORI_HIP_FILM_SAMPLES")) cap = (size_t) std::max(256ll, atoll(e));
-        const uint32_t spp_per_launch = (uint32_t) std::max<size_t>(1, std::min<size_t>(a.spp_count, cap / ((size_t) a.n_sel_tiles * 256)));
-        if (ctx->film_reference && spp_per_launch != a.spp_count) { ctx->error = "render: film_order = reference needs all samples of the frame in the film store at once"; return NORI_ERR_UNSUPPORTED; }
-        FilmStore film;
-        std::string ferr = film_prepare(ctx->film, (size_t) a.n_sel_tiles * 256 * spp_per_launch, a.n_sel_tiles, a.tile_w, s, film);
-        if (ferr.empty() && d_m2) ferr = film_moments_prepare(ctx->moments, film, a.n_sel_tiles, a.tile_w, s);
-        if (!ferr.empty()) { ctx->error = ferr; return NORI_ERR_OUT_OF_MEMORY; }
-        FilmLaunch fl;
-        fl.tile_first = 0; fl.store_tile_first = 0; fl.n_tiles = a.n_sel_tiles; fl.tile_mod = a.tile_mod; fl.tile_rem = a.tile_rem;
-        fl.tiles_x = a.tiles_x; fl.tiles_y = a.tiles_y; fl.tile_w = a.tile_w;
-        fl.tile_list = a.tile_list; fl.tile_inverse = tile_inverse;
-        const bool count = params->count_traversal != 0;
-        const uint32_t need = ctx->bvh.max_depth + 1;
-        for (uint32_t sb = 0; sb < a.spp_count; sb += spp_per_launch) {
-            RenderArgs a2 = a;
-            a2.spp_begin = a.spp_begin + sb; a2.spp_count = std::min(spp_per_launch, a.spp_count - sb);
-            plan_chunks(a2);
-            hipError_t e;
-            timer.begin(KC_TRACE, s);
-            /* the LDS stack is sized to the tree: fewer entries -> more workgroups per CU */
-            if (need <= 16) e = count ? launch_render<16, true>(ctx, a2, film, s) : launch_render<16, false>(ctx, a2, film, s);
-            else if (need <= 24) e = count ? launch_render<24, true>(ctx, a2, film, s) : launch_render<24, false>(ctx, a2, film, s);
-            else if (need <= 32) e = count ? launch_render<32, true>(ctx, a2, film, s) : launch_render<32, false>(ctx, a2, film, s);
-            else e = count ? launch_render<64, true>(ctx, a2, film, s) : launch_render<64, false>(ctx, a2, film, s);
-            timer.end(s);
-            HIP_TRY(ctx, e);
-            fl.n_spp = a2.spp_count;
-            timer.begin(KC_FILM, s);
-            if (!(a.debug_flags & 1u) && !ctx->film_reference) film_gather(ctx->dev, ctx->d_filter, film, fl, s);
-            if (d_m2 && !(a.debug_flags & 1u)) film_gather_moments(ctx->dev, ctx->d_filter, film, ctx->moments, fl, s);      /* before the next launch overwrites the store */
-            timer.end(s);
-            n_workgroups += a2.n_sel_tiles * a2.n_chunks;
-        }
-        timer.begin(KC_FILM, s);
-        if (ctx->film_reference) {
-            std::string rerr = film_reference_order(ctx->film, film, ctx->dev, ctx->d_filter, a.spp_count, a.tiles_x, share, (float *) d_rgbw, s);
-            if (!rerr.empty()) { ctx->error = rerr; return NORI_ERR_INTERNAL; }
-        } else film_resolve(ctx->dev, film, fl, (float *) d_rgbw, s);
-        if (d_m2) film_resolve_moments(ctx->dev, film, ctx->moments, fl, d_m2, s);
-        timer.end(s);
-        HIP_TRY(ctx, hipGetLastError());
-        if (stats) n_invalid = film_invalid_count(film, s);
-    }
+    const bool work = a.n_sel_tiles > 0 && a.spp_count > 0;
+    int rc = NORI_OK;
+    if (params->seed_mode == NORI_SEED_NORI_BLOCK && work) { rc = render_block_serial(ctx, c); engine = 2; }      /* (2: stats come from ctx->d_stats like the megakernel's) */
+    else if (engine == 1 && work) rc = render_wavefront(ctx, c);
+    else if (work) rc = render_megakernel(ctx, c);
+    if (rc) return rc;
     if (stats) {
-        HIP_TRY(ctx, hipEventRecord(ev1, s));
-        HIP_TRY(ctx, hipEventSynchronize(ev1));
-        float ms = 0.0f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, ev0, ev1));
-        unsigned long long h[16];
-        HIP_TRY(ctx, hipMemcpy(h, ctx->d_stats, sizeof(h), hipMemcpyDeviceToHost));
+        float ms = 0.0f; unsigned long long h[16];
+        if ((rc = scope.end(ms, h))) return rc;
+        const WfStats &wst = c.wst;
         memset(stats, 0, sizeof(*stats));
         stats->n_camera_samples = h[0]; stats->n_closest_rays = h[1]; stats->n_shadow_rays = h[2];
-        stats->n_node_tests = h[3]; stats->n_tri_tests = h[4]; stats->n_invalid = n_invalid;
+        stats->n_node_tests = h[3]; stats->n_tri_tests = h[4]; stats->n_invalid = c.n_invalid;
         stats->kernel_ms = ms;
         stats->engine = (uint32_t) engine;
         if (getenv("NORI_HIP_CENSUS") && h[8])
             fprintf(stderr, "[census] shade runs %llu lanes %.1f | inner runs %llu lanes %.1f | leaf runs %llu lanes %.1f\n", h[8], (double) h[9] / h[8], h[10], (double) h[11] / std::max(1ull, h[10]), h[12], (double) h[13] / std::max(1ull, h[12]));
-        stats->n_workgroups = n_workgroups;
+        stats->n_workgroups = c.n_workgroups;
         float cms[KC_COUNT]; unsigned int cl[KC_COUNT];
         timer.collect(cms, cl);
-        if (engine == 1) { for (int c = 0; c < KC_COUNT; ++c) { cms[c] = wst.class_ms[c]; cl[c] = wst.class_launches[c]; } }
+        if (engine == 1) { for (int k = 0; k < KC_COUNT; ++k) { cms[k] = wst.class_ms[k]; cl[k] = wst.class_launches[k]; } }
         stats->trace_ms = cms[KC_TRACE]; stats->shade_ms = cms[KC_SHADE]; stats->film_ms = cms[KC_FILM]; stats->n_trace_launches = cl[KC_TRACE];
         if (engine == 1) {
             stats->n_camera_samples = wst.n_camera; stats->n_closest_rays = wst.n_closest; stats->n_shadow_rays = wst.n_shadow;
@@ -1461,580 +1350,6 @@ static int render_impl(nori_hip_ctx *ctx, const nori_render_params *params, void
 }
 
 extern "C" {
-
-int nori_hip_render(nori_hip_ctx *ctx, const nori_render_params *params, void *d_rgbw, nori_render_stats *stats) {
-    return render_impl(ctx, params, d_rgbw, stats, nullptr);
-}
-
-int nori_hip_render_moments(nori_hip_ctx *ctx, const nori_render_params *params, void *d_rgbw, void *d_m2, nori_render_stats *stats) {
-    if (ctx && (!d_rgbw || !d_m2)) { ctx->error = "render_moments: needs an RGBW frame and a moment frame"; return NORI_ERR_INVALID_ARGUMENT; }
-    return render_impl(ctx, params, d_rgbw, stats, nullptr, (float *) d_m2);
-}
-
-int nori_hip_render_moments_host(nori_hip_ctx *ctx, const nori_render_params *params, float *rgbw, float *m2, nori_render_stats *stats) {
-    REQUIRE_ACCEL(ctx);
-    if (!params || !rgbw || !m2) return NORI_ERR_INVALID_ARGUMENT;
-    DeviceGuard g(ctx->device);
-    const size_t fb = frame_floats(ctx) * sizeof(float);
-    SCRATCH_OUT(ctx, df, 2 * fb);
-    HIP_TRY(ctx, hipMemset(df.p, 0, 2 * fb));
-    nori_render_stats local;
-    int rc = nori_hip_render_moments(ctx, params, df.p, (char *) df.p + fb, stats ? stats : &local);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(rgbw, df.p, fb, hipMemcpyDeviceToHost));
-    HIP_TRY(ctx, hipMemcpy(m2, (char *) df.p + fb, fb, hipMemcpyDeviceToHost));
-    return NORI_OK;
-}
-
-int nori_hip_error_map(nori_hip_ctx *ctx, const void *d_rgbw, const void *d_m2, void *d_err, float threshold, nori_error_summary *out, void *stream) {
-    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
-    if (!d_rgbw || !d_m2 || (!d_err && !out)) { ctx->error = "error_map: needs both frames and a map or a summary to fill"; return NORI_ERR_INVALID_ARGUMENT; }
-    DeviceGuard g(ctx->device);
-    FilmErrorSummary sum;
-    const std::string err = film_error_map(ctx->moments, ctx->dev, (const float *) d_rgbw, (const float *) d_m2, (float *) d_err, threshold, out ? &sum : nullptr, stream);
-    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
-    if (out) {
-        memset(out, 0, sizeof(*out));
-        out->sum_err = sum.sum_err; out->max_err = sum.max_err; out->threshold = threshold;
-        out->n_pixels = sum.n_pixels; out->n_empty = sum.n_empty; out->n_above = sum.n_above;
-    }
-    return NORI_OK;
-}
-
-int nori_hip_error_map_host(nori_hip_ctx *ctx, const float *rgbw, const float *m2, float *err, float threshold, nori_error_summary *out) {
-    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
-    if (!rgbw || !m2 || (!err && !out)) { ctx->error = "error_map: needs both frames and a map or a summary to fill"; return NORI_ERR_INVALID_ARGUMENT; }
-    DeviceGuard g(ctx->device);
-    const size_t fb = frame_floats(ctx) * sizeof(float);
-    const size_t eb = (size_t) ctx->host.camera.width * (size_t) ctx->host.camera.height * sizeof(float);
-    SCRATCH_OUT(ctx, df, 2 * fb + eb);
-    char *d_rgbw = (char *) df.p, *d_m2 = d_rgbw + fb, *d_err = d_m2 + fb;
-    HIP_TRY(ctx, hipMemcpy(d_rgbw, rgbw, fb, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d_m2, m2, fb, hipMemcpyHostToDevice));
-    int rc = nori_hip_error_map(ctx, d_rgbw, d_m2, err ? d_err : nullptr, threshold, out, nullptr);
-    if (rc) return rc;
-    if (err) HIP_TRY(ctx, hipMemcpy(err, d_err, eb, hipMemcpyDeviceToHost));      /* (a blocking copy: behind the kernel on the default stream) */
-    return NORI_OK;
-}
-
-int nori_hip_render_to_error(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_mean_err,
-                             void *d_rgbw, void *d_m2, uint32_t *spp_done, nori_error_summary *last, nori_render_stats *stats) {
-    REQUIRE_ACCEL(ctx);
-    if (!params || !d_rgbw || !d_m2) return NORI_ERR_INVALID_ARGUMENT;
-    if (pass_spp == 0) { ctx->error = "render_to_error: pass_spp must be at least 1"; return NORI_ERR_INVALID_ARGUMENT; }
-    if (!(target_mean_err >= 0.0f)) { ctx->error = "render_to_error: the target error must be a number >= 0"; return NORI_ERR_INVALID_ARGUMENT; }
-    if (params->tile_mod != 1) { ctx->error = "render_to_error: renders whole frames (tile_mod 1): the error of a share says nothing about the frame"; return NORI_ERR_INVALID_ARGUMENT; }
-    nori_render_stats total; memset(&total, 0, sizeof(total));
-    nori_error_summary sum; memset(&sum, 0, sizeof(sum));
-    bool evaluated = false;
-    uint32_t done = 0, passes = 0;
-    while (done < params->spp_count) {
-        nori_render_params p = *params;
-        p.spp_begin = params->spp_begin + done; p.spp_count = std::min(pass_spp, params->spp_count - done);
-        nori_render_stats st;
-        int rc = nori_hip_render_moments(ctx, &p, d_rgbw, d_m2, &st);
-        if (rc) return rc;
-        total.n_camera_samples += st.n_camera_samples; total.n_closest_rays += st.n_closest_rays; total.n_shadow_rays += st.n_shadow_rays;
-        total.n_node_tests += st.n_node_tests; total.n_tri_tests += st.n_tri_tests; total.n_invalid += st.n_invalid;
-        total.kernel_ms += st.kernel_ms; total.trace_ms += st.trace_ms; total.shade_ms += st.shade_ms; total.film_ms += st.film_ms; total.tail_ms += st.tail_ms;
-        total.n_workgroups += st.n_workgroups; total.n_trace_launches += st.n_trace_launches;
-        total.lds_bytes = st.lds_bytes; total.engine = st.engine; total.trace_cus = st.trace_cus; total.tail_cus = st.tail_cus; total.wf_record = st.wf_record;
-        done += p.spp_count; ++passes;
-        evaluated = false;
-        if (passes >= 2) {      /* (one pass of few samples has no variance to speak of) */
-            rc = nori_hip_error_map(ctx, d_rgbw, d_m2, nullptr, target_mean_err, &sum, params->stream);
-            if (rc) return rc;
-            evaluated = true;
-            if (sum.sum_err / (double) sum.n_pixels <= (double) target_mean_err) break;
-        }
-    }
-    if (last) {
-        if (!evaluated) { int rc = nori_hip_error_map(ctx, d_rgbw, d_m2, nullptr, target_mean_err, &sum, params->stream); if (rc) return rc; }
-        *last = sum;
-    }
-    if (spp_done) *spp_done = done;
-    if (stats) *stats = total;
-    return NORI_OK;
-}
-
-int nori_hip_render_to_error_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_mean_err,
-                                  float *rgbw, float *m2, float *err, uint32_t *spp_done, nori_error_summary *last, nori_render_stats *stats) {
-    REQUIRE_ACCEL(ctx);
-    if (!params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;
-    DeviceGuard g(ctx->device);
-    const size_t fb = frame_floats(ctx) * sizeof(float);
-    const size_t eb = (size_t) ctx->host.camera.width * (size_t) ctx->host.camera.height * sizeof(float);
-    SCRATCH_OUT(ctx, df, 2 * fb + eb);
-    HIP_TRY(ctx, hipMemset(df.p, 0, 2 * fb + eb));
-    char *d_rgbw = (char *) df.p, *d_m2 = d_rgbw + fb, *d_err = d_m2 + fb;
-    int rc = nori_hip_render_to_error(ctx, params, pass_spp, target_mean_err, d_rgbw, d_m2, spp_done, last, stats);
-    if (rc) return rc;
-    if (err) {
-        rc = nori_hip_error_map(ctx, d_rgbw, d_m2, d_err, target_mean_err, nullptr, params->stream);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipStreamSynchronize((hipStream_t) params->stream));
-        HIP_TRY(ctx, hipMemcpy(err, d_err, eb, hipMemcpyDeviceToHost));
-    }
-    HIP_TRY(ctx, hipMemcpy(rgbw, d_rgbw, fb, hipMemcpyDeviceToHost));
-    if (m2) HIP_TRY(ctx, hipMemcpy(m2, d_m2, fb, hipMemcpyDeviceToHost));
-    return NORI_OK;
-}
-
-/* ---- tile lists, tile errors, selection, the adaptive loop (film_tiles.h) ---- */
-
-static uint32_t frame_tiles(const nori_hip_ctx *ctx) {
-    return (uint32_t) ((ctx->host.camera.width + kTile - 1) / kTile) * (uint32_t) ((ctx->host.camera.height + kTile - 1) / kTile);
-}
-
-/* a host list: strictly ascending raster ids of tiles of the frame */
-static int check_tile_list(nori_hip_ctx *ctx, const char *what, const uint32_t *tiles, uint32_t n) {
-    const uint32_t n_frame = frame_tiles(ctx);
-    if (n && !tiles) { ctx->error = std::string(what) + ": no tile list"; return NORI_ERR_INVALID_ARGUMENT; }
-    for (uint32_t i = 0; i < n; ++i) {
-        if (tiles[i] >= n_frame) { ctx->error = std::string(what) + ": tile " + std::to_string(tiles[i]) + " (entry " + std::to_string(i) + ") is out of range: the frame has " + std::to_string(n_frame) + " tiles"; return NORI_ERR_INVALID_ARGUMENT; }
-        if (i && tiles[i] <= tiles[i - 1]) { ctx->error = std::string(what) + ": the tile list must be strictly ascending (entry " + std::to_string(i) + ": " + std::to_string(tiles[i]) + " after " + std::to_string(tiles[i - 1]) + ")"; return NORI_ERR_INVALID_ARGUMENT; }
-    }
-    return NORI_OK;
-}
-
-/* what render_impl refuses for a list, checked before the list is looked at (an empty list is refused the same way) */
-static int check_tiles_render(nori_hip_ctx *ctx, const nori_render_params *params) {
-    if (ctx->film_reference || params->seed_mode == NORI_SEED_NORI_BLOCK) {
-        ctx->error = "render_tiles: a tile list is rendered by the fast film with NORI_SEED_PER_SAMPLE only (reference order and the block-serial sampler render whole frames)";
-        return NORI_ERR_UNSUPPORTED;
-    }
-    if (params->tile_mod != 1 || params->tile_rem != 0) { ctx->error = "render_tiles: the list names the tiles (tile_mod 1, tile_rem 0)"; return NORI_ERR_INVALID_ARGUMENT; }
-    return NORI_OK;
-}
-
-static void add_stats(nori_render_stats &total, const nori_render_stats &st) {
-    total.n_camera_samples += st.n_camera_samples; total.n_closest_rays += st.n_closest_rays; total.n_shadow_rays += st.n_shadow_rays;
-    total.n_node_tests += st.n_node_tests; total.n_tri_tests += st.n_tri_tests; total.n_invalid += st.n_invalid;
-    total.kernel_ms += st.kernel_ms; total.trace_ms += st.trace_ms; total.shade_ms += st.shade_ms; total.film_ms += st.film_ms; total.tail_ms += st.tail_ms;
-    total.n_workgroups += st.n_workgroups; total.n_trace_launches += st.n_trace_launches;
-    total.lds_bytes = st.lds_bytes; total.engine = st.engine; total.trace_cus = st.trace_cus; total.tail_cus = st.tail_cus; total.wf_record = st.wf_record;
-}
-
-int nori_hip_render_tiles(nori_hip_ctx *ctx, const nori_render_params *params, const uint32_t *tiles, uint32_t n_tiles,
-                          void *d_rgbw, void *d_m2, nori_render_stats *stats) {
-    REQUIRE_ACCEL(ctx);
-    if (!params || !d_rgbw) return NORI_ERR_INVALID_ARGUMENT;
-    int rc = check_tiles_render(ctx, params);
-    if (rc) return rc;
-    rc = check_tile_list(ctx, "render_tiles", tiles, n_tiles);
-    if (rc) return rc;
-    if (n_tiles == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return NORI_OK; }      /* nothing is touched */
-    DeviceGuard g(ctx->device);
-    const std::string err = film_tiles_upload(ctx->tiles, tiles, n_tiles, frame_tiles(ctx), params->stream);
-    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
-    return render_impl(ctx, params, d_rgbw, stats, nullptr, (float *) d_m2, &ctx->tiles);
-}
-
-int nori_hip_render_tiles_host(nori_hip_ctx *ctx, const nori_render_params *params, const uint32_t *tiles, uint32_t n_tiles,
-                               float *rgbw, float *m2, nori_render_stats *stats) {
-    REQUIRE_ACCEL(ctx);
-    if (!params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;
-    DeviceGuard g(ctx->device);
-    const size_t fb = frame_floats(ctx) * sizeof(float);
-    SCRATCH_OUT(ctx, df, 2 * fb);
-    HIP_TRY(ctx, hipMemset(df.p, 0, 2 * fb));
-    nori_render_stats local;
-    int rc = nori_hip_render_tiles(ctx, params, tiles, n_tiles, df.p, m2 ? (char *) df.p + fb : nullptr, stats ? stats : &local);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(rgbw, df.p, fb, hipMemcpyDeviceToHost));
-    if (m2) HIP_TRY(ctx, hipMemcpy(m2, (char *) df.p + fb, fb, hipMemcpyDeviceToHost));
-    return NORI_OK;
-}
-
-int nori_hip_tile_errors(nori_hip_ctx *ctx, const void *d_rgbw, const void *d_m2, void *d_tile_err, void *stream) {
-    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
-    if (!d_rgbw || !d_m2 || !d_tile_err) { ctx->error = "tile_errors: needs both frames and an array to fill"; return NORI_ERR_INVALID_ARGUMENT; }
-    DeviceGuard g(ctx->device);
-    const std::string err = film_tile_errors(ctx->dev, (const float *) d_rgbw, (const float *) d_m2, (float *) d_tile_err, stream);
-    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
-    return NORI_OK;
-}
-
-int nori_hip_tile_errors_host(nori_hip_ctx *ctx, const float *rgbw, const float *m2, float *tile_err) {
-    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
-    if (!rgbw || !m2 || !tile_err) { ctx->error = "tile_errors: needs both frames and an array to fill"; return NORI_ERR_INVALID_ARGUMENT; }
-    DeviceGuard g(ctx->device);
-    const size_t fb = frame_floats(ctx) * sizeof(float), eb = (size_t) frame_tiles(ctx) * sizeof(float);
-    SCRATCH_OUT(ctx, df, 2 * fb + eb);
-    char *d_rgbw = (char *) df.p, *d_m2 = d_rgbw + fb, *d_err = d_m2 + fb;
-    HIP_TRY(ctx, hipMemcpy(d_rgbw, rgbw, fb, hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy(d_m2, m2, fb, hipMemcpyHostToDevice));
-    int rc = nori_hip_tile_errors(ctx, d_rgbw, d_m2, d_err, nullptr);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(tile_err, d_err, eb, hipMemcpyDeviceToHost));      /* (a blocking copy: behind the kernel on the default stream) */
-    return NORI_OK;
-}
-
-int nori_hip_select_tiles(nori_hip_ctx *ctx, const void *d_tile_err, float target, const uint32_t *tiles_in, uint32_t n_in,
-                          uint32_t *tiles_out, uint32_t *n_out) {
-    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
-    if (!d_tile_err || !n_out || (n_in && !tiles_out)) { ctx->error = "select_tiles: needs the tile errors, a list to fill and its length"; return NORI_ERR_INVALID_ARGUMENT; }
-    int rc = check_tile_list(ctx, "select_tiles", tiles_in, n_in);
-    if (rc) return rc;
-    DeviceGuard g(ctx->device);
-    std::string err = film_tiles_upload(ctx->tiles, tiles_in, n_in, frame_tiles(ctx), nullptr);
-    if (err.empty()) err = film_tiles_select(ctx->tiles, (const float *) d_tile_err, target, frame_tiles(ctx), nullptr);
-    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
-    *n_out = ctx->tiles.n;
-    if (ctx->tiles.n) HIP_TRY(ctx, hipMemcpy(tiles_out, ctx->tiles.list[ctx->tiles.cur], (size_t) ctx->tiles.n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return NORI_OK;
-}
-
-int nori_hip_render_adaptive(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_tile_err,
-                             void *d_rgbw, void *d_m2, void *d_tile_spp, nori_adaptive_summary *out, nori_render_stats *stats) {
-    REQUIRE_ACCEL(ctx);
-    if (!params || !d_rgbw || !d_m2) return NORI_ERR_INVALID_ARGUMENT;
-    if (pass_spp == 0) { ctx->error = "render_adaptive: pass_spp must be at least 1"; return NORI_ERR_INVALID_ARGUMENT; }
-    if (!(target_tile_err >= 0.0f)) { ctx->error = "render_adaptive: the target error must be a number >= 0"; return NORI_ERR_INVALID_ARGUMENT; }
-    if (params->tile_mod != 1) { ctx->error = "render_adaptive: renders whole frames (tile_mod 1): the loop shares the tiles out itself"; return NORI_ERR_INVALID_ARGUMENT; }
-    int rc = check_tiles_render(ctx, params);
-    if (rc) return rc;
-    DeviceGuard g(ctx->device);
-    hipStream_t s = (hipStream_t) params->stream;
-    FilmTiles &T = ctx->tiles;
-    const uint32_t n_frame = frame_tiles(ctx);
-    {      /* the active set starts as all tiles */
-        std::vector<uint32_t> all(n_frame);
-        for (uint32_t i = 0; i < n_frame; ++i) all[i] = i;
-        const std::string err = film_tiles_upload(T, all.data(), n_frame, n_frame, s);
-        if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
-    }
-    HIP_TRY(ctx, hipMemsetAsync(T.tile_spp, 0, (size_t) n_frame * sizeof(uint32_t), s));
-    nori_render_stats total; memset(&total, 0, sizeof(total));
-    uint32_t done = 0, passes = 0;
-    bool evaluated = false;
-    while (done < params->spp_count && T.n > 0) {
-        nori_render_params p = *params;
-        p.spp_begin = params->spp_begin + done; p.spp_count = std::min(pass_spp, params->spp_count - done);
-        nori_render_stats st;
-        rc = render_impl(ctx, &p, d_rgbw, &st, nullptr, (float *) d_m2, &T);
-        if (rc) return rc;
-        add_stats(total, st);
-        film_tiles_add_spp(T, T.tile_spp, p.spp_count, s);
-        done += p.spp_count; ++passes;
-        evaluated = false;
-        if (passes >= 2) {      /* (one pass of few samples has no variance to speak of) */
-            std::string err = film_tile_errors(ctx->dev, (const float *) d_rgbw, (const float *) d_m2, T.tile_err, s);
-            if (err.empty()) err = film_tiles_select(T, T.tile_err, target_tile_err, n_frame, s);
-            if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
-            evaluated = true;
-        }
-    }
-    if (out) {
-        memset(out, 0, sizeof(*out));
-        uint32_t n_unconverged = T.n;
-        if (!evaluated) {      /* the samples were spent in one pass: the frames as they are left are measured once, without retiring anything */
-            std::string err = film_tile_errors(ctx->dev, (const float *) d_rgbw, (const float *) d_m2, T.tile_err, s);
-            if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
-            std::vector<float> te(n_frame);
-            HIP_TRY(ctx, hipMemcpyAsync(te.data(), T.tile_err, (size_t) n_frame * sizeof(float), hipMemcpyDeviceToHost, s));
-            HIP_TRY(ctx, hipStreamSynchronize(s));
-            n_unconverged = 0;
-            for (uint32_t i = 0; i < n_frame; ++i) n_unconverged += !(te[i] <= target_tile_err) ? 1u : 0u;
-        }
-        std::vector<uint32_t> spp(n_frame);
-        HIP_TRY(ctx, hipMemcpyAsync(spp.data(), T.tile_spp, (size_t) n_frame * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_TRY(ctx, hipStreamSynchronize(s));
-        out->passes = passes; out->n_tiles = n_frame; out->n_unconverged = n_unconverged;
-        out->spp_min = *std::min_element(spp.begin(), spp.end()); out->spp_max = *std::max_element(spp.begin(), spp.end());
-        rc = nori_hip_error_map(ctx, d_rgbw, d_m2, nullptr, target_tile_err, &out->frame, params->stream);
-        if (rc) return rc;
-    }
-    if (d_tile_spp) HIP_TRY(ctx, hipMemcpyAsync(d_tile_spp, T.tile_spp, (size_t) n_frame * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    if (stats) *stats = total;
-    return NORI_OK;
-}
-
-int nori_hip_render_adaptive_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_tile_err,
-                                  float *rgbw, float *m2, float *err, uint32_t *tile_spp, nori_adaptive_summary *out, nori_render_stats *stats) {
-    REQUIRE_ACCEL(ctx);
-    if (!params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;
-    DeviceGuard g(ctx->device);
-    const size_t fb = frame_floats(ctx) * sizeof(float);
-    const size_t eb = (size_t) ctx->host.camera.width * (size_t) ctx->host.camera.height * sizeof(float);
-    const size_t tb = (size_t) frame_tiles(ctx) * sizeof(uint32_t);
-    SCRATCH_OUT(ctx, df, 2 * fb + eb + tb);
-    HIP_TRY(ctx, hipMemset(df.p, 0, 2 * fb + eb + tb));
-    char *d_rgbw = (char *) df.p, *d_m2 = d_rgbw + fb, *d_err = d_m2 + fb, *d_spp = d_err + eb;
-    int rc = nori_hip_render_adaptive(ctx, params, pass_spp, target_tile_err, d_rgbw, d_m2, d_spp, out, stats);
-    if (rc) return rc;
-    if (err) {
-        rc = nori_hip_error_map(ctx, d_rgbw, d_m2, d_err, target_tile_err, nullptr, params->stream);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipStreamSynchronize((hipStream_t) params->stream));
-        HIP_TRY(ctx, hipMemcpy(err, d_err, eb, hipMemcpyDeviceToHost));
-    }
-    HIP_TRY(ctx, hipMemcpy(rgbw, d_rgbw, fb, hipMemcpyDeviceToHost));
-    if (m2) HIP_TRY(ctx, hipMemcpy(m2, d_m2, fb, hipMemcpyDeviceToHost));
-    if (tile_spp) HIP_TRY(ctx, hipMemcpy(tile_spp, d_spp, tb, hipMemcpyDeviceToHost));
-    return NORI_OK;
-}
-
-/* ---- first-hit feature frames (features.h): one trace for all requested features, then the film once per feature ---- */
-
-int nori_hip_render_features(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t features,
-                             void *d_albedo, void *d_normal, void *d_depth, nori_render_stats *stats) {
-    REQUIRE_ACCEL(ctx);
-    if (!params) return NORI_ERR_INVALID_ARGUMENT;
-    void *d_frame[kFeatureCount] = {d_albedo, d_normal, d_depth};
-    if (features == 0u || (features & ~kFeatureAll)) { ctx->error = "render_features: the mask must name at least one of NORI_FEATURE_ALBEDO | NORMAL | DEPTH and nothing else"; return NORI_ERR_INVALID_ARGUMENT; }
-    for (int f = 0; f < kFeatureCount; ++f)
-        if ((features & (1u << f)) && !d_frame[f]) { ctx->error = "render_features: a requested feature has no frame"; return NORI_ERR_INVALID_ARGUMENT; }
-    if (params->tile_mod == 0 || params->tile_rem >= params->tile_mod) { ctx->error = "render: bad tile_mod/tile_rem"; return NORI_ERR_INVALID_ARGUMENT; }
-    if (params->seed_mode != NORI_SEED_PER_SAMPLE && params->seed_mode != NORI_SEED_NORI_BLOCK) { ctx->error = "render: unknown seed_mode"; return NORI_ERR_INVALID_ARGUMENT; }
-    if (params->seed_mode == NORI_SEED_NORI_BLOCK) {
-        ctx->error = "render_features: NORI_SEED_PER_SAMPLE only (a block's serial stream depends on the paths the beauty render traced: its camera samples cannot be drawn again without them)";
-        return NORI_ERR_UNSUPPORTED;
-    }
-    if (ctx->host.filter.border > 8) { ctx->error = "render: reconstruction filter radius too large for the LDS tile"; return NORI_ERR_UNSUPPORTED; }
-    DeviceGuard g(ctx->device);
-    hipStream_t s = (hipStream_t) params->stream;
-
-    RenderArgs a;      /* the tile / chunk geometry of the megakernel path (plan_chunks) */
-    a.spp_begin = params->spp_begin; a.spp_count = params->spp_count;
-    a.tile_mod = params->tile_mod; a.tile_rem = params->tile_rem;
-    a.tiles_x = (uint32_t) ((ctx->host.camera.width + kTile - 1) / kTile);
-    a.tiles_y = (uint32_t) ((ctx->host.camera.height + kTile - 1) / kTile);
-    const uint32_t n_tiles = a.tiles_x * a.tiles_y;
-    a.n_sel_tiles = n_tiles > a.tile_rem ? (n_tiles - a.tile_rem + a.tile_mod - 1) / a.tile_mod : 0;
-    a.tile_w = kTile + 2 * ctx->host.filter.border;
-    a.debug_flags = 0u; a.th_shade = a.th_inner = a.th_leaf = 1u;
-    plan_chunks(a);
-    const uint32_t need = ctx->bvh.max_depth + 1;
-    unsigned long long n_invalid = 0; uint32_t n_workgroups = 0;
-
-    struct EventPair {      /* destroyed on every return path */
-        hipEvent_t a = nullptr, b = nullptr;
-        ~EventPair() { if (a) (void) hipEventDestroy(a); if (b) (void) hipEventDestroy(b); }
-    } evp;
-    if (stats) {
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_stats, 0, 16 * sizeof(unsigned long long), s));
-        HIP_TRY(ctx, hipEventCreate(&evp.a)); HIP_TRY(ctx, hipEventCreate(&evp.b));
-        HIP_TRY(ctx, hipEventRecord(evp.a, s));
-    }
-    KernelTimer timer(stats && params->time_kernels != 0);
-    if (a.n_sel_tiles > 0 && a.spp_count > 0) {
-        /* as the megakernel path of render_impl: a call that produces more samples than the store budget is cut into launches
-           over sample sub-ranges, each followed by its gathers; the accumulators are carried from launch to launch */
-        size_t cap = (size_t) 1 << 29;
-        if (const char *e = getenv("NORI_HIP_FILM_SAMPLES")) cap = (size_t) std::max(256ll, atoll(e));
-        const uint32_t spp_per_launch = (uint32_t) std::max<size_t>(1, std::min<size_t>(a.spp_count, cap / ((size_t) a.n_sel_tiles * 256)));
-        const size_t n_samples = (size_t) a.n_sel_tiles * 256 * spp_per_launch;
-        FilmStore film;      /* pos, n_parts and the invalid counter are the film's own; always the fast film (no reference order of a feature frame exists) */
-        std::string ferr = film_prepare(ctx->film, n_samples, a.n_sel_tiles, a.tile_w, s, film);
-        if (ferr.empty()) ferr = feature_store_prepare(ctx->features, features, film, n_samples, a.n_sel_tiles, a.tile_w, s);
-        if (!ferr.empty()) { ctx->error = ferr; return NORI_ERR_OUT_OF_MEMORY; }
-        FilmLaunch fl;
-        fl.tile_first = 0; fl.store_tile_first = 0; fl.n_tiles = a.n_sel_tiles; fl.tile_mod = a.tile_mod; fl.tile_rem = a.tile_rem;
-        fl.tiles_x = a.tiles_x; fl.tiles_y = a.tiles_y; fl.tile_w = a.tile_w;
-        for (uint32_t sb = 0; sb < a.spp_count; sb += spp_per_launch) {
-            RenderArgs a2 = a;
-            a2.spp_begin = a.spp_begin + sb; a2.spp_count = std::min(spp_per_launch, a.spp_count - sb);
-            plan_chunks(a2);
-            FeatureLaunch pl;
-            pl.spp_begin = a2.spp_begin; pl.spp_count = a2.spp_count; pl.tile_mod = a2.tile_mod; pl.tile_rem = a2.tile_rem; pl.tiles_x = a2.tiles_x;
-            pl.n_sel_tiles = a2.n_sel_tiles; pl.n_chunks = a2.n_chunks; pl.chunk_spp = a2.chunk_spp; pl.mask = features;
-            timer.begin(KC_TRACE, s);
-            const hipError_t e = feature_pass_launch(ctx->dev, pl, need, film, ctx->features, ctx->d_stats, s);
-            timer.end(s);
-            HIP_TRY(ctx, e);
-            fl.n_spp = a2.spp_count;
-            timer.begin(KC_FILM, s);
-            for (int f = 0; f < kFeatureCount; ++f)      /* before the next launch overwrites the store */
-                if (features & (1u << f)) film_gather(ctx->dev, ctx->d_filter, feature_view(film, ctx->features, f), fl, s);
-            timer.end(s);
-            n_workgroups += a2.n_sel_tiles * a2.n_chunks;
-        }
-        timer.begin(KC_FILM, s);
-        for (int f = 0; f < kFeatureCount; ++f)
-            if (features & (1u << f)) film_resolve(ctx->dev, feature_view(film, ctx->features, f), fl, (float *) d_frame[f], s);
-        timer.end(s);
-        HIP_TRY(ctx, hipGetLastError());
-        if (stats) n_invalid = film_invalid_count(film, s);
-    }
-    if (stats) {
-        HIP_TRY(ctx, hipEventRecord(evp.b, s));
-        HIP_TRY(ctx, hipEventSynchronize(evp.b));
-        float ms = 0.0f;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, evp.a, evp.b));
-        unsigned long long h[16];
-        HIP_TRY(ctx, hipMemcpy(h, ctx->d_stats, sizeof(h), hipMemcpyDeviceToHost));
-        memset(stats, 0, sizeof(*stats));
-        stats->n_camera_samples = h[0]; stats->n_closest_rays = h[1]; stats->n_invalid = n_invalid;
-        stats->kernel_ms = ms; stats->engine = 3u; stats->n_workgroups = n_workgroups;
-        float cms[KC_COUNT]; unsigned int cl[KC_COUNT];
-        timer.collect(cms, cl);
-        stats->trace_ms = cms[KC_TRACE]; stats->film_ms = cms[KC_FILM]; stats->n_trace_launches = cl[KC_TRACE];
-        stats->lds_bytes = feature_pass_lds_bytes(need);
-    }
-    return NORI_OK;
-}
-
-int nori_hip_render_features_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t features,
-                                  float *albedo, float *normal, float *depth, nori_render_stats *stats) {
-    REQUIRE_ACCEL(ctx);
-    if (!params) return NORI_ERR_INVALID_ARGUMENT;
-    float *frame[kFeatureCount] = {albedo, normal, depth};
-    DeviceGuard g(ctx->device);
-    const size_t fb = frame_floats(ctx) * sizeof(float);
-    SCRATCH_OUT(ctx, df, kFeatureCount * fb);
-    HIP_TRY(ctx, hipMemset(df.p, 0, kFeatureCount * fb));
-    char *d[kFeatureCount];
-    for (int f = 0; f < kFeatureCount; ++f) d[f] = frame[f] ? (char *) df.p + f * fb : nullptr;
-    nori_render_stats local;
-    int rc = nori_hip_render_features(ctx, params, features, d[0], d[1], d[2], stats ? stats : &local);
-    if (rc) return rc;
-    for (int f = 0; f < kFeatureCount; ++f)
-        if ((features & (1u << f)) && frame[f]) HIP_TRY(ctx, hipMemcpy(frame[f], d[f], fb, hipMemcpyDeviceToHost));
-    return NORI_OK;
-}
-
-/* ---- the denoiser (denoise.h): guide records from the frames, then the NL-means filter over them ---- */
-
-static int denoise_frames_ok(nori_hip_ctx *ctx, const void *rgbw, const void *m2, const void *out, const char *what) {
-    if (!rgbw || !m2 || !out) { ctx->error = std::string(what) + ": needs the RGBW frame, the moment frame and a buffer to fill"; return NORI_ERR_INVALID_ARGUMENT; }
-    return NORI_OK;
-}
-
-/* the launch of step B from the public parameters (NULL: the defaults), or the message of the first one out of range */
-static std::string denoise_plan(const nori_denoise_params *params, DenoiseLaunch &dl) {
-    const nori_denoise_params def = NORI_DENOISE_PARAMS_DEFAULT;
-    const nori_denoise_params p = params ? *params : def;
-    if (p.radius < 1u || p.radius > (uint32_t) kDenoiseMaxRadius) return "denoise: the window radius must be 1 .. 8";
-    if (p.patch > (uint32_t) kDenoiseMaxPatch) return "denoise: the patch radius must be 0 .. 2";
-    if (!(p.k_c > 0.0f)) return "denoise: k_c must be positive";
-    if (!(p.alpha >= 0.0f)) return "denoise: alpha must not be negative";
-    if (!(p.tau_albedo > 0.0f) || !(p.tau_normal > 0.0f) || !(p.tau_cov > 0.0f)) return "denoise: tau_albedo, tau_normal and tau_cov must be positive";
-    if (!(p.k_depth > 0.0f)) return "denoise: k_depth must be positive";
-    dl.radius = (int32_t) p.radius; dl.patch = (int32_t) p.patch;
-    dl.kc2 = p.k_c * p.k_c; dl.alpha = p.alpha;
-    dl.tau_albedo = p.tau_albedo; dl.tau_normal = p.tau_normal;
-    dl.kd2 = p.k_depth * p.k_depth; dl.tau_cov = p.tau_cov;
-    return std::string();
-}
-
-int nori_hip_denoise_guides(nori_hip_ctx *ctx, const void *d_rgbw, const void *d_m2, const void *d_albedo, const void *d_normal,
-                            const void *d_depth, void *d_guides, void *stream) {
-    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
-    if (int rc = denoise_frames_ok(ctx, d_rgbw, d_m2, d_guides, "denoise_guides")) return rc;
-    DeviceGuard g(ctx->device);
-    HIP_TRY(ctx, denoise_guides_launch(ctx->host.camera.width, ctx->host.camera.height, ctx->host.filter.border, (const float *) d_rgbw, (const float *) d_m2,
-                                       (const float *) d_albedo, (const float *) d_normal, (const float *) d_depth, (float *) d_guides, stream));
-    return NORI_OK;
-}
-
-int nori_hip_denoise(nori_hip_ctx *ctx, const nori_denoise_params *params, const void *d_rgbw, const void *d_m2, const void *d_albedo,
-                     const void *d_normal, const void *d_depth, void *d_rgb_out, void *d_wsum, void *stream) {
-    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
-    if (int rc = denoise_frames_ok(ctx, d_rgbw, d_m2, d_rgb_out, "denoise")) return rc;
-    DenoiseLaunch dl;
-    const std::string bad = denoise_plan(params, dl);
-    if (!bad.empty()) { ctx->error = bad; return NORI_ERR_INVALID_ARGUMENT; }
-    dl.width = ctx->host.camera.width; dl.height = ctx->host.camera.height;
-    dl.terms = (d_albedo ? kDenoiseAlbedo : 0u) | (d_normal ? kDenoiseNormal : 0u) | (d_depth ? kDenoiseDepth : 0u);
-    DeviceGuard g(ctx->device);
-    float *d_guides = nullptr;
-    const std::string err = denoise_store_guides(ctx->denoise, stream, (size_t) dl.width * (size_t) dl.height, &d_guides);
-    if (!err.empty()) { ctx->error = err; return NORI_ERR_OUT_OF_MEMORY; }
-    HIP_TRY(ctx, denoise_guides_launch(dl.width, dl.height, ctx->host.filter.border, (const float *) d_rgbw, (const float *) d_m2, (const float *) d_albedo,
-                                       (const float *) d_normal, (const float *) d_depth, d_guides, stream));
-    HIP_TRY(ctx, denoise_filter_launch(dl, d_guides, (float *) d_rgb_out, (float *) d_wsum, stream));
-    return NORI_OK;
-}
-
-/* the host twins: the frames that are given go to one scratch buffer, in the order rgbw, m2, albedo, normal, depth */
-struct DenoiseHostFrames {
-    char *d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-};
-static hipError_t denoise_upload(const float *const frame[5], char *base, size_t fb, DenoiseHostFrames &out) {
-    for (int f = 0; f < 5; ++f) {
-        if (!frame[f]) continue;
-        out.d[f] = base + (size_t) f * fb;
-        const hipError_t e = hipMemcpy(out.d[f], frame[f], fb, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-int nori_hip_denoise_guides_host(nori_hip_ctx *ctx, const float *rgbw, const float *m2, const float *albedo, const float *normal,
-                                 const float *depth, float *guides) {
-    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
-    if (int rc = denoise_frames_ok(ctx, rgbw, m2, guides, "denoise_guides")) return rc;
-    DeviceGuard g(ctx->device);
-    const size_t fb = frame_floats(ctx) * sizeof(float);
-    const size_t gb = (size_t) ctx->host.camera.width * (size_t) ctx->host.camera.height * kGuideFloats * sizeof(float);
-    SCRATCH_OUT(ctx, df, 5 * fb + gb);
-    const float *const frame[5] = {rgbw, m2, albedo, normal, depth};
-    DenoiseHostFrames d;
-    HIP_TRY(ctx, denoise_upload(frame, (char *) df.p, fb, d));
-    char *d_guides = (char *) df.p + 5 * fb;
-    int rc = nori_hip_denoise_guides(ctx, d.d[0], d.d[1], d.d[2], d.d[3], d.d[4], d_guides, nullptr);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(guides, d_guides, gb, hipMemcpyDeviceToHost));      /* (a blocking copy: behind the kernel on the default stream) */
-    return NORI_OK;
-}
-
-int nori_hip_denoise_host(nori_hip_ctx *ctx, const nori_denoise_params *params, const float *rgbw, const float *m2, const float *albedo,
-                          const float *normal, const float *depth, float *rgb_out, float *wsum) {
-    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
-    if (int rc = denoise_frames_ok(ctx, rgbw, m2, rgb_out, "denoise")) return rc;
-    DeviceGuard g(ctx->device);
-    const size_t fb = frame_floats(ctx) * sizeof(float);
-    const size_t pb = (size_t) ctx->host.camera.width * (size_t) ctx->host.camera.height * sizeof(float);
-    SCRATCH_OUT(ctx, df, 5 * fb + 4 * pb);
-    const float *const frame[5] = {rgbw, m2, albedo, normal, depth};
-    DenoiseHostFrames d;
-    HIP_TRY(ctx, denoise_upload(frame, (char *) df.p, fb, d));
-    char *d_out = (char *) df.p + 5 * fb, *d_wsum = d_out + 3 * pb;
-    int rc = nori_hip_denoise(ctx, params, d.d[0], d.d[1], d.d[2], d.d[3], d.d[4], d_out, wsum ? d_wsum : nullptr, nullptr);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(rgb_out, d_out, 3 * pb, hipMemcpyDeviceToHost));
-    if (wsum) HIP_TRY(ctx, hipMemcpy(wsum, d_wsum, pb, hipMemcpyDeviceToHost));
-    return NORI_OK;
-}
-
-int nori_hip_block_acc_floats(nori_hip_ctx *ctx, size_t *n_floats) {
-    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
-    if (!n_floats) return NORI_ERR_INVALID_ARGUMENT;
-    *n_floats = film_block_acc_floats(ctx->dev);
-    return NORI_OK;
-}
-
-int nori_hip_render_block_rows(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t row_begin, uint32_t row_count,
-                               void *d_block_acc, nori_render_stats *stats) {
-    FilmBlockRows share;
-    share.row_begin = row_begin; share.row_count = row_count; share.block_acc = (float *) d_block_acc;
-    return render_impl(ctx, params, nullptr, stats, &share);
-}
-
-int nori_hip_resolve_blocks(nori_hip_ctx *ctx, const void *d_block_acc, void *d_rgbw, void *stream) {
-    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
-    if (!d_block_acc || !d_rgbw) return NORI_ERR_INVALID_ARGUMENT;
-    DeviceGuard g(ctx->device);
-    const std::string err = film_resolve_blocks(ctx->film, ctx->dev, (const float *) d_block_acc, (float *) d_rgbw, (hipStream_t) stream);
-    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
-    return NORI_OK;
-}
-
-int nori_hip_render_host(nori_hip_ctx *ctx, const nori_render_params *params, float *rgbw, nori_render_stats *stats) {
-    REQUIRE_ACCEL(ctx);
-    if (!params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;
-    DeviceGuard g(ctx->device);
-    const size_t fb = frame_floats(ctx) * sizeof(float);
-    SCRATCH_OUT(ctx, df, fb);
-    HIP_TRY(ctx, hipMemset(df.p, 0, fb));
-    nori_render_stats local;
-    int rc = nori_hip_render(ctx, params, df.p, stats ? stats : &local);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpy(rgbw, df.p, fb, hipMemcpyDeviceToHost));
-    return NORI_OK;
-}
 
 int nori_hip_develop(nori_hip_ctx *ctx, const void *d_rgbw, void *d_rgb, void *stream) {
     if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;

@@ -9,7 +9,7 @@ OBJ=$ROOT/build/obj
 mkdir -p $OBJ
 FLAGS="-DNORI_LAB -O3 --offload-arch=gfx950 -std=c++17 -ffp-contract=off -fno-slp-vectorize -mllvm -disable-machine-sink -fPIC -Wno-comment -Wno-unused-result"
 UNITS=${UNITS:-wavefront.hip}
-ALL="nori_hip.hip lbvh.hip wavefront.hip film.hip film_tiles.hip group.hip scene_prep.cpp"
+ALL=$(cd $ROOT && python -c "import __graft_entry__ as g; print(' '.join(g.HIP_SOURCES))")      # the one list of translation units
 NEWEST=$(ls -t $DEV/*.h $ROOT/include/nori_hip.h | head -1)
 for f in $ALL; do
   if [ ! -f $OBJ/$f.o ] || [ $DEV/$f -nt $OBJ/$f.o ] || [ $NEWEST -nt $OBJ/$f.o ]; then
