@@ -771,6 +771,84 @@ int nori_hip_denoise_guides_host(nori_hip_ctx *ctx, const float *rgbw, const flo
 int nori_hip_denoise_host(nori_hip_ctx *ctx, const nori_denoise_params *params, const float *rgbw, const float *m2, const float *albedo,
                           const float *normal, const float *depth, float *rgb_out, float *wsum /* may be NULL */);
 
+/* ------------------------------------------- the denoiser with the variance of its output; adaptive sampling that stops on it
+ *
+ * No counterpart in the reference.  The last link of moments -> error map -> tile lists -> feature frames -> denoiser: an estimate
+ * of how good the DENOISED frame is, so that the adaptive loop can retire tiles on the error of what the user will look at.  A
+ * translation unit of its own (denoise_error.h); the kernels of nori_hip_denoise, of the renders, the film and the tile lists are
+ * not involved and give the same bits before and after a call.
+ *
+ * nori_hip_denoise_var is nori_hip_denoise with three more accumulators in step B.  Per pixel p, vnum = (0, 0, 0) beside num and
+ * wsum, and in step 5 of every contributing tap, after wsum = wsum + w:
+ *   ww = w * w;  for c in r, g, b, in that order:  vnum_c = vnum_c + ww * var_qc          (var_q: step A's var of the tap's pixel)
+ * and after the loop  var_out_c = (vnum_c / wsum) / wsum.  A pixel with valid_p == 0 gives var_out = (0, 0, 0).  float32 without
+ * contraction, IEEE division, in the order written, as the rest of step B.  d_rgb_out and d_wsum have the bits nori_hip_denoise
+ * gives on the same frames; d_var_out is height * width * 3 floats in d_rgb_out's layout.  var_out is the variance of the output
+ * under FIXED weights and independent pixel means: sum_q w_q^2 var_q / (sum_q w_q)^2.
+ * tiles: n_tiles raster ids of NORI_TILE_SIZE^2 tiles in HOST memory, strictly ascending -- checked and refused as for
+ * nori_hip_render_tiles --, or NULL: the whole frame.  With a list only the pixels of the listed tiles are written (one workgroup
+ * per listed tile; guide records are made for the whole frame, because windows reach into neighbouring tiles), and they have the
+ * bits of the whole-frame call.  The list is copied to device memory of the context's: the call synchronises `stream` once for
+ * the upload and replaces the context's current tile list, as nori_hip_select_tiles does.  tiles != NULL with n_tiles == 0
+ * succeeds and touches nothing.  Otherwise as nori_hip_denoise: asynchronous on `stream`, the same errors, and
+ * NORI_ERR_INVALID_ARGUMENT for d_var_out == NULL.
+ *
+ * The error of a denoised pixel, with rgb, var, wsum as nori_hip_denoise_var wrote them -- the form of nori_hip_error_map's
+ * formula, so a target means the same thing for the raw and the denoised frame:
+ *   if !(wsum > 0): err = 0 and the pixel counts as empty; else num = 0, den = 0 and
+ *   for c in r, g, b:  num = num + sqrt(var_c);  den = den + |rgb_c|
+ *   err = num / (den + 0.03f)
+ * nori_hip_denoised_error_map writes err per pixel to d_err (height * width floats, or NULL) and the summary to out (or NULL; one
+ * of the two must be given), reduced in the fixed order of nori_hip_error_map's summary, with its synchronisation rules: with out
+ * the call synchronises `stream`, without it is asynchronous and uses nothing of the context's.  nori_hip_denoised_tile_errors is
+ * nori_hip_tile_errors for this error: one 256-thread workgroup per tile, thread ly * 16 + lx, 0 outside the frame, the binary64
+ * tree off = 128 .. 1, tile_err = (float) (sum / n); asynchronous on `stream`.  No atomics anywhere.  The _host twins take HOST
+ * buffers and are synchronous.
+ *
+ * nori_hip_render_adaptive_denoised is nori_hip_render_adaptive with the tiles retired on the denoised tile errors.  The active set
+ * starts as all tiles; d_rgb_out, d_var_out and d_wsum are zeroed.  Pass k renders its sample range of the active tiles with
+ * moments, ADDING into d_rgbw and d_m2, and adds to tile_spp, exactly as nori_hip_render_adaptive.  From the second pass on each
+ * pass is followed by step A over the whole frame, the variance filter over the ACTIVE tiles only (the list as the selection left
+ * it in device memory), nori_hip_denoised_tile_errors of the outputs, and the selection: the active set is replaced by its members
+ * with !(tile_err <= target_tile_err).  A retired tile never returns.  The loop stops when the set is empty or the samples are
+ * spent; then step A and the filter run once over the WHOLE frame (the neighbours of a retired tile have changed since it was last
+ * filtered), so the outputs are nori_hip_denoise_var of the frames as they are left.  The retiring can be replayed from outside:
+ * the active tiles' filtered pixels are those of a whole-frame nori_hip_denoise_var of the frames after that pass.
+ * d_albedo, d_normal, d_depth: feature frames the caller rendered (nori_hip_render_features), each may be NULL.  denoise_params
+ * NULL: the defaults.  d_tile_spp may be NULL.  out (may be NULL): as nori_adaptive_summary says, frame being the summary of the
+ * denoised error map of the outputs (threshold = target); n_unconverged = the tiles active when the loop stopped, or, if only one
+ * pass ran, the tiles whose final denoised tile error is not <= target.  Arguments are checked as for nori_hip_render_adaptive and
+ * nori_hip_denoise, with the same codes.  Synchronous.  The _host twin renders into zeroed scratch frames, takes the feature frames
+ * from HOST memory and writes rgbw, rgb_out and, where not NULL, m2, var_out, wsum, err (the denoised error map) and tile_spp.
+ * Limits.  The estimate holds the weights fixed -- they are functions of the same noisy means -- and takes the pixels' means as
+ * independent; it carries no bias term, so what the filter blurs away is not counted.  Under pixel filters wider than the box
+ * neighbouring pixels share samples and the estimate is low.  Below about 16 samples per pixel the weights themselves are
+ * unreliable.  One device only.  Not built: a dual-buffer (cross-filtered) estimate. */
+int nori_hip_denoise_var(nori_hip_ctx *ctx, const nori_denoise_params *params /* NULL: the defaults */, const void *d_rgbw, const void *d_m2,
+                         const void *d_albedo, const void *d_normal, const void *d_depth,
+                         const uint32_t *tiles /* HOST, strictly ascending, or NULL: the whole frame */, uint32_t n_tiles,
+                         void *d_rgb_out, void *d_var_out, void *d_wsum /* may be NULL */, void *stream);
+int nori_hip_denoise_var_host(nori_hip_ctx *ctx, const nori_denoise_params *params, const float *rgbw, const float *m2, const float *albedo,
+                              const float *normal, const float *depth, const uint32_t *tiles, uint32_t n_tiles,
+                              float *rgb_out, float *var_out, float *wsum /* may be NULL */);
+int nori_hip_denoised_error_map(nori_hip_ctx *ctx, const void *d_rgb, const void *d_var, const void *d_wsum,
+                                void *d_err /* height*width floats, may be NULL */, float threshold, nori_error_summary *out, void *stream);
+int nori_hip_denoised_error_map_host(nori_hip_ctx *ctx, const float *rgb, const float *var, const float *wsum, float *err /* may be NULL */,
+                                     float threshold, nori_error_summary *out);
+int nori_hip_denoised_tile_errors(nori_hip_ctx *ctx, const void *d_rgb, const void *d_var, const void *d_wsum,
+                                  void *d_tile_err /* tiles_x*tiles_y floats */, void *stream);
+int nori_hip_denoised_tile_errors_host(nori_hip_ctx *ctx, const float *rgb, const float *var, const float *wsum, float *tile_err);
+int nori_hip_render_adaptive_denoised(nori_hip_ctx *ctx, const nori_render_params *params /* spp_count = the most a pixel may get */,
+                                      uint32_t pass_spp, float target_tile_err, const nori_denoise_params *denoise_params /* NULL: the defaults */,
+                                      void *d_rgbw, void *d_m2, const void *d_albedo, const void *d_normal, const void *d_depth /* each may be NULL */,
+                                      void *d_rgb_out, void *d_var_out, void *d_wsum,
+                                      void *d_tile_spp /* tiles_x*tiles_y uint32, may be NULL; overwritten */,
+                                      nori_adaptive_summary *out, nori_render_stats *stats);
+int nori_hip_render_adaptive_denoised_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_tile_err,
+                                           const nori_denoise_params *denoise_params, float *rgbw, float *m2, const float *albedo,
+                                           const float *normal, const float *depth, float *rgb_out, float *var_out, float *wsum,
+                                           float *err, uint32_t *tile_spp, nori_adaptive_summary *out, nori_render_stats *stats);
+
 /* film_order = "reference" shared out over devices or ranks.  The reference adds a 32x32 block's samples consecutively
  * into the block's own ImageBlock (renderBlock, src/main.cpp:27-55) and the blocks into the frame in BlockGenerator's order
  * (src/block.cpp:93-152): the smallest share that keeps the order is a block, the one handed out here is a ROW of blocks.

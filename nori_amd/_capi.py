@@ -210,6 +210,16 @@ HIP_PROTOTYPES = {
     "nori_hip_denoise": (C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, _P, _P]),
     "nori_hip_denoise_guides_host": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "nori_hip_denoise_host": (C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, _P]),
+    "nori_hip_denoise_var": (C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P]),
+    "nori_hip_denoise_var_host": (C.c_int, [_P, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P]),
+    "nori_hip_denoised_error_map": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.POINTER(ErrorSummary), _P]),
+    "nori_hip_denoised_error_map_host": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.POINTER(ErrorSummary)]),
+    "nori_hip_denoised_tile_errors": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "nori_hip_denoised_tile_errors_host": (C.c_int, [_P, _P, _P, _P, _P]),
+    "nori_hip_render_adaptive_denoised": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_float, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P,
+                                                    _P, _P, _P, _P, C.POINTER(AdaptiveSummary), C.POINTER(RenderStats)]),
+    "nori_hip_render_adaptive_denoised_host": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_float, C.POINTER(DenoiseParams), _P, _P, _P, _P, _P,
+                                                         _P, _P, _P, _P, _P, C.POINTER(AdaptiveSummary), C.POINTER(RenderStats)]),
     "nori_hip_error_map": (C.c_int, [_P, _P, _P, _P, C.c_float, C.POINTER(ErrorSummary), _P]),
     "nori_hip_error_map_host": (C.c_int, [_P, _P, _P, _P, C.c_float, C.POINTER(ErrorSummary)]),
     "nori_hip_render_to_error": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_float, _P, _P, C.POINTER(C.c_uint32),

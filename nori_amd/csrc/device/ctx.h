@@ -11,6 +11,7 @@
 #include "film_tiles.h"
 #include "features.h"
 #include "denoise.h"
+#include "denoise_error.h"
 #include "scene_prep.h"
 #include "wavefront.h"
 #include "render_plan.h"
@@ -56,6 +57,7 @@ struct nori_hip_ctx {
     FilmTiles tiles;          /* renders by tile list, tile selection, the adaptive loop: lists, inverse table, tile errors (film_tiles.h) */
     FeatureStore features;    /* nori_hip_render_features: a sample plane and a set of tile accumulators per feature (features.h) */
     DenoiseStore denoise;     /* nori_hip_denoise: the guide records between its two kernels, a buffer per stream (denoise.h) */
+    DenoiseErrorStore denoise_error;      /* nori_hip_denoised_error_map: the partial sums of its summary (denoise_error.h) */
 };
 
 #define HIP_TRY(ctx, expr)                                                                         \

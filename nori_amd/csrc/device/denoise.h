@@ -23,6 +23,8 @@
  *                                  default R = 5, F = 1 and 49088 at R = 8, F = 2: every instantiation stays below the 64 KiB a
  *                                  workgroup gets without opting in, so the large window is served by the same kernel with a
  *                                  larger static array, features from memory in both.
+ *                                  Its body is one __device__ function in denoise_filter.h, which denoise_error.hip compiles a second
+ *                                  time with the accumulators of the output's variance (denoise_error.h).
  * No atomics: the same frames give the same bytes.
  */
 #pragma once

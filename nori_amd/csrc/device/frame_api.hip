@@ -1,6 +1,7 @@
 /* frame_api.hip -- the frame-level half of the C ABI of include/nori_hip.h: nori_hip_render and what is built on it (moments, error map,
- * render to an error, tile lists, selection, the adaptive loop, feature frames, the denoiser, block rows) and the _host twins.  No kernel
- * lives here: every render ends in render_impl (nori_hip.hip), everything else in film.hip / film_tiles.hip / features.hip / denoise.hip. */
+ * render to an error, tile lists, selection, the adaptive loop, feature frames, the denoiser, the denoiser with its error and the loop that
+ * stops on it, block rows) and the _host twins.  No kernel lives here: every render ends in render_impl (nori_hip.hip), everything else in
+ * film.hip / film_tiles.hip / features.hip / denoise.hip / denoise_error.hip. */
 #include <cstring>
 #include <initializer_list>
 #include "ctx.h"      /* (the HIP runtime, <algorithm>, <string>, <vector>) */
@@ -9,7 +10,7 @@
 #define RC_TRY(expr) do { if (int rc__ = (expr)) return rc__; } while (0)
 
 /* The device side of a _host twin: ONE allocation per call (hipMalloc is slow, and the adaptive CLI path calls these per frame), cut
-   into the parts in order (at most 8) and freed on every return path; call(d) gets their device addresses.  A render ADDS into its
+   into the parts in order (at most 12) and freed on every return path; call(d) gets their device addresses.  A render ADDS into its
    frames, so the render twins ask for zero; the twins that upload zero nothing.  The downloads are blocking copies: behind the
    kernels of the default stream -- a call that queued work on another stream synchronises it itself. */
 struct HostPart { size_t bytes; const void *in; void *out; };      /* in: uploaded before the call, out: downloaded after it; NULL: not */
@@ -21,7 +22,7 @@ static int host_twin(nori_hip_ctx *ctx, bool zero, std::initializer_list<HostPar
     Scratch buf;
     HIP_TRY(ctx, hipMalloc(&buf.p, std::max<size_t>(total, 16)));
     if (zero) HIP_TRY(ctx, hipMemset(buf.p, 0, total));
-    char *d[8], *at = (char *) buf.p;
+    char *d[12], *at = (char *) buf.p;
     int n = 0;
     for (const HostPart &p : parts) { d[n++] = at; if (p.in) HIP_TRY(ctx, hipMemcpy(at, p.in, p.bytes, hipMemcpyHostToDevice)); at += p.bytes; }
     RC_TRY(call(d));
@@ -437,6 +438,198 @@ int nori_hip_denoise_host(nori_hip_ctx *ctx, const nori_denoise_params *params, 
     const size_t fb = frame_bytes(ctx);
     return host_twin(ctx, false, {DENOISE_IN, {3 * pixel_bytes(ctx), nullptr, rgb_out}, {pixel_bytes(ctx), nullptr, wsum}},
                      [&](char **d) { return nori_hip_denoise(ctx, params, DENOISE_ARGS, d[5], wsum ? d[6] : nullptr, nullptr); });
+}
+
+/* ---- the denoiser with its output variance, the error of a denoised frame, the loop that stops on it (denoise_error.h) ---- */
+
+/* steps A and B with the variance on `stream`: over the tiles of d_list (DEVICE), or, d_list null, over the whole frame */
+static int denoise_var_run(nori_hip_ctx *ctx, DenoiseLaunch dl, const void *d_rgbw, const void *d_m2, const void *d_albedo, const void *d_normal,
+                           const void *d_depth, const uint32_t *d_list, uint32_t n_list, void *d_rgb_out, void *d_var_out, void *d_wsum, void *stream) {
+    dl.width = ctx->host.camera.width; dl.height = ctx->host.camera.height;
+    dl.terms = (d_albedo ? kDenoiseAlbedo : 0u) | (d_normal ? kDenoiseNormal : 0u) | (d_depth ? kDenoiseDepth : 0u);
+    float *d_guides = nullptr;
+    const std::string err = denoise_store_guides(ctx->denoise, stream, (size_t) dl.width * (size_t) dl.height, &d_guides);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_OUT_OF_MEMORY; }
+    HIP_TRY(ctx, denoise_guides_launch(dl.width, dl.height, ctx->host.filter.border, (const float *) d_rgbw, (const float *) d_m2, (const float *) d_albedo,
+                                       (const float *) d_normal, (const float *) d_depth, d_guides, stream));
+    HIP_TRY(ctx, denoise_filter_var_launch(dl, d_guides, d_list, n_list, (float *) d_rgb_out, (float *) d_var_out, (float *) d_wsum, stream));
+    return NORI_OK;
+}
+
+int nori_hip_denoise_var(nori_hip_ctx *ctx, const nori_denoise_params *params, const void *d_rgbw, const void *d_m2, const void *d_albedo,
+                         const void *d_normal, const void *d_depth, const uint32_t *tiles, uint32_t n_tiles, void *d_rgb_out, void *d_var_out,
+                         void *d_wsum, void *stream) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    RC_TRY(denoise_frames_ok(ctx, d_rgbw, d_m2, d_rgb_out, "denoise_var"));
+    if (!d_var_out) { ctx->error = "denoise_var: needs a buffer for the variance"; return NORI_ERR_INVALID_ARGUMENT; }
+    DenoiseLaunch dl;
+    const std::string bad = denoise_plan(params, dl);
+    if (!bad.empty()) { ctx->error = bad; return NORI_ERR_INVALID_ARGUMENT; }
+    DeviceGuard g(ctx->device);
+    const uint32_t *d_list = nullptr;
+    if (tiles) {
+        RC_TRY(check_tile_list(ctx, "denoise_var", tiles, n_tiles));
+        if (n_tiles == 0) return NORI_OK;      /* nothing is touched */
+        const std::string err = film_tiles_upload(ctx->tiles, tiles, n_tiles, frame_tiles(ctx), stream);
+        if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+        d_list = ctx->tiles.list[ctx->tiles.cur];
+    }
+    return denoise_var_run(ctx, dl, d_rgbw, d_m2, d_albedo, d_normal, d_depth, d_list, n_tiles, d_rgb_out, d_var_out, d_wsum, stream);
+}
+
+int nori_hip_denoise_var_host(nori_hip_ctx *ctx, const nori_denoise_params *params, const float *rgbw, const float *m2, const float *albedo,
+                              const float *normal, const float *depth, const uint32_t *tiles, uint32_t n_tiles, float *rgb_out, float *var_out, float *wsum) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    RC_TRY(denoise_frames_ok(ctx, rgbw, m2, rgb_out, "denoise_var"));
+    if (!var_out) { ctx->error = "denoise_var: needs a buffer for the variance"; return NORI_ERR_INVALID_ARGUMENT; }
+    const size_t fb = frame_bytes(ctx), pb = pixel_bytes(ctx);
+    /* (with a list the buffers go up as well as down: the pixels of the other tiles come back as they went) */
+    return host_twin(ctx, false, {DENOISE_IN, {3 * pb, tiles ? rgb_out : nullptr, rgb_out}, {3 * pb, tiles ? var_out : nullptr, var_out}, {pb, tiles ? wsum : nullptr, wsum}},
+                     [&](char **d) { return nori_hip_denoise_var(ctx, params, DENOISE_ARGS, tiles, n_tiles, d[5], d[6], wsum ? d[7] : nullptr, nullptr); });
+}
+
+static int denoised_frames_ok(nori_hip_ctx *ctx, const void *rgb, const void *var, const void *wsum, bool out, const char *what) {
+    if (!rgb || !var || !wsum || !out) { ctx->error = std::string(what) + ": needs the denoised frame, its variance, its weight sums and something to fill"; return NORI_ERR_INVALID_ARGUMENT; }
+    return NORI_OK;
+}
+
+int nori_hip_denoised_error_map(nori_hip_ctx *ctx, const void *d_rgb, const void *d_var, const void *d_wsum, void *d_err, float threshold,
+                                nori_error_summary *out, void *stream) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    RC_TRY(denoised_frames_ok(ctx, d_rgb, d_var, d_wsum, d_err || out, "denoised_error_map"));
+    DeviceGuard g(ctx->device);
+    FilmErrorSummary sum;
+    const std::string err = denoised_error_map(ctx->denoise_error, ctx->host.camera.width, ctx->host.camera.height, (const float *) d_rgb, (const float *) d_var,
+                                               (const float *) d_wsum, (float *) d_err, threshold, out ? &sum : nullptr, stream);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        out->sum_err = sum.sum_err; out->max_err = sum.max_err; out->threshold = threshold;
+        out->n_pixels = sum.n_pixels; out->n_empty = sum.n_empty; out->n_above = sum.n_above;
+    }
+    return NORI_OK;
+}
+
+int nori_hip_denoised_error_map_host(nori_hip_ctx *ctx, const float *rgb, const float *var, const float *wsum, float *err, float threshold, nori_error_summary *out) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    RC_TRY(denoised_frames_ok(ctx, rgb, var, wsum, err || out, "denoised_error_map"));
+    const size_t pb = pixel_bytes(ctx);
+    return host_twin(ctx, false, {{3 * pb, rgb, nullptr}, {3 * pb, var, nullptr}, {pb, wsum, nullptr}, {pb, nullptr, err}},
+                     [&](char **d) { return nori_hip_denoised_error_map(ctx, d[0], d[1], d[2], err ? d[3] : nullptr, threshold, out, nullptr); });
+}
+
+int nori_hip_denoised_tile_errors(nori_hip_ctx *ctx, const void *d_rgb, const void *d_var, const void *d_wsum, void *d_tile_err, void *stream) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    RC_TRY(denoised_frames_ok(ctx, d_rgb, d_var, d_wsum, d_tile_err != nullptr, "denoised_tile_errors"));
+    DeviceGuard g(ctx->device);
+    const std::string err = denoised_tile_errors(ctx->host.camera.width, ctx->host.camera.height, (const float *) d_rgb, (const float *) d_var, (const float *) d_wsum,
+                                                 (float *) d_tile_err, stream);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    return NORI_OK;
+}
+
+int nori_hip_denoised_tile_errors_host(nori_hip_ctx *ctx, const float *rgb, const float *var, const float *wsum, float *tile_err) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    RC_TRY(denoised_frames_ok(ctx, rgb, var, wsum, tile_err != nullptr, "denoised_tile_errors"));
+    const size_t pb = pixel_bytes(ctx);
+    return host_twin(ctx, false, {{3 * pb, rgb, nullptr}, {3 * pb, var, nullptr}, {pb, wsum, nullptr}, {(size_t) frame_tiles(ctx) * sizeof(float), nullptr, tile_err}},
+                     [&](char **d) { return nori_hip_denoised_tile_errors(ctx, d[0], d[1], d[2], d[3], nullptr); });
+}
+
+int nori_hip_render_adaptive_denoised(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_tile_err,
+                                      const nori_denoise_params *denoise_params, void *d_rgbw, void *d_m2, const void *d_albedo, const void *d_normal,
+                                      const void *d_depth, void *d_rgb_out, void *d_var_out, void *d_wsum, void *d_tile_spp,
+                                      nori_adaptive_summary *out, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !d_rgbw || !d_m2) return NORI_ERR_INVALID_ARGUMENT;
+    if (!d_rgb_out || !d_var_out || !d_wsum) { ctx->error = "render_adaptive_denoised: needs buffers for the denoised frame, its variance and its weight sums"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (pass_spp == 0) { ctx->error = "render_adaptive_denoised: pass_spp must be at least 1"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (!(target_tile_err >= 0.0f)) { ctx->error = "render_adaptive_denoised: the target error must be a number >= 0"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (params->tile_mod != 1) { ctx->error = "render_adaptive_denoised: renders whole frames (tile_mod 1): the loop shares the tiles out itself"; return NORI_ERR_INVALID_ARGUMENT; }
+    RC_TRY(check_tiles_params(ctx, params, nullptr));
+    DenoiseLaunch dl;
+    const std::string bad = denoise_plan(denoise_params, dl);
+    if (!bad.empty()) { ctx->error = bad; return NORI_ERR_INVALID_ARGUMENT; }
+    DeviceGuard g(ctx->device);
+    hipStream_t s = (hipStream_t) params->stream;
+    FilmTiles &T = ctx->tiles;
+    const uint32_t n_frame = frame_tiles(ctx);
+    const size_t n_pixels = (size_t) ctx->host.camera.width * (size_t) ctx->host.camera.height;
+    {      /* the active set starts as all tiles */
+        std::vector<uint32_t> all(n_frame);
+        for (uint32_t i = 0; i < n_frame; ++i) all[i] = i;
+        const std::string err = film_tiles_upload(T, all.data(), n_frame, n_frame, s);
+        if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    }
+    HIP_TRY(ctx, hipMemsetAsync(T.tile_spp, 0, (size_t) n_frame * sizeof(uint32_t), s));
+    HIP_TRY(ctx, hipMemsetAsync(d_rgb_out, 0, n_pixels * 3 * sizeof(float), s));
+    HIP_TRY(ctx, hipMemsetAsync(d_var_out, 0, n_pixels * 3 * sizeof(float), s));
+    HIP_TRY(ctx, hipMemsetAsync(d_wsum, 0, n_pixels * sizeof(float), s));
+    auto tile_errors = [&]() -> int {      /* of the outputs as they stand, into T.tile_err */
+        const std::string err = denoised_tile_errors(ctx->host.camera.width, ctx->host.camera.height, (const float *) d_rgb_out, (const float *) d_var_out,
+                                                     (const float *) d_wsum, T.tile_err, s);
+        if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+        return NORI_OK;
+    };
+    nori_render_stats total; memset(&total, 0, sizeof(total));
+    uint32_t done = 0, passes = 0;
+    while (done < params->spp_count && T.n > 0) {
+        nori_render_params p = *params;
+        p.spp_begin = params->spp_begin + done; p.spp_count = std::min(pass_spp, params->spp_count - done);
+        nori_render_stats st;
+        RC_TRY(render_impl(ctx, &p, d_rgbw, &st, nullptr, (float *) d_m2, &T));
+        add_stats(total, st);
+        film_tiles_add_spp(T, T.tile_spp, p.spp_count, s);
+        done += p.spp_count; ++passes;
+        if (passes >= 2) {      /* (one pass of few samples has no variance to speak of) */
+            /* guide records of the whole frame, the filter over the active tiles alone: the list as the selection left it on the device */
+            RC_TRY(denoise_var_run(ctx, dl, d_rgbw, d_m2, d_albedo, d_normal, d_depth, T.list[T.cur], T.n, d_rgb_out, d_var_out, d_wsum, s));
+            RC_TRY(tile_errors());
+            const std::string err = film_tiles_select(T, T.tile_err, target_tile_err, n_frame, s);
+            if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+        }
+    }
+    /* the outputs: the whole frame once more -- the neighbours of a retired tile have changed since it was last filtered */
+    RC_TRY(denoise_var_run(ctx, dl, d_rgbw, d_m2, d_albedo, d_normal, d_depth, nullptr, 0, d_rgb_out, d_var_out, d_wsum, s));
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        uint32_t n_unconverged = T.n;
+        if (passes < 2) {      /* no evaluation was made: the final frame is measured once, without retiring anything */
+            RC_TRY(tile_errors());
+            std::vector<float> te(n_frame);
+            HIP_TRY(ctx, hipMemcpyAsync(te.data(), T.tile_err, (size_t) n_frame * sizeof(float), hipMemcpyDeviceToHost, s));
+            HIP_TRY(ctx, hipStreamSynchronize(s));
+            n_unconverged = 0;
+            for (uint32_t i = 0; i < n_frame; ++i) n_unconverged += !(te[i] <= target_tile_err) ? 1u : 0u;
+        }
+        std::vector<uint32_t> spp(n_frame);
+        HIP_TRY(ctx, hipMemcpyAsync(spp.data(), T.tile_spp, (size_t) n_frame * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        out->passes = passes; out->n_tiles = n_frame; out->n_unconverged = n_unconverged;
+        out->spp_min = *std::min_element(spp.begin(), spp.end()); out->spp_max = *std::max_element(spp.begin(), spp.end());
+        RC_TRY(nori_hip_denoised_error_map(ctx, d_rgb_out, d_var_out, d_wsum, nullptr, target_tile_err, &out->frame, params->stream));
+    }
+    if (d_tile_spp) HIP_TRY(ctx, hipMemcpyAsync(d_tile_spp, T.tile_spp, (size_t) n_frame * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    if (stats) *stats = total;
+    return NORI_OK;
+}
+
+int nori_hip_render_adaptive_denoised_host(nori_hip_ctx *ctx, const nori_render_params *params, uint32_t pass_spp, float target_tile_err,
+                                           const nori_denoise_params *denoise_params, float *rgbw, float *m2, const float *albedo, const float *normal,
+                                           const float *depth, float *rgb_out, float *var_out, float *wsum, float *err, uint32_t *tile_spp,
+                                           nori_adaptive_summary *out, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !rgbw || !rgb_out) return NORI_ERR_INVALID_ARGUMENT;
+    const size_t fb = frame_bytes(ctx), pb = pixel_bytes(ctx);
+    /* parts 0 .. 9 = rgbw, m2, albedo, normal, depth, rgb_out, var_out, wsum, err, tile_spp */
+    return host_twin(ctx, true, {{fb, nullptr, rgbw}, {fb, nullptr, m2}, {fb, albedo, nullptr}, {fb, normal, nullptr}, {fb, depth, nullptr}, {3 * pb, nullptr, rgb_out},
+                                 {3 * pb, nullptr, var_out}, {pb, nullptr, wsum}, {pb, nullptr, err}, {(size_t) frame_tiles(ctx) * sizeof(uint32_t), nullptr, tile_spp}}, [&](char **d) -> int {
+        RC_TRY(nori_hip_render_adaptive_denoised(ctx, params, pass_spp, target_tile_err, denoise_params, d[0], d[1], albedo ? d[2] : nullptr, normal ? d[3] : nullptr,
+                                                 depth ? d[4] : nullptr, d[5], d[6], d[7], d[9], out, stats));
+        if (err) { RC_TRY(nori_hip_denoised_error_map(ctx, d[5], d[6], d[7], d[8], target_tile_err, nullptr, params->stream)); HIP_TRY(ctx, hipStreamSynchronize((hipStream_t) params->stream)); }
+        return NORI_OK;
+    });
 }
 
 int nori_hip_block_acc_floats(nori_hip_ctx *ctx, size_t *n_floats) {

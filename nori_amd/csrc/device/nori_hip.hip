@@ -542,6 +542,7 @@ void nori_hip_destroy(nori_hip_ctx *ctx) {
     film_tiles_release(ctx->tiles);
     feature_store_release(ctx->features);
     denoise_store_release(ctx->denoise);
+    denoise_error_release(ctx->denoise_error);
     if (ctx->d_stats) (void) hipFree(ctx->d_stats);
     delete ctx;
 }

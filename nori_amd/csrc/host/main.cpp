@@ -1,5 +1,5 @@
 /*
- * main.cpp -- `nori <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]] [--denoise [--denoise-radius R] [--denoise-patch F]]`
+ * main.cpp -- `nori <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]] [--denoise [--denoise-radius R] [--denoise-patch F]] [--target-denoised-error E [--pass-spp K] [--feature-spp K] [--denoise-radius R] [--denoise-patch F]]`
  * Command line of the reference (src/main.cpp:150-246).  There is no GUI on a
  * compute node: --no-gui is accepted and implied; --threads is accepted for
  * compatibility (the work runs on the GPU).  --seed block renders with the
@@ -22,7 +22,11 @@
  * three feature frames with the scene's sample count (or --feature-spp), runs nori_hip_denoise over
  * them -- window radius --denoise-radius (1..8, default 5), patch radius --denoise-patch (0..2,
  * default 1) -- and writes <scene>.denoised.exr beside the usual output; one device only, not
- * together with --target-error.  A <test> root runs during parsing
+ * together with --target-error.  --target-denoised-error E renders the three feature frames first (K = --feature-spp, default
+ * min(sampleCount, 16)), then runs nori_hip_render_adaptive_denoised: passes of --pass-spp samples per pixel over the 16x16 tiles
+ * whose DENOISED error (nori_hip_denoised_tile_errors) is still above E, the scene's sampleCount being the most a pixel gets.  It
+ * writes the usual output (the raw frame), <scene>.denoised.exr, <scene>.error.exr (the denoised error map) and <scene>.spp.exr and
+ * prints where it stopped; one device only, not together with --denoise, --target-error or --adaptive.  A <test> root runs during parsing
  * (its activate()), as in the reference; failures exit with -1.
  */
 #include <nori/bitmap.h>
@@ -32,13 +36,14 @@ using namespace nori;
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        cerr << "Syntax: " << argv[0] << " <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]] [--denoise [--denoise-radius R] [--denoise-patch F]]" << endl;
+        cerr << "Syntax: " << argv[0] << " <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]] [--denoise [--denoise-radius R] [--denoise-patch F]] [--target-denoised-error E [--pass-spp K] [--feature-spp K] [--denoise-radius R] [--denoise-patch F]]" << endl;
         return -1;
     }
     std::string sceneName;
     bool toError = false, havePassSpp = false, adaptive = false, features = false, haveFeatureSpp = false;
     long featureSpp = 16;
     bool denoise = false, haveDenoiseRadius = false, haveDenoisePatch = false;
+    bool toDenoisedError = false;
     long denoiseRadius = 5, denoisePatch = 1;
     float targetError = 0.0f;
     long passSpp = 16;
@@ -77,6 +82,15 @@ int main(int argc, char **argv) {
                 return -1;
             }
             toError = true; ++i;
+            continue;
+        } else if (token == "--target-denoised-error") {
+            char *end = nullptr;
+            if (i + 1 < argc) targetError = std::strtof(argv[i + 1], &end);
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !(targetError >= 0.0f) || std::isinf(targetError)) {
+                cerr << "Usage: \"--target-denoised-error\" expects a relative error of the denoised frame >= 0 following it, e.g. --target-denoised-error 0.02 [--pass-spp K]." << endl;
+                return -1;
+            }
+            toDenoisedError = true; ++i;
             continue;
         } else if (token == "--pass-spp") {
             char *end = nullptr;
@@ -137,7 +151,15 @@ int main(int argc, char **argv) {
             cerr << "Fatal error: unknown file \"" << token << "\", expected an extension of type .xml or .exr" << endl;
         }
     }
-    if (havePassSpp && !toError) {
+    if (toDenoisedError && (denoise || toError || adaptive)) {
+        cerr << "Usage: \"--target-denoised-error\" is a loop of its own and does not go with " << (denoise ? "--denoise" : toError ? "--target-error" : "--adaptive") << "." << endl;
+        return -1;
+    }
+    if (toDenoisedError && gpus > 1) {
+        cerr << "Usage: \"--target-denoised-error\" renders on one device: moment and feature frames over several GPUs are not supported (got --gpus " << gpus << ")." << endl;
+        return -1;
+    }
+    if (havePassSpp && !toError && !toDenoisedError) {
         cerr << "Usage: \"--pass-spp\" goes with --target-error E." << endl;
         return -1;
     }
@@ -149,11 +171,11 @@ int main(int argc, char **argv) {
         cerr << "\"--target-error\" renders on one device: moment frames over several GPUs are not supported (got --gpus " << gpus << ")." << endl;
         return -1;
     }
-    if (haveFeatureSpp && !features && !denoise) {
+    if (haveFeatureSpp && !features && !denoise && !toDenoisedError) {
         cerr << "Usage: \"--feature-spp\" goes with --features (or --denoise)." << endl;
         return -1;
     }
-    if ((haveDenoiseRadius || haveDenoisePatch) && !denoise) {
+    if ((haveDenoiseRadius || haveDenoisePatch) && !denoise && !toDenoisedError) {
         cerr << "Usage: \"" << (haveDenoiseRadius ? "--denoise-radius" : "--denoise-patch") << "\" goes with --denoise." << endl;
         return -1;
     }
@@ -189,8 +211,10 @@ int main(int argc, char **argv) {
             std::vector<float> denoised;
             nori_denoise_params dn = NORI_DENOISE_PARAMS_DEFAULT;
             dn.radius = (uint32_t) denoiseRadius; dn.patch = (uint32_t) denoisePatch;
-            const uint32_t denoiseFeatureSpp = haveFeatureSpp ? (uint32_t) featureSpp : (uint32_t) scene->getSampler()->getSampleCount();
-            std::unique_ptr<ImageBlock> result = denoise ? renderSceneDenoised(scene, dn, denoiseFeatureSpp, denoised, &st)
+            const uint32_t denoiseFeatureSpp = haveFeatureSpp ? (uint32_t) featureSpp
+                                               : toDenoisedError ? (uint32_t) std::min<size_t>(scene->getSampler()->getSampleCount(), 16) : (uint32_t) scene->getSampler()->getSampleCount();
+            std::unique_ptr<ImageBlock> result = toDenoisedError ? renderSceneAdaptiveDenoised(scene, targetError, (uint32_t) passSpp, dn, denoiseFeatureSpp, adaptiveSummary, denoised, errorMap, tileSpp, &st)
+                                                 : denoise ? renderSceneDenoised(scene, dn, denoiseFeatureSpp, denoised, &st)
                                                  : adaptive ? renderSceneAdaptive(scene, targetError, (uint32_t) passSpp, adaptiveSummary, errorMap, tileSpp, &st)
                                                  : toError ? renderSceneToError(scene, targetError, (uint32_t) passSpp, sppDone, summary, errorMap, &st)
                                                          : renderScene(scene, &st);
@@ -202,10 +226,10 @@ int main(int argc, char **argv) {
             if (lastdot != std::string::npos) outputName.erase(lastdot, std::string::npos);
             bitmap->saveEXR(outputName);
             bitmap->savePNG(outputName);
-            if (adaptive) {
+            if (adaptive || toDenoisedError) {
                 const nori_error_summary &f = adaptiveSummary.frame;
-                cout << "Stopped after " << adaptiveSummary.passes << " passes: " << adaptiveSummary.spp_min << " to " << adaptiveSummary.spp_max << " samples per pixel, "
-                     << adaptiveSummary.n_unconverged << " of " << adaptiveSummary.n_tiles << " tiles above the target " << targetError << "; mean error "
+                cout << (toDenoisedError ? "Denoised error: stopped after " : "Stopped after ") << adaptiveSummary.passes << " passes: " << adaptiveSummary.spp_min << " to " << adaptiveSummary.spp_max << " samples per pixel, "
+                     << adaptiveSummary.n_unconverged << " of " << adaptiveSummary.n_tiles << " tiles above the target " << targetError << (toDenoisedError ? "; mean predicted error of the denoised frame " : "; mean error ")
                      << f.sum_err / (double) std::max<uint64_t>(f.n_pixels, 1) << " (max " << f.max_err << ", " << f.n_above << " of " << f.n_pixels << " pixels above the target)" << endl;
                 Bitmap errorBitmap(scene->getCamera()->getOutputSize()), sppBitmap(scene->getCamera()->getOutputSize());
                 const int tilesX = ((int) errorBitmap.cols() + NORI_TILE_SIZE - 1) / NORI_TILE_SIZE;
@@ -225,7 +249,7 @@ int main(int argc, char **argv) {
                         errorBitmap.set(y, x, Color3f(errorMap[(size_t) y * errorBitmap.cols() + x]));
                 errorBitmap.saveEXR(outputName + ".error");
             }
-            if (denoise) {
+            if (denoise || toDenoisedError) {
                 Bitmap db(scene->getCamera()->getOutputSize());
                 for (int y = 0; y < db.rows(); ++y)
                     for (int x = 0; x < db.cols(); ++x) {

@@ -319,4 +319,11 @@ void renderSceneFeatures(Scene *scene, uint32_t spp, std::vector<float> &albedo,
 std::unique_ptr<ImageBlock> renderSceneDenoised(Scene *scene, const nori_denoise_params &dn, uint32_t featureSpp, std::vector<float> &denoised,
                                                 nori_render_stats *stats = nullptr);
 
+/* `--target-denoised-error E`: the three feature frames through renderSceneFeatures, then nori_hip_render_adaptive_denoised_host --
+   passes over the tiles whose DENOISED error is still above E.  The returned block is the raw frame; `denoised` receives height *
+   width * 3 floats, `errorMap` the denoised error map, `tileSpp` the samples every 16x16 tile received */
+std::unique_ptr<ImageBlock> renderSceneAdaptiveDenoised(Scene *scene, float targetError, uint32_t passSpp, const nori_denoise_params &dn, uint32_t featureSpp,
+                                                        nori_adaptive_summary &summary, std::vector<float> &denoised, std::vector<float> &errorMap,
+                                                        std::vector<uint32_t> &tileSpp, nori_render_stats *stats = nullptr);
+
 NORI_NAMESPACE_END

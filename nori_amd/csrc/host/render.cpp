@@ -184,4 +184,38 @@ std::unique_ptr<ImageBlock> renderSceneDenoised(Scene *scene, const nori_denoise
     return result;
 }
 
+std::unique_ptr<ImageBlock> renderSceneAdaptiveDenoised(Scene *scene, float targetError, uint32_t passSpp, const nori_denoise_params &dn, uint32_t featureSpp,
+                                                        nori_adaptive_summary &summary, std::vector<float> &denoised, std::vector<float> &errorMap,
+                                                        std::vector<uint32_t> &tileSpp, nori_render_stats *stats) {
+    const Camera *camera = scene->getCamera();
+    scene->getIntegrator()->preprocess(scene);
+    if (const char *gpus = std::getenv("NORI_GPUS"))
+        if (std::atoi(gpus) > 1) throw NoriException("--target-denoised-error renders on one device: moment and feature frames over a device group are not supported (got --gpus %s)", gpus);
+    if (const char *seed = std::getenv("NORI_SEED"))
+        if (std::string(seed) == "block") throw NoriException("--target-denoised-error renders in passes, which --seed block cannot (a block's stream is serial from sample 0)");
+    std::unique_ptr<ImageBlock> result(new ImageBlock(camera->getOutputSize(), camera->getReconstructionFilter()));
+    result->clear();
+    const int w = camera->getOutputSize().x(), h = camera->getOutputSize().y();
+    const size_t n = (size_t) w * h;
+    denoised.assign(n * 3, 0.0f);
+    errorMap.assign(n, 0.0f);
+    tileSpp.assign((size_t) ((w + NORI_TILE_SIZE - 1) / NORI_TILE_SIZE) * ((h + NORI_TILE_SIZE - 1) / NORI_TILE_SIZE), 0u);
+    std::vector<float> fa, fn, fd;
+    int border = 0;
+    renderSceneFeatures(scene, featureSpp, fa, fn, fd, border);      /* first: the loop is guided by them from its second pass on */
+
+    nori_render_params params;
+    std::memset(&params, 0, sizeof(params));
+    params.spp_begin = 0;
+    params.spp_count = (uint32_t) scene->getSampler()->getSampleCount();      /* the most a pixel may get */
+    params.tile_mod = 1; params.tile_rem = 0;
+    params.seed_mode = NORI_SEED_PER_SAMPLE;
+    nori_render_stats local;
+    Device &dev = scene->device();
+    dev.check(nori_hip_render_adaptive_denoised_host(dev.ctx(), &params, passSpp, targetError, &dn, result->data(), nullptr, fa.data(), fn.data(), fd.data(),
+                                                     denoised.data(), nullptr, nullptr, errorMap.data(), tileSpp.data(), &summary, stats ? stats : &local),
+              "nori_hip_render_adaptive_denoised_host");
+    return result;
+}
+
 NORI_NAMESPACE_END

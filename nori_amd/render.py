@@ -503,6 +503,124 @@ class Renderer:
         d = [C.c_void_p(t.data_ptr()) if t is not None else None for t in (rgbw, m2, albedo, normal, depth, guides)]
         self._check(self._lib.nori_hip_denoise_guides(self._h, *d, raw), "denoise_guides")
 
+    # -- the denoiser with its output variance, the error of a denoised frame, the loop that stops on it (nori_hip_denoise_var) --
+    def _pixel_shapes(self):
+        c = self.scene.camera
+        return (c.height, c.width, 3), (c.height, c.width)
+
+    def _is_pixels(self, t, shape):
+        return t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape and str(t.dtype) == "torch.float32"
+
+    def denoise_var_into(self, rgb_out, var_out, rgbw, m2, albedo=None, normal=None, depth=None, wsum=None, tiles=None, stream=None, **params):
+        """denoise_into with the variance of the output under fixed weights into var_out (height, width, 3).  tiles: strictly
+        ascending raster ids -- only those tiles' pixels are written (the call then synchronises `stream` once) -- or None: the
+        whole frame."""
+        rgb_shape, px_shape = self._pixel_shapes()
+        assert self._is_frame(rgbw) and self._is_frame(m2)
+        for t in (albedo, normal, depth):
+            assert t is None or self._is_frame(t)
+        assert self._is_pixels(rgb_out, rgb_shape) and self._is_pixels(var_out, rgb_shape) and (wsum is None or self._is_pixels(wsum, px_shape))
+        p = capi.DenoiseParams(**params)
+        raw = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        d = [C.c_void_p(t.data_ptr()) if t is not None else None for t in (rgbw, m2, albedo, normal, depth)]
+        o = [C.c_void_p(t.data_ptr()) if t is not None else None for t in (rgb_out, var_out, wsum)]
+        tl = None if tiles is None else self._tile_list(tiles)
+        self._check(self._lib.nori_hip_denoise_var(self._h, C.byref(p), *d, ptr(tl) if tl is not None else None, 0 if tl is None else tl.shape[0], *o, raw), "denoise_var")
+
+    def denoise_var_host(self, rgbw, m2, albedo=None, normal=None, depth=None, tiles=None, out=None, **params):
+        """Host frames: (rgb, var (height, width, 3), wsum (height, width)).  With `tiles` only the listed tiles' pixels of `out`
+        -- a triple of arrays to write into, fresh zeros by default -- are written."""
+        frames = self._host_frames(rgbw, m2, albedo, normal, depth)
+        rgb_shape, px_shape = self._pixel_shapes()
+        rgb, var, wsum = out if out is not None else (np.zeros(rgb_shape, np.float32), np.zeros(rgb_shape, np.float32), np.zeros(px_shape, np.float32))
+        assert rgb.shape == var.shape == rgb_shape and wsum.shape == px_shape and all(a.dtype == np.float32 for a in (rgb, var, wsum))
+        p = capi.DenoiseParams(**params)
+        tl = None if tiles is None else self._tile_list(tiles)
+        self._check(self._lib.nori_hip_denoise_var_host(self._h, C.byref(p), *[ptr(a) for a in frames], ptr(tl) if tl is not None else None,
+                                                        0 if tl is None else tl.shape[0], ptr(rgb), ptr(var), ptr(wsum)), "denoise_var_host")
+        return rgb, var, wsum
+
+    def denoised_error_map(self, rgb, var, wsum, threshold=0.0, want_map=True, stream=None):
+        """error_map for a denoised frame, its variance and its weight sums (as denoise_var writes them): (err (height, width),
+        summary dict).  Torch CUDA tensors give a CUDA map; numpy arrays are copied to the device and give a numpy map."""
+        rgb_shape, px_shape = self._pixel_shapes()
+        s = capi.ErrorSummary()
+        if isinstance(rgb, np.ndarray):
+            rgb, var, wsum = (np.ascontiguousarray(a, dtype=np.float32) for a in (rgb, var, wsum))
+            assert rgb.shape == var.shape == rgb_shape and wsum.shape == px_shape
+            err = np.zeros(px_shape, np.float32) if want_map else None
+            self._check(self._lib.nori_hip_denoised_error_map_host(self._h, ptr(rgb), ptr(var), ptr(wsum), ptr(err), float(threshold), C.byref(s)), "denoised_error_map_host")
+            return err, s.as_dict()
+        import torch
+        assert self._is_pixels(rgb, rgb_shape) and self._is_pixels(var, rgb_shape) and self._is_pixels(wsum, px_shape)
+        err = torch.empty(px_shape, dtype=torch.float32, device=rgb.device) if want_map else None
+        raw = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._check(self._lib.nori_hip_denoised_error_map(self._h, C.c_void_p(rgb.data_ptr()), C.c_void_p(var.data_ptr()), C.c_void_p(wsum.data_ptr()),
+                                                          C.c_void_p(err.data_ptr()) if err is not None else None, float(threshold), C.byref(s), raw), "denoised_error_map")
+        return err, s.as_dict()
+
+    def denoised_tile_errors(self, rgb, var, wsum, stream=None):
+        """tile_errors for a denoised frame: (tiles_y, tiles_x) float32, a CUDA tensor for CUDA tensors, a numpy array for numpy arrays."""
+        rgb_shape, px_shape = self._pixel_shapes()
+        if isinstance(rgb, np.ndarray):
+            rgb, var, wsum = (np.ascontiguousarray(a, dtype=np.float32) for a in (rgb, var, wsum))
+            assert rgb.shape == var.shape == rgb_shape and wsum.shape == px_shape
+            out = np.zeros(self.tile_grid(), np.float32)
+            self._check(self._lib.nori_hip_denoised_tile_errors_host(self._h, ptr(rgb), ptr(var), ptr(wsum), ptr(out)), "denoised_tile_errors_host")
+            return out
+        import torch
+        assert self._is_pixels(rgb, rgb_shape) and self._is_pixels(var, rgb_shape) and self._is_pixels(wsum, px_shape)
+        out = torch.empty(self.tile_grid(), dtype=torch.float32, device=rgb.device)
+        raw = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._check(self._lib.nori_hip_denoised_tile_errors(self._h, C.c_void_p(rgb.data_ptr()), C.c_void_p(var.data_ptr()), C.c_void_p(wsum.data_ptr()),
+                                                            C.c_void_p(out.data_ptr()), raw), "denoised_tile_errors")
+        return out
+
+    def render_adaptive_denoised(self, rgbw_tensor, m2_tensor, target_tile_err, albedo=None, normal=None, depth=None, pass_spp=16, spp_count=None,
+                                 spp_begin=0, stream=None, count_traversal=False, time_kernels=False, seed_mode=capi.SEED_PER_SAMPLE, tile_mod=1, **params):
+        """render_adaptive with the tiles retired on the error of the DENOISED frame: accumulates into both frame tensors; albedo,
+        normal, depth are feature frames rendered beforehand (render_features_into), each optional; params: nori_denoise_params.
+        Returns (rgb_out, var_out (height, width, 3), wsum (height, width), tile_spp (tiles_y, tiles_x) int32 -- CUDA tensors --,
+        summary dict, stats dict); the first three are denoise_var of the frames as they are left."""
+        import torch
+        assert self._is_frame(rgbw_tensor) and self._is_frame(m2_tensor)
+        for t in (albedo, normal, depth):
+            assert t is None or self._is_frame(t)
+        rgb_shape, px_shape = self._pixel_shapes()
+        spp = self.scene.sample_count if spp_count is None else spp_count
+        raw = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        p = self._params(spp_begin, spp, tile_mod, 0, count_traversal, raw, time_kernels, seed_mode)
+        dp = capi.DenoiseParams(**params)
+        dev = rgbw_tensor.device
+        rgb, var = torch.empty(rgb_shape, dtype=torch.float32, device=dev), torch.empty(rgb_shape, dtype=torch.float32, device=dev)
+        wsum, tile_spp = torch.empty(px_shape, dtype=torch.float32, device=dev), torch.zeros(self.tile_grid(), dtype=torch.int32, device=dev)
+        out, st = capi.AdaptiveSummary(), capi.RenderStats()
+        d = [C.c_void_p(t.data_ptr()) if t is not None else None for t in (rgbw_tensor, m2_tensor, albedo, normal, depth, rgb, var, wsum, tile_spp)]
+        self._check(self._lib.nori_hip_render_adaptive_denoised(self._h, C.byref(p), int(pass_spp), float(target_tile_err), C.byref(dp), *d, C.byref(out), C.byref(st)),
+                    "render_adaptive_denoised")
+        return rgb, var, wsum, tile_spp, out.as_dict(), st.as_dict()
+
+    def render_adaptive_denoised_host(self, target_tile_err, albedo=None, normal=None, depth=None, pass_spp=16, spp_count=None, spp_begin=0,
+                                      count_traversal=False, **params):
+        """The same loop into fresh host arrays; returns a dict: rgbw, m2, rgb, var, wsum, err (the denoised error map), tile_spp,
+        summary, stats."""
+        feats = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (albedo, normal, depth)]
+        for a in feats:
+            assert a is None or a.shape == tuple(self.frame_shape())
+        rgb_shape, px_shape = self._pixel_shapes()
+        spp = self.scene.sample_count if spp_count is None else spp_count
+        p = self._params(spp_begin, spp, 1, 0, count_traversal, None)
+        dp = capi.DenoiseParams(**params)
+        r = dict(rgbw=np.zeros(self.frame_shape(), np.float32), m2=np.zeros(self.frame_shape(), np.float32), rgb=np.zeros(rgb_shape, np.float32),
+                 var=np.zeros(rgb_shape, np.float32), wsum=np.zeros(px_shape, np.float32), err=np.zeros(px_shape, np.float32),
+                 tile_spp=np.zeros(self.tile_grid(), np.uint32))
+        out, st = capi.AdaptiveSummary(), capi.RenderStats()
+        self._check(self._lib.nori_hip_render_adaptive_denoised_host(self._h, C.byref(p), int(pass_spp), float(target_tile_err), C.byref(dp), ptr(r["rgbw"]), ptr(r["m2"]),
+                                                                     *[ptr(a) for a in feats], ptr(r["rgb"]), ptr(r["var"]), ptr(r["wsum"]), ptr(r["err"]),
+                                                                     ptr(r["tile_spp"]), C.byref(out), C.byref(st)), "render_adaptive_denoised_host")
+        r["summary"], r["stats"] = out.as_dict(), st.as_dict()
+        return r
+
     # -- film_order = reference shared out: rows of 32x32 blocks (include/nori_hip.h: nori_hip_render_block_rows) --
     def block_rows(self) -> int:
         """rows of 32x32 blocks (NORI_BLOCK_SIZE) in the frame"""
