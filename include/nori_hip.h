@@ -484,6 +484,25 @@ int nori_hip_debug_emitter_sample(nori_hip_ctx *ctx, int reader /* nori_tables_r
 int nori_hip_debug_emitter_tables(nori_hip_ctx *ctx, uint32_t counts[3], uint32_t *emitters, uint32_t *cdf_offset,
                                   uint32_t *n_triangles, float *inv_area, float *cdf);
 
+/* wf_extend -- the traversal kernel of the wavefront engine -- on n rays of the caller's choosing, all arrays in HOST memory.
+ * Slot k is a stored path vertex as wf_shade would have left it: origin origins[3 k ..] (both rays start there, with the mint every
+ * stored ray has, 1e-4), a continuation ray dir_a[3 k ..] (slot A: closest hit, maxt = inf) and / or a shadow ray dir_b[4 k ..] =
+ * (d.xyz, maxt) (slot B: any hit), as flags[k] says: 0 (empty slot: nothing is traced), 1 (A), 2 | 4 (B, the path ends on it) or
+ * 1 | 2 (B, then A, by the same lane).  The directions of a slot the flags do not name are not read.  The records go into the
+ * context's path-state pool and ONE launch over stored paths is made, with the kernel variant, stack, persistent grid, thresholds
+ * and NORI_HIP_WF_* knobs a render of this scene would use.
+ * hits[4 k ..] = (t, u, v, hit word) as the kernel wrote them: the closest hit of A -- (inf, 0, 0) without one, or without A --, the
+ * word's low 31 bits the GLOBAL triangle index (a mesh's triangles follow those of the meshes before it) or 0x7fffffff, bit 31 =
+ * B was occluded.  An empty slot keeps the four words NORI_EXTEND_SENTINEL the array is filled with before the launch.
+ * counts = {closest-hit queries, shadow queries, node tests, triangle tests}; the last two are counted with count_traversal != 0,
+ * by the kernels a render with nori_render_params::count_traversal runs.
+ * NORI_ERR_INVALID_ARGUMENT, before anything is launched: n larger than the option "wavefront_paths" (or than the 2^29 records a
+ * pool can index), a flag word other than those four, a non-finite origin, direction component or maxt (maxt = +inf is a valid
+ * value) or a direction of all zeros in a slot the flags name.  n == 0 launches nothing.  Needs an acceleration structure. */
+#define NORI_EXTEND_SENTINEL 0xcdcdcdcdu
+int nori_hip_debug_extend(nori_hip_ctx *ctx, const float *origins, const float *dir_a, const float *dir_b, const uint32_t *flags, size_t n,
+                          int count_traversal, float *hits, unsigned long long counts[4]);
+
 /* pcg32::nextFloat stream (Independent::next1D, src/independent.cpp:46-48):
  * out[k*count + j] = j-th float of pcg32.seed(seed_state[k], seed_seq[k]). */
 int nori_hip_pcg32_floats(nori_hip_ctx *ctx, const uint64_t *seed_state,

@@ -23,6 +23,9 @@ WARP_NAMES = {"square": 0, "tent": 1, "disk": 2, "uniform_sphere": 3,
               "uniform_hemisphere": 4, "cosine_hemisphere": 5, "beckmann": 6}
 ARITH_OP_NAMES = {"rcp": 0, "div": 1, "div_shared": 2, "sqrt": 3, "slab_rcp": 4, "sin": 5, "cos": 6, "log": 7, "exp": 8}      # nori_arith_op
 TABLES_READER_NAMES = {"global": 0, "redirected": 1, "lds": 2}      # nori_tables_reader
+F_HAS_A, F_HAS_B, F_END_AFTER_B = 1, 2, 4      # flag words of nori_hip_debug_extend (wf_records.h)
+EXTEND_SENTINEL = 0xCDCDCDCD      # NORI_EXTEND_SENTINEL
+EXTEND_MISS_A, EXTEND_OCCLUDED_B = 0x7FFFFFFF, 0x80000000      # the hit word: low 31 bits without a closest hit, bit 31
 TEXTURE_NAMES = {"image": 0, "checkerboard": 1}
 TEXTURE_FILTER_NAMES = {"nearest": 0, "bilinear": 1}
 TEXTURE_WRAP_NAMES = {"repeat": 0, "clamp": 1}
@@ -197,6 +200,7 @@ HIP_PROTOTYPES = {
     "nori_hip_debug_arith": (C.c_int, [_P, C.c_int, _P, _P, C.c_size_t, _P]),
     "nori_hip_debug_emitter_sample": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, _P, _P]),
     "nori_hip_debug_emitter_tables": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "nori_hip_debug_extend": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_int, _P, _P]),
     "nori_hip_pcg32_floats": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, _P]),
     "nori_hip_pcg32_floats_at": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_size_t, C.c_uint32, _P]),
     "nori_hip_splat": (C.c_int, [_P, _P, _P, C.c_size_t, _P]),

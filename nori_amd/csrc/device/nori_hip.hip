@@ -1017,6 +1017,41 @@ int nori_hip_debug_emitter_tables(nori_hip_ctx *ctx, uint32_t counts[3], uint32_
     return NORI_OK;
 }
 
+int nori_hip_debug_extend(nori_hip_ctx *ctx, const float *origins, const float *dir_a, const float *dir_b, const uint32_t *flags, size_t n,
+                          int count_traversal, float *hits, unsigned long long counts[4]) {
+    REQUIRE_ACCEL(ctx);
+    if (!counts) { ctx->error = "debug_extend: counts must not be NULL"; return NORI_ERR_INVALID_ARGUMENT; }
+    for (int k = 0; k < 4; ++k) counts[k] = 0;
+    if (n == 0) return NORI_OK;
+    if (!origins || !dir_a || !dir_b || !flags || !hits) { ctx->error = "debug_extend: origins, dir_a, dir_b, flags and hits must not be NULL"; return NORI_ERR_INVALID_ARGUMENT; }
+    const size_t most = wavefront_trace_max_rays(ctx->wavefront_paths);
+    if (n > most) { ctx->error = "debug_extend: " + std::to_string(n) + " rays, the pool of this context may hold " + std::to_string(most) + " (option wavefront_paths)"; return NORI_ERR_INVALID_ARGUMENT; }
+    /* a stored ray is a finite origin and a finite direction that is not zero; only a shadow ray's maxt may be +inf */
+    const auto finite = [](float x) { return x - x == 0.0f; };
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t fl = flags[i];
+        if (fl != 0u && fl != 1u && fl != 6u && fl != 3u) { ctx->error = "debug_extend: flags[" + std::to_string(i) + "] = " + std::to_string(fl) + " is none of 0, 1, 2 | 4, 1 | 2"; return NORI_ERR_INVALID_ARGUMENT; }
+        if (fl == 0u) continue;
+        bool ok = finite(origins[3 * i]) && finite(origins[3 * i + 1]) && finite(origins[3 * i + 2]);
+        if (fl & 1u) {
+            const float *d = dir_a + 3 * i;
+            ok = ok && finite(d[0]) && finite(d[1]) && finite(d[2]) && (d[0] != 0.0f || d[1] != 0.0f || d[2] != 0.0f);
+        }
+        if (fl & 2u) {
+            const float *d = dir_b + 4 * i;
+            ok = ok && finite(d[0]) && finite(d[1]) && finite(d[2]) && (d[0] != 0.0f || d[1] != 0.0f || d[2] != 0.0f) && (finite(d[3]) || d[3] > 0.0f);
+        }
+        if (!ok) { ctx->error = "debug_extend: slot " + std::to_string(i) + " holds a non-finite origin, direction or maxt, or a direction of zeros"; return NORI_ERR_INVALID_ARGUMENT; }
+    }
+    DeviceGuard g(ctx->device);
+    const std::string err = wavefront_trace(*ctx->wf, ctx->dev, (int) ctx->bvh.max_depth + 1, count_traversal != 0, origins, dir_a, dir_b, flags, n, hits, counts);
+    if (!err.empty()) {
+        ctx->error = "debug_extend: " + err;
+        return err.find("out of memory") != std::string::npos ? NORI_ERR_OUT_OF_MEMORY : NORI_ERR_INTERNAL;
+    }
+    return NORI_OK;
+}
+
 int nori_hip_pcg32_floats(nori_hip_ctx *ctx, const uint64_t *seed_state, const uint64_t *seed_seq, size_t n, uint32_t count, float *out) {
     return nori_hip_pcg32_floats_at(ctx, seed_state, seed_seq, 0, n, count, out);
 }

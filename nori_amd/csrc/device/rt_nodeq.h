@@ -24,7 +24,8 @@
  * A tree qualifies if its root is an inner node and no box is unbounded (numerically collinear triangles, rt_types.h);
  * otherwise there are no 32-B records and wf_extend walks the 64-B nodes.  Both forms describe the same tree: same
  * links, same leaves.  The CPU harness walks either (tests/emu), which is how the conservativeness is tested
- * without a GPU: hits identical to the linear scan for every ray.
+ * without a GPU: hits identical to the linear scan for every ray -- and on the GPU, where the hand-written loop itself
+ * is given rays (tests/test_gpu_extend.py through nori_hip_debug_extend): every hit record identical to the linear scan's.
  */
 #pragma once
 #include "rt_types.h"

@@ -176,11 +176,18 @@ NORI_HD void trav_inner_step(const DevScene &sc, Stack &stack, Trav &tv, Travers
        that meets the box far from its origin; where the origin is close to a large box the error is absolute,
        <= 4 u (|c - o| + h) |r|, a tenth of the padding every leaf box carries (kBoxPadRel) for origins within the scene */
     fl *= 1.0000006f; fr *= 1.0000006f;
+    /* The near side carries the same error and is held to the ray's far limit, which after a hit is that hit's t: a box that
+       holds a hit of the SAME t (coplanar triangles of different leaves -- the scan reports the one with the larger index) or of
+       one ulp less starts, exactly, no later than that t minus the box's padding.  For an origin within the scene the padding
+       covers the error; for one thousands of scene sizes away the error, 4 u t, is hundreds of times the padding, and the box was
+       culled (tests/test_gpu_extend.py, rays of class D on coplanar sheets: 48 of 6000 records named another triangle than the
+       scan).  So the limit is widened by the same 10 u. */
+    const float limit = tv.hit.t * 1.0000006f;
     /* the box interval is clipped against [0, far limit], not [mint, ...]: a ray that leaves a surface at a
        grazing angle can re-hit its own triangle at a t that is pure rounding noise yet >= mint (the
        reference's scan reports it), while the ray is outside the triangle's box by then */
-    const bool hl = (nl <= fl) && (fl >= 0.0f) && (nl <= tv.hit.t);
-    const bool hr = (nr <= fr) && (fr >= 0.0f) && (nr <= tv.hit.t);
+    const bool hl = (nl <= fl) && (fl >= 0.0f) && (nl <= limit);
+    const bool hr = (nr <= fr) && (fr >= 0.0f) && (nr <= limit);
     const int cl = (int) f2u(q3.x), cr = (int) f2u(q3.y);
     if (hl && hr) {
         const bool leftFirst = nl <= nr;

@@ -57,6 +57,15 @@ size_t wavefront_held_bytes(const WfEngine *engine, const FilmStore &film);
 std::string wavefront_render(WfEngine &engine, FilmStore &film_store, const DevScene &sc, const float *d_filter_table,
                              const WfLaunch &launch, float *d_rgbw, void *stream, WfStats &stats);
 
+/* wf_extend on rays the caller brings (nori_hip_debug_extend, include/nori_hip.h): n records written into state copy 0 as wf_shade
+ * would have stored them, ONE launch over the stored paths -- planned by the function that plans a render's launches, environment
+ * knobs included --, then the hit records (4n floats, untouched slots keep NORI_EXTEND_SENTINEL) and counts[4] = closest-hit
+ * queries, shadow queries, node tests, triangle tests (the last two in counting launches).  All arrays in HOST memory, checked by
+ * the caller; n <= wavefront_trace_max_rays(the context's wavefront_paths).  Synchronous on the default stream. */
+size_t wavefront_trace_max_rays(size_t max_paths);
+std::string wavefront_trace(WfEngine &engine, const DevScene &sc, int stack_depth, bool count_traversal, const float *origins, const float *dir_a,
+                            const float *dir_b, const uint32_t *flags, size_t n, float *hits, unsigned long long counts[4]);
+
 /* node records of the LDS image (rt_top.h) that fit next to wf_extend's traversal stacks, per node layout */
 int wf_top_capacity(bool wide_nodes, bool records_32b, bool deeper_than_lds_stack);
 

@@ -1161,6 +1161,104 @@ static WfBuf slice(const WfBuf &b, size_t off, size_t records, int k) {
     return v;
 }
 
+/* How a context launches wf_extend on a scene's tree -- what launch_extend_dyn and WfBatch are handed, the knobs of the environment
+   included -- decided in ONE place for the two callers: a render's passes (wavefront_render) and the rays a caller brings itself
+   (wavefront_trace), so that the second is held to the launch the first makes. */
+struct ExtendPlan {
+    int thresholds = 0;             /* refill | leaf << 8 | static paths per wave << 16 | dynamic divisor << 28 (wf_extend) */
+    int lds_stack = 16;             /* traversal-stack entries kept in LDS */
+    bool spill = false;             /* the tree needs more than that (or has wide nodes) */
+    int extend_cus = 0;             /* CUs the persistent grid fills */
+    int grid = 0, grid_first = 0;   /* workgroups: passes over stored paths / the launch of a pass's new paths */
+    int inner_repeat = 24;
+    uint32_t batch_flags = 0;       /* kBatchNoAsmLoop | kBatchCountQ */
+    int finish_paths = 0, finish_grid = 0;      /* fewer live paths than this: wf_finish ends the batch; its grid */
+    size_t spill_ints_per_pipe = 0; /* of pool.spill, allocated here (0: no walk leaves the LDS stack) */
+};
+
+static std::string plan_extend(const WfEngine &eng, Pool &g_pool, const DevScene &sc, int stack_depth, bool count_traversal, int n_pipes, int split_cus, ExtendPlan &plan) {
+    const bool split = split_cus > 0;
+    int refill = 32;
+    if (const char *e = getenv("NORI_HIP_WF_REFILL")) refill = std::min(64, std::max(1, atoi(e)));
+    /* lanes at a leaf before a triangle step runs: 16 on BVH2 trees; 8 on wide trees, whose node steps are twice as long and whose
+       waves hold fewer lanes per step (terrain, trace ms at 16 / 8 / 4: 54.2 / 53.3 / 53.2; the AO scene's BVH2 walk: 62.1 / 62.6 at 8;
+       profiles/r4_05_sweeps.txt) */
+    int leaf_th = sc.wide ? 8 : 16;
+    if (const char *e = getenv("NORI_HIP_WF_LEAF")) leaf_th = std::min(64, std::max(1, atoi(e)));
+    int static_per_wave = 1024, dyn_div = 8;      /* chunking of wf_extend: all-static below static_per_wave paths per wave, else n / (waves * dyn_div) per claim */
+    if (const char *e = getenv("NORI_HIP_WF_STATIC")) static_per_wave = std::min(4095, std::max(0, atoi(e)));
+    if (const char *e = getenv("NORI_HIP_WF_DYNDIV")) dyn_div = std::min(15, std::max(1, atoi(e)));
+    plan.thresholds = refill | (leaf_th << 8) | (static_per_wave << 16) | (dyn_div << 28);
+    /* persistent extend grid: fill the CUs, but with two pipes leave half of the wave slots to
+       the other pipe's kernels */
+    /* traversal stack: what the tree needs, at most `lds_stack` entries of it in LDS */
+    /* 16 entries in LDS, deeper walks spill to HBM: a stack of 24 entries costs three of the eight workgroups per CU, and walks
+       rarely hold more than 16 deferred subtrees however deep the tree (measured, trace ms at 16 / 24 entries: table scene,
+       depth 19: 77.5 / 83.0; Cornell box with the device builders' deeper trees: 61.6 / 74.8 and 73.3 / 82.1) */
+    const bool no_asm_loop = getenv("NORI_HIP_WF_NO_ASM_LOOP") != nullptr && atoi(getenv("NORI_HIP_WF_NO_ASM_LOOP")) != 0;
+    int lds_stack = 16;
+    if (const char *e = getenv("NORI_HIP_WF_STACK")) lds_stack = atoi(e) <= 16 ? 16 : atoi(e) <= 24 ? 24 : 32;
+    int finish_paths = 524288;           /* fewer live paths than this: wf_finish ends the batch */
+    if (const char *e = getenv("NORI_HIP_WF_FINISH_PATHS")) finish_paths = std::max(256, atoi(e)) & ~255;
+    const int finish_grid = finish_paths / kB;
+    plan.finish_paths = finish_paths; plan.finish_grid = finish_grid;
+    /* LDS per workgroup: stack entries (+1: the "done" marker of the non-spilling stack) + the top-node cache */
+    const int extend_block = sc.wide ? kExtendBlockWide : kExtendBlockBvh2;
+    /* which node loop wf_extend will run (launch_extend): the hand-written one on 32-B records, or the compiler's on 64-B nodes */
+    const bool walk_q = !sc.wide && sc.nodes_q != nullptr && sc.n_triangles < (1u << 25) && !no_asm_loop;      /* 32-B node records */
+    const bool node_loop_q = walk_q && !count_traversal;         /* ... by the hand-written loop */
+    const bool count_q = walk_q && count_traversal;              /* ... by its C++ statement, counting (the same tree form as the timed kernel's) */
+    bool spill = false;
+    size_t lds_per_wg = 0;
+    while (true) {
+        spill = stack_depth > lds_stack || sc.wide != 0;
+        const int stack_entries = node_loop_q ? lds_stack + (spill ? 2 : 1) : lds_stack + (spill ? 0 : 1);      /* kLdsEntries of the kernel's stack class */
+        lds_per_wg = (size_t) stack_entries * extend_block * sizeof(int) + (size_t) std::max(1u, (node_loop_q || count_q) ? sc.top_image_q_quads : sc.top_image_quads) * sizeof(f4);
+        /* the LDS image was sized at build_accel for 16-entry stacks (wf_top_capacity): a bigger stack asked for at render time
+           (NORI_HIP_WF_STACK, an experiment knob) must not push a workgroup beyond its share of the CU's LDS -- fewer workgroups
+           per CU than the kernel is built for, or a launch that fails: back to the stack the image was sized for */
+        if (lds_stack > 16 && lds_per_wg > kLdsPerCu / (size_t) (sc.wide ? kExtendWgsWide : kExtendWgsBvh2)) { lds_stack = 16; continue; }
+        break;
+    }
+    plan.lds_stack = lds_stack; plan.spill = spill;
+    int per_cu = std::max(1, std::min(2048 / extend_block, (int) (kLdsPerCu / lds_per_wg)));      /* workgroups per CU */
+    /* every workgroup of the persistent grid must be resident from the start (a workgroup that starts late owns a
+       static share of the paths and works it off alone): the wide-node kernels are built for 7 waves per SIMD, their
+       first-pass variant (camera rays computed in the kernel: 77 - 87 registers) for 5.  (Terrain, 10 M triangles, wf_extend ms per
+       128 spp at 4 / 5 / 6 / 7 / 8 workgroups per CU: 65.7 / 57.8 / 53.9 / 53.6 / 54.2 -- the last two with the first pass still on the
+       same grid; how many records the LDS image holds does not matter there: 113, 40 or none, profiles/r4_07_c5_occupancy.txt.) */
+    if (sc.wide) per_cu = std::min(per_cu, kExtendWgsWide);
+    if (n_pipes > 1 && !split) per_cu = std::max(1, per_cu / 2);
+    if (const char *e = getenv("NORI_HIP_WF_EXTEND_WGS_PER_CU")) per_cu = std::min(2048 / extend_block, std::max(1, atoi(e)));
+    const int extend_cus = eng.n_cus - split_cus;      /* the persistent grid fills the CUs its stream owns (a tail beside it: some of its
+                                                          workgroups start when the tail's have left -- handing them their first chunk in
+                                                          the order they start instead of by position was measured and is no faster,
+                                                          profiles/r5_11_tail_overlap_c4.txt) */
+    plan.extend_cus = extend_cus;
+    plan.grid_first = extend_cus * (sc.wide ? std::min(per_cu, kExtendWgsWideFirst) : per_cu);
+    plan.grid = extend_cus * per_cu;
+    plan.spill_ints_per_pipe = 0;
+    if (stack_depth > 16) {      /* wf_finish keeps 16 entries in LDS */
+        const size_t per_pipe_ints = (size_t) (stack_depth - 16) * std::max(plan.grid * extend_block, finish_grid * kB), ints = per_pipe_ints * n_pipes;
+        if (g_pool.spill_ints < ints) {
+            if (g_pool.spill) (void) hipFree(g_pool.spill);
+            g_pool.spill = nullptr; g_pool.spill_ints = 0;
+            WF_TRY(hipMalloc((void **) &g_pool.spill, ints * sizeof(int)));
+            g_pool.spill_ints = ints;
+        }
+        plan.spill_ints_per_pipe = per_pipe_ints;
+    }
+    /* node steps repeat in a tight loop while >= 24 lanes of the wave are at inner nodes -- without the refill test, the leaf
+       vote and the rest of the trip's bookkeeping, which cost as much as the node step itself (measured, wf_extend: Cornell
+       box 51.7 -> 49.7 ms, 328 k-triangle AO 14.2 -> 12.8, table 77.7 -> 73.5, terrain 37.6 -> 34.7; the same loop
+       around the triangle step compiles with 56 B of scratch and runs 50 % slower) */
+    int inner_repeat = 24;
+    if (const char *e = getenv("NORI_HIP_WF_INNER_REPEAT")) inner_repeat = std::min(65, std::max(1, atoi(e)));
+    plan.inner_repeat = inner_repeat;
+    plan.batch_flags = (no_asm_loop ? kBatchNoAsmLoop : 0u) | (count_q ? kBatchCountQ : 0u);
+    return std::string();
+}
+
 std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScene &sc, const float *d_filter_table, const WfLaunch &L,
                              float *d_rgbw, void *stream_, WfStats &stats) {
     hipStream_t s = (hipStream_t) stream_;
@@ -1273,75 +1371,17 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
         for (int k = 0; k < n_pipes; ++k) { WF_TRY(hipStreamWaitEvent(pipes[k].stream, g_events[2], 0)); if (split) WF_TRY(hipStreamWaitEvent(pipes[k].extend_stream, g_events[2], 0)); }
     }
 
-    int refill = 32;
-    if (const char *e = getenv("NORI_HIP_WF_REFILL")) refill = std::min(64, std::max(1, atoi(e)));
-    /* lanes at a leaf before a triangle step runs: 16 on BVH2 trees; 8 on wide trees, whose node steps are twice as long and whose
-       waves hold fewer lanes per step (terrain, trace ms at 16 / 8 / 4: 54.2 / 53.3 / 53.2; the AO scene's BVH2 walk: 62.1 / 62.6 at 8;
-       profiles/r4_05_sweeps.txt) */
-    int leaf_th = sc.wide ? 8 : 16;
-    if (const char *e = getenv("NORI_HIP_WF_LEAF")) leaf_th = std::min(64, std::max(1, atoi(e)));
-    int static_per_wave = 1024, dyn_div = 8;      /* chunking of wf_extend: all-static below static_per_wave paths per wave, else n / (waves * dyn_div) per claim */
-    if (const char *e = getenv("NORI_HIP_WF_STATIC")) static_per_wave = std::min(4095, std::max(0, atoi(e)));
-    if (const char *e = getenv("NORI_HIP_WF_DYNDIV")) dyn_div = std::min(15, std::max(1, atoi(e)));
-    const int thresholds = refill | (leaf_th << 8) | (static_per_wave << 16) | (dyn_div << 28);
-    /* persistent extend grid: fill the CUs, but with two pipes leave half of the wave slots to
-       the other pipe's kernels */
-    /* traversal stack: what the tree needs, at most `lds_stack` entries of it in LDS */
-    /* 16 entries in LDS, deeper walks spill to HBM: a stack of 24 entries costs three of the eight workgroups per CU, and walks
-       rarely hold more than 16 deferred subtrees however deep the tree (measured, trace ms at 16 / 24 entries: table scene,
-       depth 19: 77.5 / 83.0; Cornell box with the device builders' deeper trees: 61.6 / 74.8 and 73.3 / 82.1) */
-    const bool no_asm_loop = getenv("NORI_HIP_WF_NO_ASM_LOOP") != nullptr && atoi(getenv("NORI_HIP_WF_NO_ASM_LOOP")) != 0;
-    int lds_stack = 16;
-    if (const char *e = getenv("NORI_HIP_WF_STACK")) lds_stack = atoi(e) <= 16 ? 16 : atoi(e) <= 24 ? 24 : 32;
-    int finish_paths = 524288;           /* fewer live paths than this: wf_finish ends the batch */
-    if (const char *e = getenv("NORI_HIP_WF_FINISH_PATHS")) finish_paths = std::max(256, atoi(e)) & ~255;
-    const int finish_grid = finish_paths / kB;
-    /* LDS per workgroup: stack entries (+1: the "done" marker of the non-spilling stack) + the top-node cache */
-    const int extend_block = sc.wide ? kExtendBlockWide : kExtendBlockBvh2;
-    /* which node loop wf_extend will run (launch_extend): the hand-written one on 32-B records, or the compiler's on 64-B nodes */
-    const bool walk_q = !sc.wide && sc.nodes_q != nullptr && sc.n_triangles < (1u << 25) && !no_asm_loop;      /* 32-B node records */
-    const bool node_loop_q = walk_q && !L.count_traversal;         /* ... by the hand-written loop */
-    const bool count_q = walk_q && L.count_traversal;              /* ... by its C++ statement, counting (the same tree form as the timed kernel's) */
-    bool spill = false;
-    size_t lds_per_wg = 0;
-    while (true) {
-        spill = L.stack_depth > lds_stack || sc.wide != 0;
-        const int stack_entries = node_loop_q ? lds_stack + (spill ? 2 : 1) : lds_stack + (spill ? 0 : 1);      /* kLdsEntries of the kernel's stack class */
-        lds_per_wg = (size_t) stack_entries * extend_block * sizeof(int) + (size_t) std::max(1u, (node_loop_q || count_q) ? sc.top_image_q_quads : sc.top_image_quads) * sizeof(f4);
-        /* the LDS image was sized at build_accel for 16-entry stacks (wf_top_capacity): a bigger stack asked for at render time
-           (NORI_HIP_WF_STACK, an experiment knob) must not push a workgroup beyond its share of the CU's LDS -- fewer workgroups
-           per CU than the kernel is built for, or a launch that fails: back to the stack the image was sized for */
-        if (lds_stack > 16 && lds_per_wg > kLdsPerCu / (size_t) (sc.wide ? kExtendWgsWide : kExtendWgsBvh2)) { lds_stack = 16; continue; }
-        break;
-    }
-    int per_cu = std::max(1, std::min(2048 / extend_block, (int) (kLdsPerCu / lds_per_wg)));      /* workgroups per CU */
-    /* every workgroup of the persistent grid must be resident from the start (a workgroup that starts late owns a
-       static share of the paths and works it off alone): the wide-node kernels are built for 7 waves per SIMD, their
-       first-pass variant (camera rays computed in the kernel: 77 - 87 registers) for 5.  (Terrain, 10 M triangles, wf_extend ms per
-       128 spp at 4 / 5 / 6 / 7 / 8 workgroups per CU: 65.7 / 57.8 / 53.9 / 53.6 / 54.2 -- the last two with the first pass still on the
-       same grid; how many records the LDS image holds does not matter there: 113, 40 or none, profiles/r4_07_c5_occupancy.txt.) */
-    if (sc.wide) per_cu = std::min(per_cu, kExtendWgsWide);
-    if (n_pipes > 1 && !split) per_cu = std::max(1, per_cu / 2);
-    if (const char *e = getenv("NORI_HIP_WF_EXTEND_WGS_PER_CU")) per_cu = std::min(2048 / extend_block, std::max(1, atoi(e)));
-    const int extend_cus = eng.n_cus - split_cus;      /* the persistent grid fills the CUs its stream owns (a tail beside it: some of its
-                                                          workgroups start when the tail's have left -- handing them their first chunk in
-                                                          the order they start instead of by position was measured and is no faster,
-                                                          profiles/r5_11_tail_overlap_c4.txt) */
-    const int extend_grid_first = extend_cus * (sc.wide ? std::min(per_cu, kExtendWgsWideFirst) : per_cu);
-    const int extend_grid = extend_cus * per_cu;
+    /* how wf_extend is launched on this scene (plan_extend: the knobs, the stack, the persistent grid, the spill buffer) */
+    ExtendPlan plan;
+    err = plan_extend(eng, g_pool, sc, L.stack_depth, L.count_traversal, n_pipes, split_cus, plan);
+    if (!err.empty()) return err;
+    const int thresholds = plan.thresholds, lds_stack = plan.lds_stack, extend_cus = plan.extend_cus, extend_grid = plan.grid, extend_grid_first = plan.grid_first;
+    const bool spill = plan.spill;
+    const int finish_paths = plan.finish_paths, finish_grid = plan.finish_grid;
+    for (int k = 0; k < n_pipes && plan.spill_ints_per_pipe != 0; ++k) pipes[k].b.stack_spill = g_pool.spill + plan.spill_ints_per_pipe * k;
     stats.trace_cus = (uint32_t) extend_cus; stats.tail_cus = (uint32_t) tail_cus;
     const bool compact = record_compact(sc);
     stats.record = compact ? NORI_WF_RECORD_COMPACT : NORI_WF_RECORD_FULL;
-    if (L.stack_depth > 16) {      /* wf_finish keeps 16 entries in LDS */
-        const size_t per_pipe_ints = (size_t) (L.stack_depth - 16) * std::max(extend_grid * extend_block, finish_grid * kB), ints = per_pipe_ints * n_pipes;
-        if (g_pool.spill_ints < ints) {
-            if (g_pool.spill) (void) hipFree(g_pool.spill);
-            g_pool.spill = nullptr; g_pool.spill_ints = 0;
-            WF_TRY(hipMalloc((void **) &g_pool.spill, ints * sizeof(int)));
-            g_pool.spill_ints = ints;
-        }
-        for (int k = 0; k < n_pipes; ++k) pipes[k].b.stack_spill = g_pool.spill + per_pipe_ints * k;
-    }
 
     /* wf_finish: the persistent form (a lane pulls path after path) on four workgroups per CU of the stream it runs on -- the pa5
        table scene's tail 22 -> 19 ms on all CUs, 223 -> 80 ms on 16 (profiles/r5_06_tail_probe_c4.txt) */
@@ -1353,12 +1393,6 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
     }
     struct { bool active = false; FilmLaunch fl; FilmStore film; } pend;      /* overlap: the batch whose tail is in flight -- its film gather is still to come */
 
-    /* node steps repeat in a tight loop while >= 24 lanes of the wave are at inner nodes -- without the refill test, the leaf
-       vote and the rest of the trip's bookkeeping, which cost as much as the node step itself (measured, wf_extend: Cornell
-       box 51.7 -> 49.7 ms, 328 k-triangle AO 14.2 -> 12.8, table 77.7 -> 73.5, terrain 37.6 -> 34.7; the same loop
-       around the triangle step compiles with 56 B of scratch and runs 50 % slower) */
-    int inner_repeat = 24;
-    if (const char *e = getenv("NORI_HIP_WF_INNER_REPEAT")) inner_repeat = std::min(65, std::max(1, atoi(e)));
     int sync_every = 6;      /* path-loop iterations between two readbacks of the path count */
     if (const char *e = getenv("NORI_HIP_WF_SYNC_EVERY")) sync_every = std::min(64, std::max(1, atoi(e)));
     const bool census = getenv("NORI_HIP_CENSUS") != nullptr;
@@ -1387,8 +1421,8 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
             P.bt.tile_first = P.t0; P.bt.n_tiles = nt; P.bt.s_first = L.spp_begin + P.s0; P.bt.n_spp = ns;
             P.bt.tile_mod = L.tile_mod; P.bt.tile_rem = L.tile_rem; P.bt.tiles_x = L.tiles_x; P.bt.tile_w = L.tile_w;
             P.bt.tile_list = L.tile_list;
-            P.bt.inner_repeat = inner_repeat;
-            P.bt.flags = (no_asm_loop ? kBatchNoAsmLoop : 0u) | (count_q ? kBatchCountQ : 0u);
+            P.bt.inner_repeat = plan.inner_repeat;
+            P.bt.flags = plan.batch_flags;
             P.bt.pool = (uint32_t) pool_paths;
             P.batch_samples = nt * 256u * ns;
             WF_TRY(hipMemsetAsync(P.b.ctr, 0, C_COUNT * sizeof(uint32_t), P.stream));
@@ -1545,6 +1579,56 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
                 z[Z_TRIPS], z[Z_INNER_TRIPS], (double) z[Z_INNER_LANES] / std::max(1ull, z[Z_INNER_TRIPS]), z[Z_LEAF_TRIPS],
                 (double) z[Z_LEAF_LANES] / std::max(1ull, z[Z_LEAF_TRIPS]), z[Z_REFILLS], (double) z[Z_REFILL_LANES] / std::max(1ull, z[Z_REFILLS]));
     }
+    return std::string();
+}
+
+size_t wavefront_trace_max_rays(size_t max_paths) {
+    /* a record's index is 30 bits of wf_extend's `rid`, and the pool holds state_capacity(n) records per copy */
+    size_t n = std::min<size_t>(max_paths, (size_t) 1 << 29);
+    while (n > 0 && state_capacity(n) >= ((size_t) 1 << 30)) n /= 2;
+    return n;
+}
+
+std::string wavefront_trace(WfEngine &eng, const DevScene &sc, int stack_depth, bool count_traversal, const float *origins, const float *dir_a,
+                            const float *dir_b, const uint32_t *flags, size_t n, float *hits, unsigned long long counts[4]) {
+    for (int k = 0; k < 4; ++k) counts[k] = 0;
+    if (n == 0) return std::string();
+    hipStream_t s = nullptr;
+    Pool &pool = eng.pool;
+    std::string err = ensure_pool(pool, state_capacity(n));
+    if (!err.empty()) return err;
+    ExtendPlan plan;
+    err = plan_extend(eng, pool, sc, stack_depth, count_traversal, 1, 0, plan);
+    if (!err.empty()) return err;
+    WfBuf b = slice(pool.buf, 0, pool.capacity, 0);
+    b.samp_pos = nullptr; b.samp_L = nullptr; b.census = nullptr;      /* (read by the launch of NEW paths and by counting builds under NORI_HIP_CENSUS only) */
+    if (plan.spill_ints_per_pipe != 0) b.stack_spill = pool.spill;
+    /* state copy 0 as wf_shade would have stored these paths (wf_records.h) */
+    std::vector<P3> o(n); std::vector<f4> dA(n), dB(n);
+    for (size_t i = 0; i < n; ++i) {
+        o[i].x = origins[3 * i]; o[i].y = origins[3 * i + 1]; o[i].z = origins[3 * i + 2];
+        f4 a; a.x = dir_a[3 * i]; a.y = dir_a[3 * i + 1]; a.z = dir_a[3 * i + 2]; a.w = kInf;
+        dA[i] = state_dA(a, flags[i], (flags[i] & F_HAS_A) != 0u);
+        dB[i].x = dir_b[4 * i]; dB[i].y = dir_b[4 * i + 1]; dB[i].z = dir_b[4 * i + 2]; dB[i].w = dir_b[4 * i + 3];
+    }
+    WF_TRY(hipMemcpy(b.st[0].o, o.data(), n * sizeof(P3), hipMemcpyHostToDevice));
+    WF_TRY(hipMemcpy(b.st[0].dA, dA.data(), n * sizeof(f4), hipMemcpyHostToDevice));
+    WF_TRY(hipMemcpy(b.st[0].dB, dB.data(), n * sizeof(f4), hipMemcpyHostToDevice));
+    WF_TRY(hipMemsetAsync(b.hit, (int) (NORI_EXTEND_SENTINEL & 0xffu), n * sizeof(f4), s));
+    uint32_t h_ctr[C_COUNT] = {0};
+    h_ctr[C_N + 0] = (uint32_t) n;
+    WF_TRY(hipMemcpy(b.ctr, h_ctr, sizeof(h_ctr), hipMemcpyHostToDevice));
+    WF_TRY(hipMemsetAsync(pool.buf.stats, 0, 2 * S_COUNT * sizeof(unsigned long long), s));
+    WfBatch bt;
+    bt.tile_first = 0; bt.n_tiles = 0; bt.s_first = 0; bt.n_spp = 0; bt.tile_mod = 1; bt.tile_rem = 0; bt.tiles_x = 0; bt.tile_w = 0;
+    bt.inner_repeat = plan.inner_repeat; bt.flags = plan.batch_flags; bt.pool = (uint32_t) n;
+    launch_extend_dyn(sc, b, 0, plan.thresholds, plan.lds_stack, plan.spill, count_traversal, kStoredOnly, plan.grid, bt, s);
+    WF_TRY(hipGetLastError());
+    unsigned long long h[S_COUNT];
+    WF_TRY(hipStreamSynchronize(s));
+    WF_TRY(hipMemcpy(hits, b.hit, n * sizeof(f4), hipMemcpyDeviceToHost));
+    WF_TRY(hipMemcpy(h, pool.buf.stats, sizeof(h), hipMemcpyDeviceToHost));
+    counts[0] = h[S_CLOSEST]; counts[1] = h[S_SHADOW]; counts[2] = h[S_NODES]; counts[3] = h[S_TRIS];
     return std::string();
 }
 

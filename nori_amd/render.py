@@ -213,6 +213,38 @@ class Renderer:
         return {"n_meshes": nm, "n_emitters": ne, "n_cdf": nc, "emitters": em[:ne], "cdf_offset": off[:nm], "n_triangles": nt[:nm],
                 "inv_area": inv[:nm], "cdf": cdf[:nc]}
 
+    def extend(self, origins, dir_a=None, dir_b=None, maxt_b=None, flags=None, count_traversal=False):
+        """wf_extend, the wavefront engine's traversal kernel, on rays of the caller's (include/nori_hip.h: nori_hip_debug_extend).
+        Slot k starts at origins[k]; dir_a [n, 3]: its continuation ray (closest hit), dir_b [n, 3] with maxt_b [n] (default inf): its
+        shadow ray (any hit).  flags [n] (capi.F_*) default from the directions given: A, B (the path ends on it) or B then A; pass
+        them to mix kinds and empty slots (0) in one call -- a direction the flags do not name is not read.
+        Returns ((t, u, v, tri, occluded), counts): per slot the closest hit of A (t = inf, tri = capi.EXTEND_MISS_A without one;
+        tri is the GLOBAL triangle index) and whether B was occluded; a slot nothing was written to (an empty one) has
+        tri = EXTEND_SENTINEL & EXTEND_MISS_A and the sentinel's bits in t, u, v.  counts: closest / shadow queries traced, node /
+        triangle tests (with count_traversal)."""
+        o = _f32(origins, 3)
+        n = o.shape[0]
+        if flags is None:
+            flags = np.full(n, (capi.F_HAS_A if dir_a is not None else 0) |
+                            (0 if dir_b is None else capi.F_HAS_B if dir_a is not None else capi.F_HAS_B | capi.F_END_AFTER_B), np.uint32)
+        flags = np.ascontiguousarray(flags, dtype=np.uint32)
+        da = np.zeros((n, 3), np.float32) if dir_a is None else _f32(dir_a, 3)
+        db = np.zeros((n, 4), np.float32)
+        db[:, 3] = np.inf
+        if dir_b is not None:
+            db[:, :3] = _f32(dir_b, 3)
+        if maxt_b is not None:
+            db[:, 3] = np.asarray(maxt_b, dtype=np.float32)
+        if not (da.shape[0] == n and db.shape[0] == n and flags.shape == (n,)):
+            raise ValueError("extend: origins, directions and flags of different lengths")
+        hits = np.zeros((n, 4), np.float32)
+        counts = (C.c_ulonglong * 4)()
+        self._check(self._lib.nori_hip_debug_extend(self._h, ptr(o), ptr(da), ptr(db), ptr(flags), n, int(bool(count_traversal)), ptr(hits), counts), "debug_extend")
+        word = hits[:, 3].copy().view(np.uint32)
+        names = ("n_closest_rays", "n_shadow_rays", "n_node_tests", "n_tri_tests")
+        return ((hits[:, 0].copy(), hits[:, 1].copy(), hits[:, 2].copy(), word & np.uint32(capi.EXTEND_MISS_A), (word >> 31).astype(bool)),
+                {k: int(v) for k, v in zip(names, counts)})
+
     def pcg32_floats(self, seed_state, seed_seq, count: int):
         ss = np.ascontiguousarray(seed_state, dtype=np.uint64)
         sq = np.ascontiguousarray(seed_seq, dtype=np.uint64)
