@@ -484,6 +484,15 @@ int nori_hip_debug_emitter_sample(nori_hip_ctx *ctx, int reader /* nori_tables_r
 int nori_hip_debug_emitter_tables(nori_hip_ctx *ctx, uint32_t counts[3], uint32_t *emitters, uint32_t *cdf_offset,
                                   uint32_t *n_triangles, float *inv_area, float *cdf);
 
+/* The tree as the kernels see it, read back from device memory after a device synchronise -- whichever builder made it
+ * (NORI_ACCEL_HOST_SAH: the uploaded copy).  *root = the root's child-link code; counts = {n_nodes, n_pairs, wide, records_32b}:
+ * node records in device memory (0: the root is a leaf), pair records (a wide tree's reserved pair 0 included), 1 if the nodes
+ * are WIDE nodes, 1 if the tree also exists as 32-B records.  Then, where the pointer is not NULL: nodes (16 floats per node
+ * record, rt_types.h), nodes32 (8 dwords per 32-B record, rt_nodeq.h) with grid = (mn[3], scale[3]) -- both left untouched
+ * without such records --, pairs (24 floats per pair record).  Call it with NULL arrays first to size them.
+ * Needs a built tree: NORI_ERR_INVALID_ARGUMENT before nori_hip_build_accel succeeded; the context stays usable. */
+int nori_hip_debug_tree(nori_hip_ctx *ctx, int32_t *root, uint32_t counts[4], float *nodes, uint32_t *nodes32, float grid[6], float *pairs);
+
 /* wf_extend -- the traversal kernel of the wavefront engine -- on n rays of the caller's choosing, all arrays in HOST memory.
  * Slot k is a stored path vertex as wf_shade would have left it: origin origins[3 k ..] (both rays start there, with the mint every
  * stored ray has, 1e-4), a continuation ray dir_a[3 k ..] (slot A: closest hit, maxt = inf) and / or a shadow ray dir_b[4 k ..] =

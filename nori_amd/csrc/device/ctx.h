@@ -34,6 +34,7 @@ struct nori_hip_ctx {
     int stack_depth = 32;
     uint64_t lbvh_bytes = 0;
     uint32_t lbvh_refs = 0;      /* references the device builder built the tree over (0: the host built it) */
+    uint32_t n_pairs = 0;        /* pair records of the tree in device memory (nori_hip_debug_tree) */
     int engine = -1;                /* -1 auto, 0 megakernel, 1 wavefront */
     int accel_layout = -1;          /* -1 auto (wide from 2^20 triangles), 0 bvh2, 1 bvh4q (wide nodes) */
     bool film_reference = false;    /* film_order = reference: samples added in the reference's own order (film.h) */

@@ -727,7 +727,17 @@ std::string build_bvh_lbvh_device(const DevScene &dev, const uint32_t *d_tri_mes
         out.d_nodes = d_nodes;
         hipLaunchKernelGGL(k_emit_wide, dim3(gridN), dim3(B), 0, 0, rnodes.as<RadixNode>(), n - 1, tmin.as<f4>(), tmax.as<f4>(), N, collapse.as<uint32_t>(),
                            pair_start.as<uint32_t>(), is_wide.as<uint32_t>(), wide_index.as<uint32_t>(), kids.as<uint32_t>(), n_kids.as<uint32_t>(), d_nodes);
-        out.root = 0; out.n_nodes = n_wide; out.n_leaves = 0; out.max_depth = 3 * levels; out.wide = true;
+        /* the leaves are those of the BVH2 the wide nodes were made of: one more than its nodes (keep, k_mark_leaves) */
+        uint32_t n_kept = 0;
+        {
+            Buf sum; LB_TRY(sum.alloc(4));
+            size_t red_bytes = 0;
+            LB_TRY(hipcub::DeviceReduce::Sum(nullptr, red_bytes, keep.as<uint32_t>(), sum.as<uint32_t>(), (int) (n - 1)));
+            Buf red_tmp; LB_TRY(red_tmp.alloc(red_bytes));
+            LB_TRY(hipcub::DeviceReduce::Sum(red_tmp.p, red_bytes, keep.as<uint32_t>(), sum.as<uint32_t>(), (int) (n - 1)));
+            LB_TRY(hipMemcpy(&n_kept, sum.p, 4, hipMemcpyDeviceToHost));
+        }
+        out.root = 0; out.n_nodes = n_wide; out.n_leaves = n_kept + 1u; out.max_depth = 3 * levels; out.wide = true;
         LB_TRY(hipGetLastError());
     } else {
         /* 6. nodes: the radix nodes that are not inside a collapsed subtree, renumbered densely (root stays 0) */
@@ -752,7 +762,7 @@ std::string build_bvh_lbvh_device(const DevScene &dev, const uint32_t *d_tri_mes
         hipLaunchKernelGGL(k_depth, dim3(gridN), dim3(B), 0, 0, pin.as<uint32_t>(), plf.as<uint32_t>(), keep.as<uint32_t>(), n, md.as<unsigned int>());
         unsigned int depth = 0;
         LB_TRY(hipMemcpy(&depth, md.p, 4, hipMemcpyDeviceToHost));
-        out.root = 0; out.n_nodes = n_nodes; out.n_leaves = 0; out.max_depth = depth;
+        out.root = 0; out.n_nodes = n_nodes; out.n_leaves = n_nodes + 1u; out.max_depth = depth;      /* a binary tree */
         LB_TRY(hipGetLastError());
     }
     lap("leaves, boxes, emission");

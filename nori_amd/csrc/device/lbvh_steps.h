@@ -214,7 +214,8 @@ NORI_HD void tri_leaf_box(const f4 *pos, const uint32_t *idx, uint32_t g, float 
     bool unbounded;
     const float pad = tri_box_pad(p1 - p0, p2 - p0, pad0, unbounded);
     if (unbounded) { mn = mk3(-kBoxInf); mx = mk3(kBoxInf); }
-    mn4.x = mn.x - pad; mn4.y = mn.y - pad; mn4.z = mn.z - pad; mx4.x = mx.x + pad; mx4.y = mx.y + pad; mx4.z = mx.z + pad;
+    mn4.x = pad_below(mn.x, pad); mn4.y = pad_below(mn.y, pad); mn4.z = pad_below(mn.z, pad);
+    mx4.x = pad_above(mx.x, pad); mx4.y = pad_above(mx.y, pad); mx4.z = pad_above(mx.z, pad);
     mn4.w = mx4.w = 0.0f;
 }
 /* ---- references: triangles split before the tree is built (after Karras & Aila 2013, section 4) ----
@@ -403,8 +404,8 @@ NORI_HD uint32_t split_emit(const f4 *pos, const uint32_t *idx, uint32_t t, uint
         if (!cut) {
             if (write) {
                 f4 a, b;
-                a.x = pt.mn.x - pad; a.y = pt.mn.y - pad; a.z = pt.mn.z - pad; a.w = 0.0f;
-                b.x = pt.mx.x + pad; b.y = pt.mx.y + pad; b.z = pt.mx.z + pad; b.w = 0.0f;
+                a.x = pad_below(pt.mn.x, pad); a.y = pad_below(pt.mn.y, pad); a.z = pad_below(pt.mn.z, pad); a.w = 0.0f;
+                b.x = pad_above(pt.mx.x, pad); b.y = pad_above(pt.mx.y, pad); b.z = pad_above(pt.mx.z, pad); b.w = 0.0f;
                 out.tri[first + written] = t; out.mn[first + written] = a; out.mx[first + written] = b;
                 out.key[first + written] = morton63(pt.mn, pt.mx, smin, sinv);
             }

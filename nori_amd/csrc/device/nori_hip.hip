@@ -640,6 +640,7 @@ int nori_hip_build_accel(nori_hip_ctx *ctx, int builder) {
         ctx->dev.nodes = res.d_nodes; ctx->dev.tris = res.d_tris;
         ctx->lbvh_bytes = (uint64_t) std::max<uint32_t>(res.n_nodes, 1) * kNodeQuads * 16 + (uint64_t) res.n_pairs * kPairQuads * 16;
         ctx->lbvh_refs = res.n_refs;
+        ctx->n_pairs = res.n_pairs;
     } else {
         const bool wide = want_wide;
         std::string err = build_bvh_sah(ctx->host, 64, ctx->bvh, wide);
@@ -649,6 +650,7 @@ int nori_hip_build_accel(nori_hip_ctx *ctx, int builder) {
         if ((rc = upload(ctx, ctx->allocs_accel, ctx->bvh.nodes, &ctx->dev.nodes))) return rc;
         if ((rc = upload(ctx, ctx->allocs_accel, ctx->bvh.tris, &ctx->dev.tris))) return rc;
         ctx->lbvh_bytes = 0; ctx->lbvh_refs = 0;
+        ctx->n_pairs = ctx->bvh.n_pairs;
     }
     if (const char *e = getenv("NORI_HIP_LAB_DEPTH_ADD")) ctx->bvh.max_depth += (uint32_t) std::max(0, atoi(e));      /* experiments: a tree priced as if it were deeper (the spilling stack, the smaller LDS image) */
     ctx->dev.root = ctx->bvh.root;
@@ -1013,6 +1015,24 @@ int nori_hip_debug_emitter_tables(nori_hip_ctx *ctx, uint32_t counts[3], uint32_
             if (n_triangles) n_triangles[i] = recs[i].n_triangles;
             if (inv_area) inv_area[i] = recs[i].inv_area;
         }
+    }
+    return NORI_OK;
+}
+
+int nori_hip_debug_tree(nori_hip_ctx *ctx, int32_t *root, uint32_t counts[4], float *nodes, uint32_t *nodes32, float grid[6], float *pairs) {
+    if (!ctx || !root || !counts) return NORI_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_accel) { ctx->error = "debug_tree: no acceleration structure built"; return NORI_ERR_INVALID_ARGUMENT; }
+    const DevScene &d = ctx->dev;
+    const uint32_t n_nodes = ctx->bvh.n_nodes, n_pairs = ctx->n_pairs;
+    *root = d.root;
+    counts[0] = n_nodes; counts[1] = n_pairs; counts[2] = d.wide; counts[3] = d.nodes_q != nullptr ? 1u : 0u;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    if (nodes && n_nodes) HIP_TRY(ctx, hipMemcpy(nodes, d.nodes, (size_t) n_nodes * kNodeQuads * sizeof(f4), hipMemcpyDeviceToHost));
+    if (pairs && n_pairs) HIP_TRY(ctx, hipMemcpy(pairs, d.tris, (size_t) n_pairs * kPairQuads * sizeof(f4), hipMemcpyDeviceToHost));
+    if (d.nodes_q) {
+        if (nodes32 && n_nodes) HIP_TRY(ctx, hipMemcpy(nodes32, d.nodes_q, (size_t) n_nodes * kNodeqQuads * sizeof(f4), hipMemcpyDeviceToHost));
+        if (grid) for (int a = 0; a < 3; ++a) { grid[a] = d.grid.mn[a]; grid[3 + a] = d.grid.scale[a]; }
     }
     return NORI_OK;
 }

@@ -305,8 +305,8 @@ static bool clip_tri_box(const double tri[3][3], int axis, double lo, double hi,
     double mn[3] = {b[0][0], b[0][1], b[0][2]}, mx[3] = {b[0][0], b[0][1], b[0][2]};
     for (int i = 1; i < n; ++i) for (int k = 0; k < 3; ++k) { mn[k] = std::min(mn[k], b[i][k]); mx[k] = std::max(mx[k], b[i][k]); }
     for (int k = 0; k < 3; ++k) {
-        out.mn[k] = std::max(within.mn[k], round_down(mn[k]) - pad);
-        out.mx[k] = std::min(within.mx[k], round_up(mx[k]) + pad);
+        out.mn[k] = std::max(within.mn[k], pad_below(round_down(mn[k]), pad));
+        out.mx[k] = std::min(within.mx[k], pad_above(round_up(mx[k]), pad));
         if (!(out.mn[k] <= out.mx[k])) return false;
     }
     return true;
@@ -682,7 +682,7 @@ std::string build_bvh_sah(const HostScene &sc, uint32_t max_depth_limit, HostBvh
             nUnbounded += unbounded ? 1u : 0u;
             for (int k = 0; k < 3; ++k) {
                 if (unbounded) { boxes[t].mn[k] = -kBoxInf; boxes[t].mx[k] = kBoxInf; }
-                else { boxes[t].mn[k] -= padT; boxes[t].mx[k] += padT; }
+                else { boxes[t].mn[k] = pad_below(boxes[t].mn[k], padT); boxes[t].mx[k] = pad_above(boxes[t].mx[k], padT); }
                 cent[3 * (size_t) t + k] = 0.5f * (boxes[t].mn[k] + boxes[t].mx[k]);
             }
         }
@@ -928,7 +928,7 @@ std::string build_bvh_sah(const HostScene &sc, uint32_t max_depth_limit, HostBvh
         std::vector<int32_t> leafAt(nRefs, -1), leaves;
         for (size_t b = 0; b < bn.size(); ++b) if (isLeaf((int32_t) b)) leafAt[bn[b].first] = (int32_t) b;
         leaves.reserve(bn.size() / 2 + 1);
-        uint32_t nPairs = wide ? 1u : 0u;        /* wide trees reserve pair 0 as the all-zero pair unused child slots point to */
+        uint32_t nPairs = (wide && !isLeaf(0)) ? 1u : 0u;        /* wide trees reserve pair 0 as the all-zero pair unused child slots point to (a tree that is one leaf has no wide node) */
         for (uint32_t p = 0; p < nRefs; ++p)
             if (leafAt[p] >= 0) { const int32_t b = leafAt[p]; leaves.push_back(b); firstPair[b] = nPairs; nPairs += (bn[b].count + 1) / 2; }
         out.tris.assign((size_t) std::max<uint32_t>(nPairs, 1) * kPairQuads, f4{0.0f, 0.0f, 0.0f, 0.0f});

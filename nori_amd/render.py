@@ -23,6 +23,21 @@ def _f32(a, shape_last=None):
     return a
 
 
+def read_tree(call) -> dict:
+    """The dict of Renderer.tree() from `call(root, counts, nodes, nodes32, grid, pairs)`, which follows nori_hip_debug_tree's convention:
+    once with NULL arrays for the counts, once with arrays."""
+    root, counts = C.c_int32(0), np.zeros(4, np.uint32)
+    call(C.byref(root), ptr(counts), None, None, None, None)
+    n_nodes, n_pairs, wide, q = (int(c) for c in counts)
+    nodes, pairs = np.zeros((max(n_nodes, 1), 16), np.float32), np.zeros((max(n_pairs, 1), 24), np.float32)
+    nodes32, grid = np.zeros((max(n_nodes, 1), 8), np.uint32), np.zeros(6, np.float32)
+    call(C.byref(root), ptr(counts), ptr(nodes), ptr(nodes32), ptr(grid), ptr(pairs))
+    assert (n_nodes, n_pairs, wide, q) == tuple(int(c) for c in counts)
+    return {"root": int(root.value), "n_nodes": n_nodes, "n_pairs": n_pairs, "wide": wide, "records_32b": q, "nodes": nodes[:n_nodes],
+            "pairs": pairs[:n_pairs], "nodes32": nodes32[:n_nodes] if q else None, "grid_mn": grid[:3].copy() if q else None,
+            "grid_scale": grid[3:].copy() if q else None}
+
+
 class Renderer:
     """Owns a `nori_hip_ctx`.  Mirrors Scene/Accel/Integrator of the reference:
     `upload` = Scene::addChild + activate, `build_accel` = Accel::build,
@@ -212,6 +227,12 @@ class Renderer:
         self._check(self._lib.nori_hip_debug_emitter_tables(self._h, ptr(counts), ptr(em), ptr(off), ptr(nt), ptr(inv), ptr(cdf)), "debug_emitter_tables")
         return {"n_meshes": nm, "n_emitters": ne, "n_cdf": nc, "emitters": em[:ne], "cdf_offset": off[:nm], "n_triangles": nt[:nm],
                 "inv_area": inv[:nm], "cdf": cdf[:nc]}
+
+    def tree(self) -> dict:
+        """The tree as it is in device memory (include/nori_hip.h: nori_hip_debug_tree): root (the root's link code), n_nodes, n_pairs,
+        wide, records_32b, nodes [n_nodes, 16] float32, pairs [n_pairs, 24] float32 and -- None without 32-B records -- nodes32
+        [n_nodes, 8] uint32, grid_mn [3], grid_scale [3] float32."""
+        return read_tree(lambda *a: self._check(self._lib.nori_hip_debug_tree(self._h, *a), "debug_tree"))
 
     def extend(self, origins, dir_a=None, dir_b=None, maxt_b=None, flags=None, count_traversal=False):
         """wf_extend, the wavefront engine's traversal kernel, on rays of the caller's (include/nori_hip.h: nori_hip_debug_extend).

@@ -109,6 +109,7 @@ def emu_lib():
             "emu_split_parts_peak": (C.c_int, [_P, C.c_uint32, C.c_float, _P, _P, _P, _P, C.c_int, _P]),
             "emu_split_clip": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, _P]),
             "emu_node_records": (C.c_longlong, [_P, _P, _P, _P, C.c_size_t]),
+            "emu_tree": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
             "emu_packed_vs_scalar": (C.c_size_t, [C.c_size_t, C.c_uint64]),
             "emu_libm_eval": (C.c_int, [C.c_int, _P, C.c_size_t, _P]),
             "emu_sample_rays": (C.c_int, [_P, _P, C.c_size_t, _P]),
@@ -351,6 +352,14 @@ class Emu(_CpuBackend):
         n64 = np.zeros((cap, 16), np.float32); n32 = np.zeros((cap, 8), np.uint32); grid = np.zeros(6, np.float32)
         n = self.lib.emu_node_records(self._h, ptr(n64), ptr(n32), ptr(grid), cap)
         return None if n < 0 else (n64[:n], n32[:n], grid[:3].copy(), grid[3:].copy())
+
+    def tree(self):
+        """Renderer.tree() of the harness's tree (emu.cpp: emu_tree) -- the same dict, so that the two compare key by key."""
+        from nori_amd.render import read_tree
+
+        def call(*a):
+            assert self.lib.emu_tree(self._h, *a) == 0
+        return read_tree(call)
 
     def nodeq_check(self, rays):
         """rt_nodeq.h: (ray, child box) pairs the exact slab test accepts and the 32-B record rejects (must be 0), and how many

@@ -388,6 +388,23 @@ long long emu_node_records(emu_ctx *c, float *nodes64, uint32_t *nodes32, float 
     return (long long) n;
 }
 
+/* nori_hip_debug_tree (include/nori_hip.h) of the harness's tree, whatever its layout: the root's link, counts = {n_nodes, n_pairs, wide,
+   records_32b} and, where the pointer is not null, the node records (16 floats each), the 32-B records (8 dwords each) with their grid
+   (mn[3], scale[3]) -- both untouched without such records -- and the pair records (24 floats each) */
+int emu_tree(emu_ctx *c, int32_t *root, uint32_t counts[4], float *nodes, uint32_t *nodes32, float *grid, float *pairs) {
+    const DevScene &sc = c->dev;
+    const uint32_t n_nodes = c->bvh.n_nodes, n_pairs = c->bvh.n_pairs;
+    *root = sc.root;
+    counts[0] = n_nodes; counts[1] = n_pairs; counts[2] = sc.wide; counts[3] = sc.nodes_q != nullptr ? 1u : 0u;
+    if (nodes && n_nodes) std::memcpy(nodes, sc.nodes, (size_t) n_nodes * kNodeQuads * sizeof(f4));
+    if (pairs && n_pairs) std::memcpy(pairs, sc.tris, (size_t) n_pairs * kPairQuads * sizeof(f4));
+    if (sc.nodes_q) {
+        if (nodes32 && n_nodes) std::memcpy(nodes32, sc.nodes_q, (size_t) n_nodes * kNodeqQuads * sizeof(f4));
+        if (grid) for (int a = 0; a < 3; ++a) { grid[a] = sc.grid.mn[a]; grid[3 + a] = sc.grid.scale[a]; }
+    }
+    return NORI_OK;
+}
+
 /* rt_nodeq.h: every ray against every node of the tree, the 32-B record's verdict per child against the exact one.
    Exact = the slab test of the stored 64-B box [c - h, c + h] in binary64 with the ray's own (binary32) reciprocal
    direction, clipped to [0, maxt] (trav_inner_step's rule).  Returns the number of (ray, child) pairs the exact test

@@ -247,7 +247,9 @@ inline std::string build_bvh_steps_host(const HostScene &scene, bool wide, uint3
         for (uint32_t i = 0; i + 1 < n; ++i)
             if (is_wide[i]) emit_wide_node(rnodes.data(), tmin.data(), tmax.data(), N, collapse.data(), pair_start.data(), wide_index.data(),
                                            kids.data() + 4 * (size_t) i, (int) n_kids[i], out.nodes.data() + (size_t) wide_index[i] * kNodeQuads);
-        out.root = 0; out.n_nodes = n_wide; out.n_leaves = 0; out.max_depth = 3 * levels; out.wide = true;
+        uint32_t n_kept = 0;
+        for (uint32_t i = 0; i + 1 < n; ++i) n_kept += keep[i];
+        out.root = 0; out.n_nodes = n_wide; out.n_leaves = n_kept + 1u; out.max_depth = 3 * levels; out.wide = true;
     } else {
         uint32_t n_nodes = 0;
         for (uint32_t i = 0; i + 1 < n; ++i) { node_index[i] = n_nodes; n_nodes += keep[i]; }
@@ -257,7 +259,7 @@ inline std::string build_bvh_steps_host(const HostScene &scene, bool wide, uint3
                                    out.nodes.data() + (size_t) node_index[i] * kNodeQuads);
         uint32_t depth = 0;
         for (uint32_t k = 0; k < n; ++k) depth = std::max(depth, leaf_depth(pin.data(), plf.data(), keep.data(), k));
-        out.root = 0; out.n_nodes = n_nodes; out.n_leaves = 0; out.max_depth = depth;
+        out.root = 0; out.n_nodes = n_nodes; out.n_leaves = n_nodes + 1u; out.max_depth = depth;
     }
     if (stats) out.sah_cost = stats->sah_cost;
     return std::string();

@@ -118,40 +118,18 @@ def test_spatial_splits_on_wide_nodes_and_in_renders(monkeypatch):
 
 
 def _check_bvh2_invariants(e, n_refs_min):
-    """A flattened BVH2 tree (64-B nodes, rt_types.h): every inner node is reached exactly once from the root, a child's box lies
-    inside its parent's (centre / half-extent: [c - h, c + h]), every leaf link covers its own range of pair records and the ranges
-    tile [0, n_pairs) without overlap.  Returns the number of leaves."""
-    n64 = e.node_records()[0]
-    n = n64.shape[0]
-    links = n64[:, 12:14].copy().view(np.uint32).astype(np.int64)
-    links[links >= 2 ** 31] -= 2 ** 32
-    # q0 = (lc.x, lc.y, rc.x, rc.y), q1 = (lc.z, rc.z, lh.z, rh.z), q2 = (lh.x, lh.y, rh.x, rh.y)
-    c = np.stack([np.stack([n64[:, 0], n64[:, 1], n64[:, 4]], 1), np.stack([n64[:, 2], n64[:, 3], n64[:, 5]], 1)], 1).astype(np.float64)
-    h = np.stack([np.stack([n64[:, 8], n64[:, 9], n64[:, 6]], 1), np.stack([n64[:, 10], n64[:, 11], n64[:, 7]], 1)], 1).astype(np.float64)
-    lo, hi = c - h, c + h
-    seen = np.zeros(n, np.int32); ranges = []
-    stack = [(0, None, None)]
-    while stack:
-        i, plo, phi = stack.pop()
-        seen[i] += 1
-        for k in (0, 1):
-            if plo is not None:                                 # this node's two boxes lie inside the box its parent holds for it
-                assert (lo[i, k] >= plo - 1e-6 * (1 + np.abs(plo))).all() and (hi[i, k] <= phi + 1e-6 * (1 + np.abs(phi))).all(), i
-            link = int(links[i, k])
-            if link >= 0:
-                stack.append((link, lo[i, k], hi[i, k]))
-            else:
-                code = ~link
-                ranges.append((code >> 3, (code & 7) + 1))
-    assert (seen == 1).all(), "an inner node is unreachable or reached twice"
-    ranges.sort()
-    pos = ranges[0][0]
-    assert pos in (0, 1)
-    for first, cnt in ranges:
-        assert first == pos, "leaf ranges overlap or leave a gap"
-        pos += cnt
-    assert 2 * (pos - ranges[0][0]) >= n_refs_min
-    return len(ranges)
+    """A flattened BVH2 tree (64-B nodes, rt_types.h) through the auditor of built trees (tests/tree_audit.py): every inner node is reached
+    exactly once from the root, every leaf link covers its own range of pair records and the ranges tile [0, n_pairs), every slot holds its
+    triangle's vertices, every triangle is in the tree and inside every box above it (no slack), the parts of a cut triangle cover it, the
+    32-B records enclose the 64-B boxes, the counts are accel_info's.  Returns the number of leaves."""
+    from tests import extend_cases, tree_audit
+    tree = e.tree()
+    assert tree["wide"] == 0
+    found = tree_audit.audit(tree, extend_cases.scene_triangles(e.scene), tree_audit.scene_meshes(e.scene), e.accel_info())
+    assert found == [], found
+    _, leaves, _ = tree_audit.walk(tree, tree_audit.Findings())
+    assert 2 * int(leaves["count"].sum()) >= n_refs_min
+    return len(leaves["first"])
 
 
 def test_tree_invariants_after_spatial_splits_and_reinsertion(monkeypatch):
@@ -920,18 +898,21 @@ def test_node_records_32b_enclose_the_64b_boxes_read_independently(scene):
     (rt_types.h: q0 = left centre x y, right centre x y; q1 = centres z, half extents z; q2 = half extents x y; q3 = links): every
     box of the 32-B form contains the 64-B box, is no more than a grid step (plus float rounding) wider per side, and the links agree."""
     sc = scenes.soup_scene(4000, 21) if scene == "soup" else scenes.cornell_box(16, 16, 1)
-    rec = Emu(sc).node_records()
-    assert rec is not None
-    n64, n32, mn, scale = rec
-    n64 = n64.astype(np.float64); mn = mn.astype(np.float64); scale = scale.astype(np.float64)
-    cx = np.stack([n64[:, 0], n64[:, 2]], 1); cy = np.stack([n64[:, 1], n64[:, 3]], 1); cz = n64[:, 4:6]
-    hx = np.stack([n64[:, 8], n64[:, 10]], 1); hy = np.stack([n64[:, 9], n64[:, 11]], 1); hz = n64[:, 6:8]
-    assert np.array_equal(n32[:, 6:8], rec[0][:, 12:14].view(np.uint32))                   # links
-    for a, (c, h) in enumerate(((cx, hx), (cy, hy), (cz, hz))):
-        lo_q = np.stack([n32[:, 2 * a] & 0xffff, n32[:, 2 * a] >> 16], 1).astype(np.float64)
-        hi_q = np.stack([n32[:, 2 * a + 1] & 0xffff, n32[:, 2 * a + 1] >> 16], 1).astype(np.float64)
-        p_lo, p_hi = mn[a] + lo_q * scale[a], mn[a] + hi_q * scale[a]
-        box_lo, box_hi = c - h, c + h
+    from tests import tree_audit
+    e = Emu(sc)
+    tree = e.tree()
+    assert tree["records_32b"] == 1
+    rec = e.node_records()                                          # the older call returns the same records
+    assert np.array_equal(rec[0].view(np.uint32), tree["nodes"].view(np.uint32)) and np.array_equal(rec[1], tree["nodes32"])      # (links are NaN patterns as floats)
+    assert np.array_equal(rec[2], tree["grid_mn"]) and np.array_equal(rec[3], tree["grid_scale"])
+    lo64, hi64, links64, _ = tree_audit.decode_bvh2(tree["nodes"])
+    p_lo3, p_hi3, q_lo3, q_hi3, links32 = tree_audit.decode_nodes32(tree["nodes32"], tree["grid_mn"], tree["grid_scale"])
+    mn, scale = tree["grid_mn"].astype(np.float64), tree["grid_scale"].astype(np.float64)
+    assert np.array_equal(links32, links64)                                                # links
+    for a in range(3):
+        lo_q, hi_q, p_lo, p_hi = q_lo3[:, :, a], q_hi3[:, :, a], p_lo3[:, :, a], p_hi3[:, :, a]
+        box_lo, box_hi = lo64[:, :, a], hi64[:, :, a]
+        c = 0.5 * (box_lo + box_hi)
         inside_grid_lo, inside_grid_hi = box_lo >= mn[a], box_hi <= mn[a] + 65535.0 * scale[a]
         assert (p_lo[inside_grid_lo] <= box_lo[inside_grid_lo]).all() and (p_hi[inside_grid_hi] >= box_hi[inside_grid_hi]).all()
         slack = scale[a] * (1.0 + 1e-6) + 1e-6 * np.abs(c)
