@@ -877,6 +877,83 @@ int nori_hip_render_adaptive_denoised_host(nori_hip_ctx *ctx, const nori_render_
                                            const float *normal, const float *depth, float *rgb_out, float *var_out, float *wsum,
                                            float *err, uint32_t *tile_spp, nori_adaptive_summary *out, nori_render_stats *stats);
 
+/* ------------------------------------------- rendering to a target error in few passes: tile sample levels from a pilot
+ *
+ * No counterpart in the reference.  The two adaptive loops above make up to budget / pass_spp passes, most of them over few tiles,
+ * and every pass pays the render's fixed price.  The error they stop on is a standard error of a mean and falls as 1 / sqrt(N), so
+ * after a pilot each tile's need can be predicted and rendered in ONE long call per group of tiles.  A translation unit of its own
+ * (film_alloc.h); no kernel of the renders, the film, the tile lists, the feature frames or the denoiser changes.
+ *
+ * Levels.  spp_j = pilot_spp << j for j = 0 .. J, J = min(7, floor(log2(spp_count / pilot_spp))), spp_count = params->spp_count: spp_J is
+ * the most a pixel gets.  Every tile of the frame has a level l and a done flag.  The pilot renders samples [spp_begin, spp_begin +
+ * spp_0) of ALL tiles with moments; all tiles start at level 0, not done.
+ * A round evaluates the tile errors E_t of the frames as they are (metric 0: nori_hip_tile_errors; metric 1: see below) and then, one
+ * thread per tile that is not done, in float32 without contraction and with IEEE division:
+ *   if (E <= target) done
+ *   else  r = E / target
+ *         need = (headroom * (float) spp_l) * (r * r)
+ *         j = l;  while (j < J && !((float) spp_j >= need)) ++j
+ *         if (j == l) done        (it sits at the top level: unconverged)
+ *         else the tile moves l -> j
+ * So a NaN error moves the tile to J (as nori_hip_select_tiles keeps a NaN in), target == 0 sends every tile with an error above zero
+ * to J, and a done tile never returns.  The moving tiles are grouped by pair (i, j), i < j: bucket b = i J - i (i - 1) / 2 + (j - i - 1)
+ * -- ascending in i, then j; J (J + 1) / 2 <= 28 buckets --, ascending tile id inside a bucket, into one array with
+ * bucket_begin[0 .. n_buckets] (a stable compaction by prefix sum: per-256-tile counts per bucket, one scan, a ranked scatter; no
+ * atomics, the same inputs give the same bytes).  The moves of a round are rendered bucket by bucket in that order, empty buckets
+ * skipped: each is one tile-list render with moments of samples [spp_begin + spp_i, spp_begin + spp_j) of the bucket's tiles, ADDING
+ * into d_rgbw and d_m2 -- what nori_hip_render_tiles does with that list.  The loop ends when a round moves nothing or after
+ * max_rounds rounds; one more evaluation then fills the summary.  The host reads bucket_begin (29 words) once per round; the lists
+ * never leave device memory.  At most 1 + J (J + 1) / 2 render calls per round, each over every tile that shares the move.
+ *
+ * metric 1 stops on the error of the DENOISED frame: an evaluation is step A over the whole frame, nori_hip_denoise_var's filter over
+ * the tiles not yet done (in the first round all tiles, later the tiles the previous round moved -- every other tile is done), whose
+ * pixels have the bits of a whole-frame call, then nori_hip_denoised_tile_errors.  d_rgb_out, d_var_out and d_wsum are zeroed at the
+ * start; at the end step A and the filter run once over the WHOLE frame, exactly as nori_hip_render_adaptive_denoised finishes, so
+ * the outputs are nori_hip_denoise_var of the frames as they are left.  metric 0 ignores the denoiser's arguments (all may be NULL).
+ *
+ * nori_hip_allocate_tiles drives the classification and the grouping without a render, as nori_hip_select_tiles drives the
+ * selection: level and done (HOST, one uint32 per tile of the frame, in and out; level <= J, done zero or not), d_tile_err on the
+ * DEVICE; tiles_out (HOST, room for every tile of the frame) receives the grouped array, bucket_begin (HOST, 29 words) the offsets:
+ * entries n_buckets .. 28 hold the number of moving tiles.  Only pilot_spp, target_tile_err and headroom steer it; all of alloc is
+ * checked.  Synchronous on the default stream.
+ *
+ * nori_hip_render_allocated.  d_tile_spp (tiles_x * tiles_y uint32, may be NULL): spp_l of every tile's final level.  d_level_log
+ * ((max_rounds + 1) * tiles_x * tiles_y uint32, may be NULL): row 0 the levels after the pilot (all 0), row k the levels after round
+ * k; rows of rounds that did not run repeat the last levels.  The loop can be replayed from the log: the tiles with
+ * log[k-1][t] = i and log[k][t] = j are bucket (i, j) of round k.  out (may be NULL): nori_adaptive_summary with passes = the render
+ * calls made (the pilot included), spp_min / spp_max over the tiles, n_unconverged = the tiles with !(E_t <= target) in the final
+ * evaluation, frame = the summary of the error map (metric 1: the denoised error map) of what is left, threshold = target.  stats: as
+ * for nori_hip_render_adaptive.  Errors, with the existing codes: NORI_ERR_INVALID_ARGUMENT for pilot_spp < 2, max_rounds < 1, a target
+ * that is not a number >= 0, headroom that is not a number >= 1, a metric other than 0 and 1, spp_count < pilot_spp, tile_mod != 1,
+ * metric 1 without its three output buffers, and denoiser parameters out of range; NORI_ERR_UNSUPPORTED for film_order = reference and
+ * NORI_SEED_NORI_BLOCK, as nori_hip_render_tiles.  Synchronous.  The _host twin renders into zeroed scratch frames and writes rgbw and,
+ * where not NULL, m2, err (the error map of the metric), tile_spp, level_log, and for metric 1 rgb_out (required), var_out, wsum.
+ * Limits.  The pilot's variance estimate is biased low where it stops tiles, and a tile's need is under-predicted from few samples:
+ * the later rounds and headroom are the remedy.  Levels are powers of two, so a tile may receive up to twice its need.  Granularity is
+ * a tile.  One device only. */
+typedef struct nori_allocate_params {
+    uint32_t pilot_spp;       /* >= 2 */
+    uint32_t max_rounds;      /* >= 1 */
+    float    target_tile_err; /* >= 0 */
+    float    headroom;        /* >= 1 */
+    int32_t  metric;          /* 0 raw, 1 denoised */
+} nori_allocate_params;
+int nori_hip_allocate_tiles(nori_hip_ctx *ctx, const nori_allocate_params *alloc, uint32_t spp_count /* the budget: sets J */,
+                            const void *d_tile_err /* tiles_x*tiles_y floats, DEVICE */,
+                            uint32_t *level /* HOST, in and out */, uint32_t *done /* HOST, in and out */,
+                            uint32_t *tiles_out /* HOST, tiles_x*tiles_y */, uint32_t *bucket_begin /* HOST, 29 */);
+int nori_hip_render_allocated(nori_hip_ctx *ctx, const nori_render_params *params /* spp_count = the most a pixel may get */,
+                              const nori_allocate_params *alloc, const nori_denoise_params *denoise_params /* NULL: the defaults */,
+                              void *d_rgbw, void *d_m2, const void *d_albedo, const void *d_normal, const void *d_depth /* each may be NULL */,
+                              void *d_rgb_out, void *d_var_out, void *d_wsum /* metric 1; metric 0: ignored */,
+                              void *d_tile_spp /* may be NULL */, void *d_level_log /* may be NULL */,
+                              nori_adaptive_summary *out, nori_render_stats *stats);
+int nori_hip_render_allocated_host(nori_hip_ctx *ctx, const nori_render_params *params, const nori_allocate_params *alloc,
+                                   const nori_denoise_params *denoise_params, float *rgbw, float *m2, const float *albedo,
+                                   const float *normal, const float *depth, float *rgb_out, float *var_out, float *wsum,
+                                   float *err, uint32_t *tile_spp, uint32_t *level_log,
+                                   nori_adaptive_summary *out, nori_render_stats *stats);
+
 /* film_order = "reference" shared out over devices or ranks.  The reference adds a 32x32 block's samples consecutively
  * into the block's own ImageBlock (renderBlock, src/main.cpp:27-55) and the blocks into the frame in BlockGenerator's order
  * (src/block.cpp:93-152): the smallest share that keeps the order is a block, the one handed out here is a ROW of blocks.

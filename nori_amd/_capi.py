@@ -148,6 +148,16 @@ class AdaptiveSummary(C.Structure):
         return d
 
 
+class AllocateParams(C.Structure):
+    """nori_allocate_params"""
+    _fields_ = [("pilot_spp", C.c_uint32), ("max_rounds", C.c_uint32), ("target_tile_err", C.c_float), ("headroom", C.c_float), ("metric", C.c_int32)]
+    METRICS = {"raw": 0, "denoised": 1}
+
+
+ALLOC_MAX_LEVEL = 7                                             # J <= 7: eight levels
+ALLOC_MAX_BUCKETS = ALLOC_MAX_LEVEL * (ALLOC_MAX_LEVEL + 1) // 2      # 28 pairs (i, j), i < j; bucket_begin has 29 words
+
+
 class AccelInfo(C.Structure):
     _fields_ = [("n_triangles", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("max_depth", C.c_uint32), ("node_bytes", C.c_uint32), ("tri_bytes", C.c_uint32),
@@ -240,6 +250,11 @@ HIP_PROTOTYPES = {
                                            C.POINTER(AdaptiveSummary), C.POINTER(RenderStats)]),
     "nori_hip_render_adaptive_host": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_float, _P, _P, _P, _P,
                                                 C.POINTER(AdaptiveSummary), C.POINTER(RenderStats)]),
+    "nori_hip_allocate_tiles": (C.c_int, [_P, C.POINTER(AllocateParams), C.c_uint32, _P, _P, _P, _P, _P]),
+    "nori_hip_render_allocated": (C.c_int, [_P, C.POINTER(RenderParams), C.POINTER(AllocateParams), C.POINTER(DenoiseParams), _P, _P, _P, _P, _P,
+                                            _P, _P, _P, _P, _P, C.POINTER(AdaptiveSummary), C.POINTER(RenderStats)]),
+    "nori_hip_render_allocated_host": (C.c_int, [_P, C.POINTER(RenderParams), C.POINTER(AllocateParams), C.POINTER(DenoiseParams), _P, _P, _P, _P, _P,
+                                                 _P, _P, _P, _P, _P, _P, C.POINTER(AdaptiveSummary), C.POINTER(RenderStats)]),
     "nori_hip_develop": (C.c_int, [_P, _P, _P, _P]),
     "nori_hip_block_acc_floats": (C.c_int, [_P, C.POINTER(C.c_size_t)]),
     "nori_hip_render_block_rows": (C.c_int, [_P, C.POINTER(RenderParams), C.c_uint32, C.c_uint32, _P, C.POINTER(RenderStats)]),

@@ -9,6 +9,7 @@
 #include "../../../include/nori_hip.h"
 #include "film.h"
 #include "film_tiles.h"
+#include "film_alloc.h"
 #include "features.h"
 #include "denoise.h"
 #include "denoise_error.h"
@@ -56,6 +57,7 @@ struct nori_hip_ctx {
     FilmStore film;
     FilmMoments moments;      /* renders that keep second moments, nori_hip_error_map: a second set of tile accumulators, partial sums */
     FilmTiles tiles;          /* renders by tile list, tile selection, the adaptive loop: lists, inverse table, tile errors (film_tiles.h) */
+    FilmAlloc alloc;          /* nori_hip_allocate_tiles, nori_hip_render_allocated: levels, done flags, the moving tiles grouped by pair (film_alloc.h) */
     FeatureStore features;    /* nori_hip_render_features: a sample plane and a set of tile accumulators per feature (features.h) */
     DenoiseStore denoise;     /* nori_hip_denoise: the guide records between its two kernels, a buffer per stream (denoise.h) */
     DenoiseErrorStore denoise_error;      /* nori_hip_denoised_error_map: the partial sums of its summary (denoise_error.h) */

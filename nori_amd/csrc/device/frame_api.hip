@@ -1,7 +1,7 @@
 /* frame_api.hip -- the frame-level half of the C ABI of include/nori_hip.h: nori_hip_render and what is built on it (moments, error map,
  * render to an error, tile lists, selection, the adaptive loop, feature frames, the denoiser, the denoiser with its error and the loop that
- * stops on it, block rows) and the _host twins.  No kernel lives here: every render ends in render_impl (nori_hip.hip), everything else in
- * film.hip / film_tiles.hip / features.hip / denoise.hip / denoise_error.hip. */
+ * stops on it, sample levels per tile from a pilot, block rows) and the _host twins.  No kernel lives here: every render ends in render_impl
+ * (nori_hip.hip), everything else in film.hip / film_tiles.hip / film_alloc.hip / features.hip / denoise.hip / denoise_error.hip. */
 #include <cstring>
 #include <initializer_list>
 #include "ctx.h"      /* (the HIP runtime, <algorithm>, <string>, <vector>) */
@@ -628,6 +628,193 @@ int nori_hip_render_adaptive_denoised_host(nori_hip_ctx *ctx, const nori_render_
         RC_TRY(nori_hip_render_adaptive_denoised(ctx, params, pass_spp, target_tile_err, denoise_params, d[0], d[1], albedo ? d[2] : nullptr, normal ? d[3] : nullptr,
                                                  depth ? d[4] : nullptr, d[5], d[6], d[7], d[9], out, stats));
         if (err) { RC_TRY(nori_hip_denoised_error_map(ctx, d[5], d[6], d[7], d[8], target_tile_err, nullptr, params->stream)); HIP_TRY(ctx, hipStreamSynchronize((hipStream_t) params->stream)); }
+        return NORI_OK;
+    });
+}
+
+/* ---- sample levels per tile from a pilot (film_alloc.h): nori_hip_allocate_tiles, nori_hip_render_allocated ---- */
+
+static int check_allocate(nori_hip_ctx *ctx, const char *what, const nori_allocate_params *ap, uint32_t spp_count, AllocLevels &lv) {
+    const std::string w(what);
+    if (!ap) { ctx->error = w + ": no nori_allocate_params"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (ap->pilot_spp < 2u) { ctx->error = w + ": pilot_spp must be at least 2 (one sample has no variance)"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (ap->max_rounds < 1u) { ctx->error = w + ": max_rounds must be at least 1"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (!(ap->target_tile_err >= 0.0f)) { ctx->error = w + ": the target error must be a number >= 0"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (!(ap->headroom >= 1.0f)) { ctx->error = w + ": headroom must be a number >= 1"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (ap->metric != 0 && ap->metric != 1) { ctx->error = w + ": metric must be 0 (raw) or 1 (denoised)"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (!alloc_levels(ap->pilot_spp, spp_count, lv)) { ctx->error = w + ": spp_count (the most a pixel may get) must be at least pilot_spp"; return NORI_ERR_INVALID_ARGUMENT; }
+    return NORI_OK;
+}
+
+int nori_hip_allocate_tiles(nori_hip_ctx *ctx, const nori_allocate_params *alloc, uint32_t spp_count, const void *d_tile_err,
+                            uint32_t *level, uint32_t *done, uint32_t *tiles_out, uint32_t *bucket_begin) {
+    if (!ctx || !ctx->have_scene) return NORI_ERR_NOT_READY;
+    if (!d_tile_err || !level || !done || !tiles_out || !bucket_begin) { ctx->error = "allocate_tiles: needs the tile errors, levels, done flags, a list and bucket_begin to fill"; return NORI_ERR_INVALID_ARGUMENT; }
+    AllocLevels lv;
+    RC_TRY(check_allocate(ctx, "allocate_tiles", alloc, spp_count, lv));
+    const uint32_t n_frame = frame_tiles(ctx);
+    for (uint32_t t = 0; t < n_frame; ++t)
+        if (level[t] > lv.J) { ctx->error = "allocate_tiles: tile " + std::to_string(t) + " is at level " + std::to_string(level[t]) + ", the top level is " + std::to_string(lv.J); return NORI_ERR_INVALID_ARGUMENT; }
+    DeviceGuard g(ctx->device);
+    FilmAlloc &A = ctx->alloc;
+    const std::string err0 = film_alloc_reserve(A, n_frame);
+    if (!err0.empty()) { ctx->error = err0; return NORI_ERR_OUT_OF_MEMORY; }
+    std::vector<uint32_t> flags(n_frame);
+    for (uint32_t t = 0; t < n_frame; ++t) flags[t] = done[t] ? 1u : 0u;
+    const size_t words = (size_t) n_frame * sizeof(uint32_t);
+    HIP_TRY(ctx, hipMemcpy(A.level, level, words, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy(A.done, flags.data(), words, hipMemcpyHostToDevice));
+    uint32_t begin[kAllocMaxBuckets + 1];
+    const std::string err = film_alloc_round(A, (const float *) d_tile_err, alloc->target_tile_err, alloc->headroom, lv, n_frame, begin, nullptr);
+    if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    HIP_TRY(ctx, hipMemcpy(level, A.level, words, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(done, A.done, words, hipMemcpyDeviceToHost));
+    const uint32_t n_moving = begin[kAllocMaxBuckets];
+    if (n_moving) HIP_TRY(ctx, hipMemcpy(tiles_out, A.list, (size_t) n_moving * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    memcpy(bucket_begin, begin, sizeof(begin));
+    return NORI_OK;
+}
+
+int nori_hip_render_allocated(nori_hip_ctx *ctx, const nori_render_params *params, const nori_allocate_params *alloc,
+                              const nori_denoise_params *denoise_params, void *d_rgbw, void *d_m2, const void *d_albedo, const void *d_normal,
+                              const void *d_depth, void *d_rgb_out, void *d_var_out, void *d_wsum, void *d_tile_spp, void *d_level_log,
+                              nori_adaptive_summary *out, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !d_rgbw || !d_m2) return NORI_ERR_INVALID_ARGUMENT;
+    AllocLevels lv;
+    RC_TRY(check_allocate(ctx, "render_allocated", alloc, params->spp_count, lv));
+    const bool denoised = alloc->metric == 1;
+    if (denoised && (!d_rgb_out || !d_var_out || !d_wsum)) { ctx->error = "render_allocated: metric 1 needs buffers for the denoised frame, its variance and its weight sums"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (params->tile_mod != 1) { ctx->error = "render_allocated: renders whole frames (tile_mod 1): the loop shares the tiles out itself"; return NORI_ERR_INVALID_ARGUMENT; }
+    RC_TRY(check_tiles_params(ctx, params, nullptr));
+    DenoiseLaunch dl;
+    if (denoised) {
+        const std::string bad = denoise_plan(denoise_params, dl);
+        if (!bad.empty()) { ctx->error = bad; return NORI_ERR_INVALID_ARGUMENT; }
+    }
+    DeviceGuard g(ctx->device);
+    hipStream_t s = (hipStream_t) params->stream;
+    FilmTiles &T = ctx->tiles;
+    FilmAlloc &A = ctx->alloc;
+    const uint32_t n_frame = frame_tiles(ctx);
+    const size_t words = (size_t) n_frame * sizeof(uint32_t);
+    const size_t n_pixels = (size_t) ctx->host.camera.width * (size_t) ctx->host.camera.height;
+    {
+        std::string err = film_tiles_reserve(T, n_frame);      /* the inverse table and the tile errors are the context's */
+        if (err.empty()) err = film_alloc_reserve(A, n_frame);
+        if (!err.empty()) { ctx->error = err; return NORI_ERR_OUT_OF_MEMORY; }
+    }
+    HIP_TRY(ctx, hipMemsetAsync(A.level, 0, words, s));
+    HIP_TRY(ctx, hipMemsetAsync(A.done, 0, words, s));
+    if (denoised) {
+        HIP_TRY(ctx, hipMemsetAsync(d_rgb_out, 0, n_pixels * 3 * sizeof(float), s));
+        HIP_TRY(ctx, hipMemsetAsync(d_var_out, 0, n_pixels * 3 * sizeof(float), s));
+        HIP_TRY(ctx, hipMemsetAsync(d_wsum, 0, n_pixels * sizeof(float), s));
+    }
+    auto log_levels = [&](uint32_t row) -> int {
+        if (d_level_log) HIP_TRY(ctx, hipMemcpyAsync((uint32_t *) d_level_log + (size_t) row * n_frame, A.level, words, hipMemcpyDeviceToDevice, s));
+        return NORI_OK;
+    };
+    /* the tile errors of the frames as they are, into T.tile_err; metric 1: step A, then the filter over d_list (null: the whole frame) */
+    auto evaluate = [&](const uint32_t *d_list, uint32_t n_list) -> int {
+        std::string err;
+        if (denoised) {
+            RC_TRY(denoise_var_run(ctx, dl, d_rgbw, d_m2, d_albedo, d_normal, d_depth, d_list, n_list, d_rgb_out, d_var_out, d_wsum, s));
+            err = denoised_tile_errors(ctx->host.camera.width, ctx->host.camera.height, (const float *) d_rgb_out, (const float *) d_var_out, (const float *) d_wsum, T.tile_err, s);
+        } else
+            err = film_tile_errors(ctx->dev, (const float *) d_rgbw, (const float *) d_m2, T.tile_err, s);
+        if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+        return NORI_OK;
+    };
+    nori_render_stats total; memset(&total, 0, sizeof(total));
+    uint32_t passes = 0, rounds = 0;
+    {      /* the pilot: every tile, level 0 */
+        nori_render_params p = *params;
+        p.spp_count = lv.spp[0];
+        nori_render_stats st;
+        RC_TRY(render_impl(ctx, &p, d_rgbw, &st, nullptr, (float *) d_m2));
+        add_stats(total, st);
+        ++passes;
+        RC_TRY(log_levels(0));
+    }
+    uint32_t n_active = n_frame;      /* tiles not done: all of them, then the tiles the last round moved (A.list, whole) */
+    bool fresh = false;               /* T.tile_err is of the frames as they are */
+    while (rounds < alloc->max_rounds) {
+        RC_TRY(evaluate(rounds == 0 ? nullptr : A.list, rounds == 0 ? 0u : n_active));
+        uint32_t begin[kAllocMaxBuckets + 1];
+        const std::string err = film_alloc_round(A, T.tile_err, alloc->target_tile_err, alloc->headroom, lv, n_frame, begin, s);
+        if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+        n_active = begin[kAllocMaxBuckets];
+        fresh = !denoised;      /* (metric 1: only the tiles not done were filtered) */
+        if (n_active == 0) break;
+        for (uint32_t i = 0; i < lv.J; ++i)
+            for (uint32_t j = i + 1; j <= lv.J; ++j) {
+                const uint32_t b = alloc_bucket(lv.J, i, j), n_b = begin[b + 1] - begin[b];
+                if (n_b == 0) continue;
+                const std::string ierr = film_alloc_inverse(A, begin[b], n_b, T.inverse, n_frame, s);
+                if (!ierr.empty()) { ctx->error = ierr; return NORI_ERR_INTERNAL; }
+                FilmTiles view;      /* the bucket's slice as a render's current list; owns nothing */
+                view.list[0] = A.list + begin[b]; view.inverse = T.inverse; view.capacity = T.capacity; view.cur = 0; view.n = n_b;
+                nori_render_params p = *params;
+                p.spp_begin = params->spp_begin + lv.spp[i]; p.spp_count = lv.spp[j] - lv.spp[i];
+                nori_render_stats st;
+                RC_TRY(render_impl(ctx, &p, d_rgbw, &st, nullptr, (float *) d_m2, &view));
+                add_stats(total, st);
+                ++passes;
+            }
+        T.n = 0;      /* the context's own list does not describe the inverse table any more */
+        fresh = false;
+        ++rounds;
+        RC_TRY(log_levels(rounds));
+    }
+    for (uint32_t r = rounds + 1; r <= alloc->max_rounds; ++r) RC_TRY(log_levels(r));      /* rounds that did not run: the levels as they were left */
+    /* one more evaluation for the summary (metric 1: the filter over the whole frame, so the outputs are denoise_var of the frames as they are left) */
+    if (denoised || (out && !fresh)) RC_TRY(evaluate(nullptr, 0));
+    if (d_tile_spp) {
+        const std::string err = film_alloc_tile_spp(A, lv, (uint32_t *) d_tile_spp, n_frame, s);
+        if (!err.empty()) { ctx->error = err; return NORI_ERR_INTERNAL; }
+    }
+    if (out) {
+        memset(out, 0, sizeof(*out));
+        std::vector<float> te(n_frame);
+        std::vector<uint32_t> level(n_frame);
+        HIP_TRY(ctx, hipMemcpyAsync(te.data(), T.tile_err, (size_t) n_frame * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipMemcpyAsync(level.data(), A.level, words, hipMemcpyDeviceToHost, s));
+        HIP_TRY(ctx, hipStreamSynchronize(s));
+        uint32_t n_unconverged = 0;
+        for (uint32_t i = 0; i < n_frame; ++i) n_unconverged += !(te[i] <= alloc->target_tile_err) ? 1u : 0u;
+        out->passes = passes; out->n_tiles = n_frame; out->n_unconverged = n_unconverged;
+        out->spp_min = lv.spp[*std::min_element(level.begin(), level.end())]; out->spp_max = lv.spp[*std::max_element(level.begin(), level.end())];
+        if (denoised) RC_TRY(nori_hip_denoised_error_map(ctx, d_rgb_out, d_var_out, d_wsum, nullptr, alloc->target_tile_err, &out->frame, params->stream));
+        else RC_TRY(nori_hip_error_map(ctx, d_rgbw, d_m2, nullptr, alloc->target_tile_err, &out->frame, params->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    if (stats) *stats = total;
+    return NORI_OK;
+}
+
+int nori_hip_render_allocated_host(nori_hip_ctx *ctx, const nori_render_params *params, const nori_allocate_params *alloc,
+                                   const nori_denoise_params *denoise_params, float *rgbw, float *m2, const float *albedo, const float *normal,
+                                   const float *depth, float *rgb_out, float *var_out, float *wsum, float *err, uint32_t *tile_spp,
+                                   uint32_t *level_log, nori_adaptive_summary *out, nori_render_stats *stats) {
+    REQUIRE_ACCEL(ctx);
+    if (!params || !rgbw || !alloc) return NORI_ERR_INVALID_ARGUMENT;
+    const bool denoised = alloc->metric == 1;
+    if (denoised && !rgb_out) { ctx->error = "render_allocated: metric 1 needs a buffer for the denoised frame"; return NORI_ERR_INVALID_ARGUMENT; }
+    const size_t fb = frame_bytes(ctx), pb = pixel_bytes(ctx), tb = (size_t) frame_tiles(ctx) * sizeof(uint32_t);
+    const size_t dn = denoised ? 1 : 0;      /* (metric 0: the denoiser's parts are empty) */
+    /* parts 0 .. 10 = rgbw, m2, albedo, normal, depth, rgb_out, var_out, wsum, err, tile_spp, level_log */
+    return host_twin(ctx, true, {{fb, nullptr, rgbw}, {fb, nullptr, m2}, {dn * fb, dn ? albedo : nullptr, nullptr}, {dn * fb, dn ? normal : nullptr, nullptr},
+                                 {dn * fb, dn ? depth : nullptr, nullptr}, {dn * 3 * pb, nullptr, dn ? rgb_out : nullptr}, {dn * 3 * pb, nullptr, dn ? var_out : nullptr},
+                                 {dn * pb, nullptr, dn ? wsum : nullptr}, {pb, nullptr, err}, {tb, nullptr, tile_spp},
+                                 {level_log ? ((size_t) alloc->max_rounds + 1) * tb : 0, nullptr, level_log}}, [&](char **d) -> int {
+        RC_TRY(nori_hip_render_allocated(ctx, params, alloc, denoise_params, d[0], d[1], dn && albedo ? d[2] : nullptr, dn && normal ? d[3] : nullptr,
+                                         dn && depth ? d[4] : nullptr, dn ? d[5] : nullptr, dn ? d[6] : nullptr, dn ? d[7] : nullptr, d[9], level_log ? d[10] : nullptr, out, stats));
+        if (err) {
+            if (denoised) RC_TRY(nori_hip_denoised_error_map(ctx, d[5], d[6], d[7], d[8], alloc->target_tile_err, nullptr, params->stream));
+            else RC_TRY(nori_hip_error_map(ctx, d[0], d[1], d[8], alloc->target_tile_err, nullptr, params->stream));
+            HIP_TRY(ctx, hipStreamSynchronize((hipStream_t) params->stream));
+        }
         return NORI_OK;
     });
 }

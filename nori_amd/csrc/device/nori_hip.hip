@@ -540,6 +540,7 @@ void nori_hip_destroy(nori_hip_ctx *ctx) {
     film_release(ctx->film);
     film_moments_release(ctx->moments);
     film_tiles_release(ctx->tiles);
+    film_alloc_release(ctx->alloc);
     feature_store_release(ctx->features);
     denoise_store_release(ctx->denoise);
     denoise_error_release(ctx->denoise_error);

@@ -1,5 +1,5 @@
 /*
- * main.cpp -- `nori <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]] [--denoise [--denoise-radius R] [--denoise-patch F]] [--target-denoised-error E [--pass-spp K] [--feature-spp K] [--denoise-radius R] [--denoise-patch F]]`
+ * main.cpp -- `nori <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]] [--denoise [--denoise-radius R] [--denoise-patch F]] [--target-denoised-error E [--pass-spp K] [--feature-spp K] [--denoise-radius R] [--denoise-patch F]] [--allocate [--pilot-spp K] [--rounds N]]`
  * Command line of the reference (src/main.cpp:150-246).  There is no GUI on a
  * compute node: --no-gui is accepted and implied; --threads is accepted for
  * compatibility (the work runs on the GPU).  --seed block renders with the
@@ -26,7 +26,11 @@
  * min(sampleCount, 16)), then runs nori_hip_render_adaptive_denoised: passes of --pass-spp samples per pixel over the 16x16 tiles
  * whose DENOISED error (nori_hip_denoised_tile_errors) is still above E, the scene's sampleCount being the most a pixel gets.  It
  * writes the usual output (the raw frame), <scene>.denoised.exr, <scene>.error.exr (the denoised error map) and <scene>.spp.exr and
- * prints where it stopped; one device only, not together with --denoise, --target-error or --adaptive.  A <test> root runs during parsing
+ * prints where it stopped; one device only, not together with --denoise, --target-error or --adaptive.  --allocate modifies --target-error E
+ * and --target-denoised-error E: instead of passes of --pass-spp samples, a pilot of K samples per pixel (--pilot-spp, default 16) and at
+ * most N rounds (--rounds, default 3) that render every tile still above E up to the level K << j its error predicts, one render per
+ * group of tiles that share a move (nori_hip_render_allocated); it writes the files of those modes, <scene>.error.exr and
+ * <scene>.spp.exr included; one device only, not together with --adaptive.  A <test> root runs during parsing
  * (its activate()), as in the reference; failures exit with -1.
  */
 #include <nori/bitmap.h>
@@ -36,7 +40,7 @@ using namespace nori;
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        cerr << "Syntax: " << argv[0] << " <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]] [--denoise [--denoise-radius R] [--denoise-patch F]] [--target-denoised-error E [--pass-spp K] [--feature-spp K] [--denoise-radius R] [--denoise-patch F]]" << endl;
+        cerr << "Syntax: " << argv[0] << " <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]] [--denoise [--denoise-radius R] [--denoise-patch F]] [--target-denoised-error E [--pass-spp K] [--feature-spp K] [--denoise-radius R] [--denoise-patch F]] [--allocate [--pilot-spp K] [--rounds N]]" << endl;
         return -1;
     }
     std::string sceneName;
@@ -44,6 +48,8 @@ int main(int argc, char **argv) {
     long featureSpp = 16;
     bool denoise = false, haveDenoiseRadius = false, haveDenoisePatch = false;
     bool toDenoisedError = false;
+    bool allocate = false, havePilotSpp = false, haveRounds = false;
+    long pilotSpp = 16, rounds = 3;
     long denoiseRadius = 5, denoisePatch = 1;
     float targetError = 0.0f;
     long passSpp = 16;
@@ -104,6 +110,21 @@ int main(int argc, char **argv) {
         } else if (token == "--adaptive") {
             adaptive = true;
             continue;
+        } else if (token == "--allocate") {
+            allocate = true;
+            continue;
+        } else if (token == "--pilot-spp" || token == "--rounds") {
+            const bool pilot = token == "--pilot-spp";
+            char *end = nullptr;
+            long v = -1;
+            if (i + 1 < argc) v = std::strtol(argv[i + 1], &end, 10);
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || v < (pilot ? 2 : 1) || v > 0x7fffffffl) {
+                cerr << "Usage: \"" << token << "\" expects " << (pilot ? "a number of samples per pixel >= 2 for the pilot" : "a number of rounds >= 1") << " following it (with --allocate)." << endl;
+                return -1;
+            }
+            (pilot ? pilotSpp : rounds) = v;
+            (pilot ? havePilotSpp : haveRounds) = true; ++i;
+            continue;
         } else if (token == "--features") {
             features = true;
             continue;
@@ -150,6 +171,22 @@ int main(int argc, char **argv) {
         } else {
             cerr << "Fatal error: unknown file \"" << token << "\", expected an extension of type .xml or .exr" << endl;
         }
+    }
+    if (allocate && adaptive) {
+        cerr << "Usage: \"--allocate\" plans the samples from a pilot and does not go with --adaptive." << endl;
+        return -1;
+    }
+    if (allocate && gpus > 1) {
+        cerr << "Usage: \"--allocate\" renders on one device: moment frames over several GPUs are not supported (got --gpus " << gpus << ")." << endl;
+        return -1;
+    }
+    if (allocate && !toError && !toDenoisedError) {
+        cerr << "Usage: \"--allocate\" goes with --target-error E or --target-denoised-error E." << endl;
+        return -1;
+    }
+    if ((havePilotSpp || haveRounds) && !allocate) {
+        cerr << "Usage: \"" << (havePilotSpp ? "--pilot-spp" : "--rounds") << "\" goes with --allocate." << endl;
+        return -1;
     }
     if (toDenoisedError && (denoise || toError || adaptive)) {
         cerr << "Usage: \"--target-denoised-error\" is a loop of its own and does not go with " << (denoise ? "--denoise" : toError ? "--target-error" : "--adaptive") << "." << endl;
@@ -213,9 +250,14 @@ int main(int argc, char **argv) {
             dn.radius = (uint32_t) denoiseRadius; dn.patch = (uint32_t) denoisePatch;
             const uint32_t denoiseFeatureSpp = haveFeatureSpp ? (uint32_t) featureSpp
                                                : toDenoisedError ? (uint32_t) std::min<size_t>(scene->getSampler()->getSampleCount(), 16) : (uint32_t) scene->getSampler()->getSampleCount();
-            std::unique_ptr<ImageBlock> result = toDenoisedError ? renderSceneAdaptiveDenoised(scene, targetError, (uint32_t) passSpp, dn, denoiseFeatureSpp, adaptiveSummary, denoised, errorMap, tileSpp, &st)
+            nori_allocate_params ap;      /* --allocate: the pilot is no longer than the scene's samples unless --pilot-spp says so */
+            ap.pilot_spp = havePilotSpp ? (uint32_t) pilotSpp : (uint32_t) std::max<size_t>(2, std::min<size_t>(scene->getSampler()->getSampleCount(), (size_t) pilotSpp));
+            ap.max_rounds = (uint32_t) rounds; ap.target_tile_err = targetError; ap.headroom = 1.0f; ap.metric = toDenoisedError ? 1 : 0;
+            const nori_allocate_params *apUsed = allocate ? &ap : nullptr;
+            if (allocate && !toDenoisedError) adaptive = true;      /* the same files and the same report as --adaptive */
+            std::unique_ptr<ImageBlock> result = toDenoisedError ? renderSceneAdaptiveDenoised(scene, targetError, (uint32_t) passSpp, dn, denoiseFeatureSpp, adaptiveSummary, denoised, errorMap, tileSpp, &st, apUsed)
                                                  : denoise ? renderSceneDenoised(scene, dn, denoiseFeatureSpp, denoised, &st)
-                                                 : adaptive ? renderSceneAdaptive(scene, targetError, (uint32_t) passSpp, adaptiveSummary, errorMap, tileSpp, &st)
+                                                 : adaptive ? renderSceneAdaptive(scene, targetError, (uint32_t) passSpp, adaptiveSummary, errorMap, tileSpp, &st, apUsed)
                                                  : toError ? renderSceneToError(scene, targetError, (uint32_t) passSpp, sppDone, summary, errorMap, &st)
                                                          : renderScene(scene, &st);
             cout << "done. (took " << timer.elapsedString() << "; kernel " << timeString(st.kernel_ms, true) << ", "
@@ -228,7 +270,7 @@ int main(int argc, char **argv) {
             bitmap->savePNG(outputName);
             if (adaptive || toDenoisedError) {
                 const nori_error_summary &f = adaptiveSummary.frame;
-                cout << (toDenoisedError ? "Denoised error: stopped after " : "Stopped after ") << adaptiveSummary.passes << " passes: " << adaptiveSummary.spp_min << " to " << adaptiveSummary.spp_max << " samples per pixel, "
+                cout << (toDenoisedError ? "Denoised error: stopped after " : "Stopped after ") << adaptiveSummary.passes << (allocate ? " render calls (a pilot of " + std::to_string(ap.pilot_spp) + " samples per pixel, at most " + std::to_string(ap.max_rounds) + " rounds): " : " passes: ") << adaptiveSummary.spp_min << " to " << adaptiveSummary.spp_max << " samples per pixel, "
                      << adaptiveSummary.n_unconverged << " of " << adaptiveSummary.n_tiles << " tiles above the target " << targetError << (toDenoisedError ? "; mean predicted error of the denoised frame " : "; mean error ")
                      << f.sum_err / (double) std::max<uint64_t>(f.n_pixels, 1) << " (max " << f.max_err << ", " << f.n_above << " of " << f.n_pixels << " pixels above the target)" << endl;
                 Bitmap errorBitmap(scene->getCamera()->getOutputSize()), sppBitmap(scene->getCamera()->getOutputSize());

@@ -304,9 +304,11 @@ std::unique_ptr<ImageBlock> renderScene(Scene *scene, nori_render_stats *stats =
 std::unique_ptr<ImageBlock> renderSceneToError(Scene *scene, float targetError, uint32_t passSpp, uint32_t &sppDone,
                                                nori_error_summary &summary, std::vector<float> &errorMap, nori_render_stats *stats = nullptr);
 /* `--target-error E --adaptive`: nori_hip_render_adaptive_host -- passes over the tiles whose error is still above E; tileSpp: the
-   samples every 16x16 tile received (row-major tile grid) */
+   samples every 16x16 tile received (row-major tile grid).  With `allocate` (`--allocate`) the samples are planned from a pilot
+   instead: nori_hip_render_allocated_host, metric 0; passSpp is not used */
 std::unique_ptr<ImageBlock> renderSceneAdaptive(Scene *scene, float targetError, uint32_t passSpp, nori_adaptive_summary &summary,
-                                                std::vector<float> &errorMap, std::vector<uint32_t> &tileSpp, nori_render_stats *stats = nullptr);
+                                                std::vector<float> &errorMap, std::vector<uint32_t> &tileSpp, nori_render_stats *stats = nullptr,
+                                                const nori_allocate_params *allocate = nullptr);
 /* `--features`: nori_hip_render_features_host on the scene's device -- the first-hit albedo, shading-normal and depth frames of camera
    samples [0, spp) of every pixel, RGBW frames with the layout of renderScene's block (`border` receives its border); decode as
    include/nori_hip.h states */
@@ -321,9 +323,11 @@ std::unique_ptr<ImageBlock> renderSceneDenoised(Scene *scene, const nori_denoise
 
 /* `--target-denoised-error E`: the three feature frames through renderSceneFeatures, then nori_hip_render_adaptive_denoised_host --
    passes over the tiles whose DENOISED error is still above E.  The returned block is the raw frame; `denoised` receives height *
-   width * 3 floats, `errorMap` the denoised error map, `tileSpp` the samples every 16x16 tile received */
+   width * 3 floats, `errorMap` the denoised error map, `tileSpp` the samples every 16x16 tile received.  With `allocate`
+   (`--allocate`): nori_hip_render_allocated_host, metric 1 */
 std::unique_ptr<ImageBlock> renderSceneAdaptiveDenoised(Scene *scene, float targetError, uint32_t passSpp, const nori_denoise_params &dn, uint32_t featureSpp,
                                                         nori_adaptive_summary &summary, std::vector<float> &denoised, std::vector<float> &errorMap,
-                                                        std::vector<uint32_t> &tileSpp, nori_render_stats *stats = nullptr);
+                                                        std::vector<uint32_t> &tileSpp, nori_render_stats *stats = nullptr,
+                                                        const nori_allocate_params *allocate = nullptr);
 
 NORI_NAMESPACE_END

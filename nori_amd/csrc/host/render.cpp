@@ -106,7 +106,8 @@ std::unique_ptr<ImageBlock> renderSceneToError(Scene *scene, float targetError, 
 }
 
 std::unique_ptr<ImageBlock> renderSceneAdaptive(Scene *scene, float targetError, uint32_t passSpp, nori_adaptive_summary &summary,
-                                                std::vector<float> &errorMap, std::vector<uint32_t> &tileSpp, nori_render_stats *stats) {
+                                                std::vector<float> &errorMap, std::vector<uint32_t> &tileSpp, nori_render_stats *stats,
+                                                const nori_allocate_params *allocate) {
     const Camera *camera = scene->getCamera();
     scene->getIntegrator()->preprocess(scene);
     if (const char *gpus = std::getenv("NORI_GPUS"))
@@ -127,8 +128,12 @@ std::unique_ptr<ImageBlock> renderSceneAdaptive(Scene *scene, float targetError,
     params.seed_mode = NORI_SEED_PER_SAMPLE;
     nori_render_stats local;
     Device &dev = scene->device();
-    dev.check(nori_hip_render_adaptive_host(dev.ctx(), &params, passSpp, targetError, result->data(), nullptr, errorMap.data(), tileSpp.data(), &summary,
-                                            stats ? stats : &local), "nori_hip_render_adaptive_host");
+    if (allocate)
+        dev.check(nori_hip_render_allocated_host(dev.ctx(), &params, allocate, nullptr, result->data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                                 errorMap.data(), tileSpp.data(), nullptr, &summary, stats ? stats : &local), "nori_hip_render_allocated_host");
+    else
+        dev.check(nori_hip_render_adaptive_host(dev.ctx(), &params, passSpp, targetError, result->data(), nullptr, errorMap.data(), tileSpp.data(), &summary,
+                                                stats ? stats : &local), "nori_hip_render_adaptive_host");
     return result;
 }
 
@@ -186,7 +191,7 @@ std::unique_ptr<ImageBlock> renderSceneDenoised(Scene *scene, const nori_denoise
 
 std::unique_ptr<ImageBlock> renderSceneAdaptiveDenoised(Scene *scene, float targetError, uint32_t passSpp, const nori_denoise_params &dn, uint32_t featureSpp,
                                                         nori_adaptive_summary &summary, std::vector<float> &denoised, std::vector<float> &errorMap,
-                                                        std::vector<uint32_t> &tileSpp, nori_render_stats *stats) {
+                                                        std::vector<uint32_t> &tileSpp, nori_render_stats *stats, const nori_allocate_params *allocate) {
     const Camera *camera = scene->getCamera();
     scene->getIntegrator()->preprocess(scene);
     if (const char *gpus = std::getenv("NORI_GPUS"))
@@ -212,9 +217,13 @@ std::unique_ptr<ImageBlock> renderSceneAdaptiveDenoised(Scene *scene, float targ
     params.seed_mode = NORI_SEED_PER_SAMPLE;
     nori_render_stats local;
     Device &dev = scene->device();
-    dev.check(nori_hip_render_adaptive_denoised_host(dev.ctx(), &params, passSpp, targetError, &dn, result->data(), nullptr, fa.data(), fn.data(), fd.data(),
-                                                     denoised.data(), nullptr, nullptr, errorMap.data(), tileSpp.data(), &summary, stats ? stats : &local),
-              "nori_hip_render_adaptive_denoised_host");
+    if (allocate)
+        dev.check(nori_hip_render_allocated_host(dev.ctx(), &params, allocate, &dn, result->data(), nullptr, fa.data(), fn.data(), fd.data(), denoised.data(), nullptr,
+                                                 nullptr, errorMap.data(), tileSpp.data(), nullptr, &summary, stats ? stats : &local), "nori_hip_render_allocated_host");
+    else
+        dev.check(nori_hip_render_adaptive_denoised_host(dev.ctx(), &params, passSpp, targetError, &dn, result->data(), nullptr, fa.data(), fn.data(), fd.data(),
+                                                         denoised.data(), nullptr, nullptr, errorMap.data(), tileSpp.data(), &summary, stats ? stats : &local),
+                  "nori_hip_render_adaptive_denoised_host");
     return result;
 }
 

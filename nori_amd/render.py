@@ -674,6 +674,100 @@ class Renderer:
         r["summary"], r["stats"] = out.as_dict(), st.as_dict()
         return r
 
+    # -- sample levels per tile from a pilot (include/nori_hip.h: nori_hip_allocate_tiles, nori_hip_render_allocated) --
+    @staticmethod
+    def allocate_levels(pilot_spp, spp_count):
+        """[spp_0 .. spp_J]: spp_j = pilot_spp << j, J = min(7, floor(log2(spp_count / pilot_spp)))"""
+        assert pilot_spp >= 1 and spp_count >= pilot_spp
+        J = 0
+        while J < capi.ALLOC_MAX_LEVEL and (pilot_spp << (J + 1)) <= spp_count:
+            J += 1
+        return [pilot_spp << j for j in range(J + 1)]
+
+    def allocate_tiles(self, tile_err, target, level, done, pilot_spp=16, spp_count=None, headroom=1.0, max_rounds=1, metric=0):
+        """One round of the allocation without a render: (level, done, tiles, bucket_begin) -- the new levels and done flags (uint32,
+        one per tile), the moving tiles grouped by pair (i, j) ascending in i then j (ascending id inside a pair), and the 29 offsets of
+        the pairs in that array.  tile_err: one float per tile, a torch CUDA tensor or a numpy array (copied to the device)."""
+        import torch
+        if isinstance(tile_err, np.ndarray):
+            tile_err = torch.from_numpy(np.ascontiguousarray(tile_err, dtype=np.float32)).to(f"cuda:{self.device}")
+        ty, tx = self.tile_grid()
+        assert tile_err.is_cuda and tile_err.is_contiguous() and tile_err.numel() == ty * tx and str(tile_err.dtype) == "torch.float32"
+        level = np.array(level, dtype=np.uint32).reshape(-1)
+        done = np.array(done, dtype=np.uint32).reshape(-1)
+        assert level.size == done.size == ty * tx
+        spp = self.scene.sample_count if spp_count is None else spp_count
+        ap = capi.AllocateParams(int(pilot_spp), int(max_rounds), float(target), float(headroom), int(metric))
+        tiles, begin = np.zeros(ty * tx, np.uint32), np.zeros(capi.ALLOC_MAX_BUCKETS + 1, np.uint32)
+        torch.cuda.synchronize(tile_err.device)      # the call runs on the default stream
+        self._check(self._lib.nori_hip_allocate_tiles(self._h, C.byref(ap), int(spp), C.c_void_p(tile_err.data_ptr()), ptr(level), ptr(done), ptr(tiles), ptr(begin)),
+                    "allocate_tiles")
+        return level, done, tiles[:int(begin[-1])].copy(), begin
+
+    def render_allocated(self, rgbw_tensor, m2_tensor, target_tile_err, albedo=None, normal=None, depth=None, metric=0, pilot_spp=16, max_rounds=3, headroom=1.0,
+                         spp_count=None, spp_begin=0, stream=None, count_traversal=False, time_kernels=False, **params):
+        """The loop of render_allocated_host on torch CUDA tensors: accumulates into both frame tensors.  metric 0 returns (tile_spp
+        (tiles_y, tiles_x) int32, level_log (max_rounds + 1, tiles) int32, summary dict, stats dict); metric 1 (the denoised error; the
+        feature frames and the nori_denoise_params count) returns (rgb_out, var_out, wsum, tile_spp, level_log, summary dict, stats dict)."""
+        import torch
+        assert self._is_frame(rgbw_tensor) and self._is_frame(m2_tensor)
+        for t in (albedo, normal, depth):
+            assert t is None or self._is_frame(t)
+        rgb_shape, px_shape = self._pixel_shapes()
+        spp = self.scene.sample_count if spp_count is None else spp_count
+        raw = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        p = self._params(spp_begin, spp, 1, 0, count_traversal, raw, time_kernels)
+        ap = capi.AllocateParams(int(pilot_spp), int(max_rounds), float(target_tile_err), float(headroom), int(metric))
+        dp = capi.DenoiseParams(**params)
+        dev = rgbw_tensor.device
+        ty, tx = self.tile_grid()
+        tile_spp = torch.zeros((ty, tx), dtype=torch.int32, device=dev)
+        level_log = torch.zeros((int(max_rounds) + 1, ty * tx), dtype=torch.int32, device=dev)
+        outs = [None, None, None]
+        if metric == 1:
+            outs = [torch.empty(rgb_shape, dtype=torch.float32, device=dev), torch.empty(rgb_shape, dtype=torch.float32, device=dev),
+                    torch.empty(px_shape, dtype=torch.float32, device=dev)]
+        out, st = capi.AdaptiveSummary(), capi.RenderStats()
+        d = [C.c_void_p(t.data_ptr()) if t is not None else None for t in (rgbw_tensor, m2_tensor, albedo, normal, depth, *outs, tile_spp, level_log)]
+        self._check(self._lib.nori_hip_render_allocated(self._h, C.byref(p), C.byref(ap), C.byref(dp), *d, C.byref(out), C.byref(st)), "render_allocated")
+        tail = (tile_spp, level_log, out.as_dict(), st.as_dict())
+        return tail if metric != 1 else (*outs, *tail)
+
+    def _render_allocated_host(self, metric, target_tile_err, feats, pilot_spp, max_rounds, headroom, spp_count, spp_begin, count_traversal, seed_mode, tile_mod, params):
+        feats = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in feats]
+        for a in feats:
+            assert a is None or a.shape == tuple(self.frame_shape())
+        rgb_shape, px_shape = self._pixel_shapes()
+        spp = self.scene.sample_count if spp_count is None else spp_count
+        p = self._params(spp_begin, spp, tile_mod, 0, count_traversal, None, seed_mode=seed_mode)
+        ap = capi.AllocateParams(int(pilot_spp), int(max_rounds), float(target_tile_err), float(headroom), int(metric))
+        dp = capi.DenoiseParams(**params)
+        n_tiles = self.tile_grid()[0] * self.tile_grid()[1]
+        r = dict(rgbw=np.zeros(self.frame_shape(), np.float32), m2=np.zeros(self.frame_shape(), np.float32), err=np.zeros(px_shape, np.float32),
+                 tile_spp=np.zeros(self.tile_grid(), np.uint32), level_log=np.zeros((max(int(max_rounds), 0) + 1, n_tiles), np.uint32))
+        if metric == 1:
+            r.update(rgb=np.zeros(rgb_shape, np.float32), var=np.zeros(rgb_shape, np.float32), wsum=np.zeros(px_shape, np.float32))
+        out, st = capi.AdaptiveSummary(), capi.RenderStats()
+        self._check(self._lib.nori_hip_render_allocated_host(self._h, C.byref(p), C.byref(ap), C.byref(dp), ptr(r["rgbw"]), ptr(r["m2"]), *[ptr(a) for a in feats],
+                                                             ptr(r.get("rgb")), ptr(r.get("var")), ptr(r.get("wsum")), ptr(r["err"]), ptr(r["tile_spp"]),
+                                                             ptr(r["level_log"]), C.byref(out), C.byref(st)), "render_allocated_host")
+        r["summary"], r["stats"] = out.as_dict(), st.as_dict()
+        return r
+
+    def render_allocated_host(self, target_tile_err, pilot_spp=16, max_rounds=3, headroom=1.0, spp_count=None, spp_begin=0, count_traversal=False,
+                              seed_mode=capi.SEED_PER_SAMPLE, tile_mod=1):
+        """Render to a tile error in few passes: a pilot of `pilot_spp` samples per pixel, then at most `max_rounds` rounds that move
+        every tile still above `target_tile_err` to the level pilot_spp << j its error predicts (at most `spp_count` per pixel), one
+        render per group of tiles that share a move.  Into fresh host arrays; returns a dict: rgbw, m2, err (the error map), tile_spp,
+        level_log ((max_rounds + 1, tiles): the level of every tile after the pilot and after each round), summary, stats."""
+        return self._render_allocated_host(0, target_tile_err, (None, None, None), pilot_spp, max_rounds, headroom, spp_count, spp_begin, count_traversal, seed_mode, tile_mod, {})
+
+    def render_allocated_denoised_host(self, target_tile_err, albedo=None, normal=None, depth=None, pilot_spp=16, max_rounds=3, headroom=1.0, spp_count=None,
+                                       spp_begin=0, count_traversal=False, seed_mode=capi.SEED_PER_SAMPLE, tile_mod=1, **params):
+        """render_allocated_host with the levels set on the error of the DENOISED frame (render_adaptive_denoised_host's metric): the
+        dict also holds rgb, var, wsum -- denoise_var of the frames as they are left --, and err is the denoised error map."""
+        return self._render_allocated_host(1, target_tile_err, (albedo, normal, depth), pilot_spp, max_rounds, headroom, spp_count, spp_begin, count_traversal, seed_mode, tile_mod, params)
+
     # -- film_order = reference shared out: rows of 32x32 blocks (include/nori_hip.h: nori_hip_render_block_rows) --
     def block_rows(self) -> int:
         """rows of 32x32 blocks (NORI_BLOCK_SIZE) in the frame"""
