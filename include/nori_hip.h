@@ -416,6 +416,50 @@ int nori_hip_intersect_device(nori_hip_ctx *ctx, const void *d_rays,
 int nori_hip_sample_rays(nori_hip_ctx *ctx, const float *pixel_samples,
                          size_t n, nori_ray *rays);
 
+/* ------------------------------------------- Thin-lens camera: depth of field
+ *
+ * No counterpart in the reference, whose PerspectiveCamera draws the aperture sample and discards it (src/perspective.cpp:78).
+ * A lens is a state of the context's camera, set after the upload: radius R >= 0 and focus distance F, both in camera space
+ * (F is a depth along the optical axis, not a distance along a ray).  R == 0 is the pinhole and NOT the arithmetic below with a
+ * zero in it: every kernel branches on R > 0, uniformly over a launch, and takes the code it ran before there was a lens -- a
+ * pinhole scene renders the bits it always rendered.
+ *
+ * For R > 0, a camera sample with film position pixelSample and apertureSample a = (a.x, a.y) -- the second pair of floats every
+ * camera sample draws (renderBlock, src/main.cpp:41-46); no random number is added, the streams keep their alignment -- gives,
+ * in float32 without FMA contraction, with the operations of the pinhole (division, reciprocal and square root correctly rounded;
+ * the sine and cosine of squareToUniformDisk are the pinned ones of nori_hip_warp):
+ *   nearP  = sampleToCamera * (pixelSample.x / width, pixelSample.y / height, 0);  d = normalized(nearP)     as nori_hip_sample_rays
+ *   invZ   = 1 / d.z
+ *   pf     = d * (F * invZ)                          the point of the pinhole ray on the plane z = F (one product, then three)
+ *   (lx, ly) = squareToUniformDisk(a)                (NORI_WARP_UNIFORM_DISK);  l = (R * lx, R * ly, 0)
+ *   dl     = normalized(pf - l)
+ *   ray.o  = cameraToWorld * l     (a point: the affine product and the division by w, as the pinhole's origin)
+ *   ray.d  = cameraToWorld * dl    (a vector)
+ *   invZl  = 1 / dl.z;   ray.mint = nearClip * invZl;   ray.maxt = farClip * invZl
+ * All rays of one film position meet at pf, so what lies at depth F is sharp; a point at depth z is spread over a circle of
+ * diameter 2 R |z - F| / z on the plane z = F.
+ *
+ * Who uses it: nori_hip_render on both engines (the megakernel's camera sample; the wavefront engine's first vertex, in its first
+ * extend and its first shade), nori_hip_render_features (feature frames are blurred like the beauty frame they guide) and
+ * nori_hip_sample_rays_lens.  Everything built on those kernels inherits the lens with no code of its own:
+ * nori_hip_render_moments, nori_hip_render_tiles, nori_hip_render_to_error, nori_hip_render_adaptive (and _denoised),
+ * nori_hip_render_allocated, film_order = reference and its block rows, the device group.  The exception is
+ * NORI_SEED_NORI_BLOCK, which exists for parity with the reference's sampler: a render in that mode with R > 0 returns
+ * NORI_ERR_UNSUPPORTED with a message and leaves the context as it was.
+ *
+ * nori_hip_set_lens        the lens of the uploaded scene, from the next launch on.  NORI_ERR_NOT_READY without a scene;
+ *                          NORI_ERR_INVALID_ARGUMENT for a radius that is negative or not finite, and, when radius > 0, for a
+ *                          focus distance that is not finite or not positive (with radius == 0 the focus distance is kept as
+ *                          given and has no effect).  nori_hip_upload_scene resets to the pinhole (0, 0).
+ * nori_hip_get_lens        what was set (either pointer may be NULL).
+ * nori_hip_sample_rays_lens  the operator-level twin: the ray of the statement above for n pairs (pixel_samples, aperture_samples:
+ *                          2n floats each), with the context's lens.  With radius == 0 the bits of nori_hip_sample_rays, which
+ *                          stays the pinhole's twin whatever the lens. */
+int nori_hip_set_lens(nori_hip_ctx *ctx, float radius, float focus_distance);
+int nori_hip_get_lens(const nori_hip_ctx *ctx, float *radius, float *focus_distance);
+int nori_hip_sample_rays_lens(nori_hip_ctx *ctx, const float *pixel_samples, const float *aperture_samples,
+                              size_t n, nori_ray *rays);
+
 /* Integrator::Li (include/nori/integrator.h:42) for n rays; path k draws its
  * random numbers from pcg32.seed(seed_state[k], seed_seq[k]).  rgb: 3n. */
 int nori_hip_li(nori_hip_ctx *ctx, const nori_ray *rays, size_t n,
@@ -692,8 +736,9 @@ int nori_hip_render_adaptive_host(nori_hip_ctx *ctx, const nori_render_params *p
  *
  * The camera sample (px, py, s) is the one nori_hip_render draws (NORI_SEED_PER_SAMPLE), in float32 without FMA contraction:
  *   pcg32.seed(py * width + px, s);  j = (nextFloat, nextFloat);  pixelSample = (px + j.x, py + j.y)
- *   a second pair of floats is drawn for the aperture and not used (src/perspective.cpp:78)
- *   ray = PerspectiveCamera::sampleRay(pixelSample)                      (src/perspective.cpp:76-97; nori_hip_sample_rays)
+ *   a second pair of floats is drawn for the aperture (src/perspective.cpp:78): unused by the pinhole, the lens's apertureSample
+ *   ray = PerspectiveCamera::sampleRay(pixelSample)                      (src/perspective.cpp:76-97; nori_hip_sample_rays;
+ *                                                                         with a lens set: nori_hip_sample_rays_lens, "Thin-lens camera")
  *   its = the closest hit of ray in [mint, maxt]                         (Accel::rayIntersect; nori_hip_intersect)
  * and the sample's three values are
  *   albedo  miss: (0, 0, 0).  Hit on mesh m: NORI_BSDF_MIRROR and NORI_BSDF_DIELECTRIC give (1, 1, 1); NORI_BSDF_DIFFUSE and
@@ -1016,6 +1061,8 @@ const char *nori_hip_group_warning(const nori_hip_group *group);
 int nori_hip_group_engines(const nori_hip_group *group, uint32_t *engines, int capacity);
 /* nori_hip_upload_scene + nori_hip_build_accel on every device, side by side (Scene::activate per device) */
 int nori_hip_group_upload_scene(nori_hip_group *group, const nori_scene_desc *scene, int builder /* nori_accel_builder */);
+/* nori_hip_set_lens on every device's context (the upload resets it, as on one context) */
+int nori_hip_group_set_lens(nori_hip_group *group, float radius, float focus_distance);
 /* The render loop of src/main.cpp:78-119 over the group: samples [spp_begin, spp_begin + spp_count) of every pixel of the
  * width x height frame (params->tile_mod must be 1: the group shares the tiles out itself), merged into the HOST buffer
  * `rgbw` (layout of nori_render_params; overwritten).  stats: counters summed over the devices, times = the slowest

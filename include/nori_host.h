@@ -35,6 +35,11 @@ const char *nori_host_root_string(const nori_host_root *root);
 /* Root is a <scene>: borrow its flattened description (valid until free). */
 int nori_host_scene_desc(const nori_host_root *root, nori_scene_desc *out);
 
+/* Root is a <scene>: the thin lens of its camera (apertureRadius, default 0 = the pinhole, and focusDistance, default 1, of
+ * the <camera>'s property list).  Not part of nori_scene_desc: apply it with nori_hip_set_lens after the upload, as
+ * nori_host_render does.  Either pointer may be NULL. */
+int nori_host_lens(const nori_host_root *root, float *radius, float *focus);
+
 /* Root is a <test>: kind 0 = ttest, 1 = chi2test. */
 typedef struct nori_host_test_info {
     int32_t kind;

@@ -201,6 +201,9 @@ HIP_PROTOTYPES = {
     "nori_hip_intersect": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int]),
     "nori_hip_intersect_device": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int, _P]),
     "nori_hip_sample_rays": (C.c_int, [_P, _P, C.c_size_t, _P]),
+    "nori_hip_set_lens": (C.c_int, [_P, C.c_float, C.c_float]),
+    "nori_hip_get_lens": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "nori_hip_sample_rays_lens": (C.c_int, [_P, _P, _P, C.c_size_t, _P]),
     "nori_hip_li": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P]),
     "nori_hip_bsdf_sample": (C.c_int, [_P, C.POINTER(BsdfDesc), _P, _P, C.c_size_t, _P, _P, _P, _P]),
     "nori_hip_bsdf_eval": (C.c_int, [_P, C.POINTER(BsdfDesc), _P, _P, C.c_size_t, _P]),
@@ -268,6 +271,7 @@ HIP_PROTOTYPES = {
     "nori_hip_group_warning": (C.c_char_p, [_P]),
     "nori_hip_group_engines": (C.c_int, [_P, C.POINTER(C.c_uint32), C.c_int]),
     "nori_hip_group_upload_scene": (C.c_int, [_P, C.POINTER(SceneDesc), C.c_int]),
+    "nori_hip_group_set_lens": (C.c_int, [_P, C.c_float, C.c_float]),
     "nori_hip_group_render_host": (C.c_int, [_P, C.POINTER(RenderParams), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(RenderStats), C.POINTER(C.c_float)]),
 }
 

@@ -56,9 +56,9 @@ __global__ __launch_bounds__(kFeatBlock, kFeatMinWaves) void feature_pass_kernel
             rng_seed(rng, (uint64_t) py * (uint64_t) sc.camera.width + (uint64_t) px, (uint64_t) s);
             const f2 j = rng_next_2d(rng);
             const f2 pixelSample = mk2((float) px + j.x, (float) py + j.y);
-            (void) rng_next_2d(rng);        /* apertureSample: drawn, unused (perspective.cpp:78) */
+            const f2 apertureSample = rng_next_2d(rng);        /* perspective.cpp:78; used by a lens only */
             RayIn ray;
-            camera_sample_ray(sc.camera, pixelSample, ray);
+            camera_sample_ray_lens(sc.camera, pixelSample, apertureSample, ray);
             /* the closest-hit query: the device body of the generic traverse<false> (rt_trace.h), statement for statement -- every
                tree form, no LDS image, the same steps in the same order, hence the same hit.  Spelt out because a call of
                traverse() itself leaves its Trav in memory (the compiler widens the loads of tv.o / tv.d before it splits the

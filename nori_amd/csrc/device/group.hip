@@ -419,6 +419,16 @@ int nori_hip_group_upload_scene(nori_hip_group *g, const nori_scene_desc *scene,
     return NORI_OK;
 }
 
+/* the lens of every context's camera (nori_hip_set_lens): all devices render one camera */
+int nori_hip_group_set_lens(nori_hip_group *g, float radius, float focus_distance) {
+    if (!g) return NORI_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < g->ctx.size(); ++k) {
+        const int rc = nori_hip_set_lens(g->ctx[k], radius, focus_distance);
+        if (rc != NORI_OK) { g->error = "device " + std::to_string(g->devices[k]) + ": " + nori_hip_last_error(g->ctx[k]); return rc; }
+    }
+    return NORI_OK;
+}
+
 int nori_hip_group_render_host(nori_hip_group *g, const nori_render_params *params, int split, int merge, int width, int height,
                                float *rgbw, nori_render_stats *stats, float *merge_ms) {
     if (!g || !params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;

@@ -29,6 +29,7 @@
  *                    render_plan.h  tile geometry, chunk plan, sample cut, wavefront budget and out-of-memory ladder: plain C++
  *                    frame_api.hip  nori_hip_render and every frame-level entry point behind it, the _host twins (no kernel)
  */
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -165,9 +166,9 @@ __global__ __launch_bounds__(kBlock, NORI_RENDER_MIN_WAVES) void render_kernel(D
                     rng_seed(st.rng, (uint64_t) py * (uint64_t) sc.camera.width + (uint64_t) px, (uint64_t) s);
                     const f2 j = rng_next_2d(st.rng);
                     pixelSample = mk2((float) px + j.x, (float) py + j.y);
-                    (void) rng_next_2d(st.rng);        /* apertureSample: drawn, unused (perspective.cpp:78) */
+                    const f2 apertureSample = rng_next_2d(st.rng);        /* perspective.cpp:78; used by a lens only */
                     RayIn cam;
-                    camera_sample_ray(sc.camera, pixelSample, cam);
+                    camera_sample_ray_lens(sc.camera, pixelSample, apertureSample, cam);
                     path_begin(st, cam);
                     ++s; ++nCam;
                 }
@@ -311,6 +312,18 @@ __global__ void sample_rays_kernel(CameraRec cam, const float *ps, size_t n, nor
     if (i >= n) return;
     RayIn r;
     camera_sample_ray(cam, mk2(ps[2 * i], ps[2 * i + 1]), r);
+    nori_ray o;
+    o.o[0] = r.o.x; o.o[1] = r.o.y; o.o[2] = r.o.z; o.d[0] = r.d.x; o.d[1] = r.d.y; o.d[2] = r.d.z;
+    o.mint = r.mint; o.maxt = r.maxt;
+    rays[i] = o;
+}
+
+/* nori_hip_sample_rays_lens: the camera sample the render kernels take (camera_sample_ray_lens), one per thread */
+__global__ void sample_rays_lens_kernel(CameraRec cam, const float *ps, const float *as, size_t n, nori_ray *rays) {
+    const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    RayIn r;
+    camera_sample_ray_lens(cam, mk2(ps[2 * i], ps[2 * i + 1]), mk2(as[2 * i], as[2 * i + 1]), r);
     nori_ray o;
     o.o[0] = r.o.x; o.o[1] = r.o.y; o.o[2] = r.o.z; o.d[0] = r.d.x; o.d[1] = r.d.y; o.d[2] = r.d.z;
     o.mint = r.mint; o.maxt = r.maxt;
@@ -833,6 +846,45 @@ int nori_hip_sample_rays(nori_hip_ctx *ctx, const float *pixel_samples, size_t n
     return NORI_OK;
 }
 
+int nori_hip_sample_rays_lens(nori_hip_ctx *ctx, const float *pixel_samples, const float *aperture_samples, size_t n, nori_ray *rays) {
+    if (!ctx) return NORI_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_scene) { ctx->error = "sample_rays_lens: no scene uploaded"; return NORI_ERR_NOT_READY; }
+    if (n == 0) return NORI_OK;
+    if (!pixel_samples || !aperture_samples || !rays) { ctx->error = "sample_rays_lens: null array"; return NORI_ERR_INVALID_ARGUMENT; }
+    DeviceGuard g(ctx->device);
+    SCRATCH_IN(ctx, dp, pixel_samples, n * 2 * sizeof(float));
+    SCRATCH_IN(ctx, da, aperture_samples, n * 2 * sizeof(float));
+    SCRATCH_OUT(ctx, dr, n * sizeof(nori_ray));
+    hipLaunchKernelGGL(sample_rays_lens_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, ctx->dev.camera,
+                       (const float *) dp.p, (const float *) da.p, n, (nori_ray *) dr.p);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpy(rays, dr.p, n * sizeof(nori_ray), hipMemcpyDeviceToHost));
+    return NORI_OK;
+}
+
+/* The lens of the uploaded scene's camera: two floats of the camera record, which travels to every kernel by value.  Nothing on the
+   device changes until the next launch; a render already enqueued keeps the record it was launched with. */
+int nori_hip_set_lens(nori_hip_ctx *ctx, float radius, float focus_distance) {
+    if (!ctx) return NORI_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_scene) { ctx->error = "set_lens: no scene uploaded"; return NORI_ERR_NOT_READY; }
+    if (!std::isfinite(radius) || radius < 0.0f) { ctx->error = "set_lens: the radius must be finite and not negative"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (radius > 0.0f && (!std::isfinite(focus_distance) || !(focus_distance > 0.0f))) {
+        ctx->error = "set_lens: a lens (radius > 0) needs a finite, positive focus distance";
+        return NORI_ERR_INVALID_ARGUMENT;
+    }
+    ctx->host.camera.lens_radius = ctx->dev.camera.lens_radius = radius;
+    ctx->host.camera.focus_distance = ctx->dev.camera.focus_distance = focus_distance;
+    return NORI_OK;
+}
+
+int nori_hip_get_lens(const nori_hip_ctx *ctx, float *radius, float *focus_distance) {
+    if (!ctx) return NORI_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_scene) return NORI_ERR_NOT_READY;      /* (the context is const: no message) */
+    if (radius) *radius = ctx->host.camera.lens_radius;
+    if (focus_distance) *focus_distance = ctx->host.camera.focus_distance;
+    return NORI_OK;
+}
+
 } // extern "C"
 
 template <int STACK>
@@ -1176,8 +1228,13 @@ int check_render_params(nori_hip_ctx *ctx, const nori_render_params *params, con
         ctx->error = "render: NORI_SEED_NORI_BLOCK renders whole frames from sample 0 (a block's stream is serial: src/independent.cpp:36-41)";
         return NORI_ERR_UNSUPPORTED;
     }
+    if (params->seed_mode == NORI_SEED_NORI_BLOCK && ctx->host.camera.lens_radius > 0.0f) {
+        ctx->error = "render: NORI_SEED_NORI_BLOCK renders the pinhole only (the mode exists for parity with the reference's sampler, and the reference has no lens); "
+                     "set the lens radius to 0 or use NORI_SEED_PER_SAMPLE";
+        return NORI_ERR_UNSUPPORTED;
+    }
     if (ctx->host.filter.border > 8) { ctx->error = "render: reconstruction filter radius too large for the LDS tile"; return NORI_ERR_UNSUPPORTED; }
-    if (features) return NORI_OK;      /* (always the fast film, whole frames or shares) */
+    if (features) return NORI_OK;     /* (always the fast film, whole frames or shares) */
     if (ctx->film_reference && params->tile_mod != 1) { ctx->error = "render: film_order = reference renders whole frames (a block's samples are added consecutively)"; return NORI_ERR_UNSUPPORTED; }
     return tiles ? check_tiles_params(ctx, params, share) : NORI_OK;
 }

@@ -17,6 +17,7 @@
 #include "rt_types.h"
 #include "rt_top.h"
 #include "rt_nodeq.h"
+#include "rt_sampling.h"      /* square_to_uniform_disk: the lens of camera_sample_ray_lens */
 
 #if defined(NORI_TRAV_HISTOGRAM) && !defined(__HIP_DEVICE_COMPILE__)
 /* CPU harness only (tools/trav_histogram.py): visits per node and per leaf pair record */
@@ -500,6 +501,26 @@ NORI_HD void camera_sample_ray(const CameraRec &cam, f2 samplePosition, RayIn &r
     ray.d = mat_vector(cam.camera_to_world, d);
     ray.mint = cam.near_clip * invZ;
     ray.maxt = cam.far_clip * invZ;
+}
+
+/* The thin lens (include/nori_hip.h, "Thin-lens camera", states it operation by operation; tests/lens_ref.py restates it in numpy).
+   The pinhole ray's point on the plane z = focus_distance stays where it is; the ray starts on the lens disk (z = 0, camera space)
+   at radius * squareToUniformDisk(apertureSample) and passes through that point.  lens_radius == 0 IS camera_sample_ray, not this
+   arithmetic with a zero in it: the branch is uniform over a launch (the record travels by value in the kernel arguments). */
+NORI_HD void camera_sample_ray_lens(const CameraRec &cam, f2 samplePosition, f2 apertureSample, RayIn &ray) {
+    if (!(cam.lens_radius > 0.0f)) { camera_sample_ray(cam, samplePosition, ray); return; }
+    f3 nearP = mat_point(cam.sample_to_camera, mk3(samplePosition.x * cam.inv_w, samplePosition.y * cam.inv_h, 0.0f));
+    f3 d = normalized(nearP);
+    float invZ = exact_rcp(d.z);
+    f3 pf = d * (cam.focus_distance * invZ);
+    f2 disk = square_to_uniform_disk(apertureSample);
+    f3 l = mk3(cam.lens_radius * disk.x, cam.lens_radius * disk.y, 0.0f);
+    f3 dl = normalized(pf - l);
+    ray.o = mat_point(cam.camera_to_world, l);
+    ray.d = mat_vector(cam.camera_to_world, dl);
+    float invZl = exact_rcp(dl.z);
+    ray.mint = cam.near_clip * invZl;
+    ray.maxt = cam.far_clip * invZl;
 }
 
 } // namespace nrt

@@ -349,6 +349,8 @@ struct CameraRec {
     float inv_w, inv_h;
     float near_clip, far_clip;
     int32_t width, height;
+    float lens_radius;            /* thin lens (camera_sample_ray_lens, rt_trace.h); 0: the pinhole.  Set by nori_hip_set_lens, */
+    float focus_distance;         /* never by a scene description: scene_prep.cpp leaves both zero */
 };
 
 struct FilterRec {

@@ -196,6 +196,7 @@ std::string prepare_scene(const nori_scene_desc &desc, HostScene &out) {
     cam.width = c.width; cam.height = c.height;
     cam.inv_w = 1.0f / (float) c.width; cam.inv_h = 1.0f / (float) c.height;
     cam.near_clip = c.near_clip; cam.far_clip = c.far_clip;
+    cam.lens_radius = 0.0f; cam.focus_distance = 0.0f;      /* the pinhole; nori_hip_set_lens sets a lens */
     std::memcpy(cam.camera_to_world, c.to_world, sizeof(float) * 16);
     {
         const float aspect = c.width / (float) c.height;

@@ -295,8 +295,8 @@ __device__ __forceinline__ bool first_vertex(const DevScene &sc, const WfBatch &
     rng_seed(rng, (uint64_t) py * (uint64_t) sc.camera.width + (uint64_t) px, (uint64_t) (bt.s_first + sl));
     const f2 j = rng_next_2d(rng);
     ps = mk2((float) px + j.x, (float) py + j.y);
-    (void) rng_next_2d(rng);          /* apertureSample: drawn, unused */
-    camera_sample_ray(sc.camera, ps, cam);
+    const f2 ap = rng_next_2d(rng);   /* apertureSample: used by a lens only */
+    camera_sample_ray_lens(sc.camera, ps, ap, cam);
     return true;
 }
 

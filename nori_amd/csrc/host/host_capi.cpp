@@ -61,6 +61,15 @@ int nori_host_scene_desc(const nori_host_root *root, nori_scene_desc *out) {
     return guarded([&] { *out = static_cast<const Scene *>(root->root.get())->getDesc(); return (int) NORI_OK; });
 }
 
+int nori_host_lens(const nori_host_root *root, float *radius, float *focus) {
+    if (!root || root->root->getClassType() != NoriObject::EScene) return NORI_ERR_INVALID_ARGUMENT;
+    const Camera *cam = static_cast<const Scene *>(root->root.get())->getCamera();
+    if (!cam) return NORI_ERR_INVALID_ARGUMENT;
+    if (radius) *radius = cam->getApertureRadius();
+    if (focus) *focus = cam->getFocusDistance();
+    return NORI_OK;
+}
+
 int nori_host_test_info_get(const nori_host_root *root, nori_host_test_info *out) {
     if (!root || !out || root->root->getClassType() != NoriObject::ETest) return NORI_ERR_INVALID_ARGUMENT;
     std::memset(out, 0, sizeof(*out));

@@ -1,5 +1,5 @@
 /*
- * main.cpp -- `nori <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]] [--denoise [--denoise-radius R] [--denoise-patch F]] [--target-denoised-error E [--pass-spp K] [--feature-spp K] [--denoise-radius R] [--denoise-patch F]] [--allocate [--pilot-spp K] [--rounds N]]`
+ * main.cpp -- `nori <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--aperture R] [--focus-distance F | --focus-pixel X Y] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]] [--denoise [--denoise-radius R] [--denoise-patch F]] [--target-denoised-error E [--pass-spp K] [--feature-spp K] [--denoise-radius R] [--denoise-patch F]] [--allocate [--pilot-spp K] [--rounds N]]`
  * Command line of the reference (src/main.cpp:150-246).  There is no GUI on a
  * compute node: --no-gui is accepted and implied; --threads is accepted for
  * compatibility (the work runs on the GPU).  --seed block renders with the
@@ -40,7 +40,7 @@ using namespace nori;
 
 int main(int argc, char **argv) {
     if (argc < 2) {
-        cerr << "Syntax: " << argv[0] << " <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]] [--denoise [--denoise-radius R] [--denoise-patch F]] [--target-denoised-error E [--pass-spp K] [--feature-spp K] [--denoise-radius R] [--denoise-patch F]] [--allocate [--pilot-spp K] [--rounds N]]" << endl;
+        cerr << "Syntax: " << argv[0] << " <scene.xml> [--no-gui] [--threads N] [--seed sample|block] [--gpus N] [--split tile|sample] [--merge reduce|gather] [--film-order fast|reference] [--aperture R] [--focus-distance F | --focus-pixel X Y] [--target-error E [--pass-spp K] [--adaptive]] [--features [--feature-spp K]] [--denoise [--denoise-radius R] [--denoise-patch F]] [--target-denoised-error E [--pass-spp K] [--feature-spp K] [--denoise-radius R] [--denoise-patch F]] [--allocate [--pilot-spp K] [--rounds N]]" << endl;
         return -1;
     }
     std::string sceneName;
@@ -54,6 +54,9 @@ int main(int argc, char **argv) {
     float targetError = 0.0f;
     long passSpp = 16;
     int gpus = 1;
+    bool haveAperture = false, haveFocusDistance = false, haveFocusPixel = false;      /* the thin lens: override the camera's apertureRadius / focusDistance */
+    float aperture = 0.0f, focusDistance = 1.0f;
+    long focusPixel[2] = {0, 0};
     for (int i = 1; i < argc; ++i) {
         std::string token(argv[i]);
         if (token == "-t" || token == "--threads") {
@@ -153,6 +156,32 @@ int main(int argc, char **argv) {
             (radius ? denoiseRadius : denoisePatch) = v;
             (radius ? haveDenoiseRadius : haveDenoisePatch) = true; ++i;
             continue;
+        } else if (token == "--aperture" || token == "--focus-distance") {
+            const bool ap = token == "--aperture";
+            char *end = nullptr;
+            float v = -1.0f;
+            if (i + 1 < argc) v = std::strtof(argv[i + 1], &end);
+            if (i + 1 >= argc || end == argv[i + 1] || *end != '\0' || !std::isfinite(v) || (ap ? !(v >= 0.0f) : !(v > 0.0f))) {
+                cerr << "Usage: \"" << token << "\" expects " << (ap ? "a lens radius >= 0 (0: the pinhole)" : "a focus distance > 0 (camera-space depth)") << " following it." << endl;
+                return -1;
+            }
+            (ap ? aperture : focusDistance) = v;
+            (ap ? haveAperture : haveFocusDistance) = true; ++i;
+            continue;
+        } else if (token == "--focus-pixel") {
+            bool ok = i + 2 < argc;
+            for (int k = 0; ok && k < 2; ++k) {
+                char *end = nullptr;
+                const long v = std::strtol(argv[i + 1 + k], &end, 10);
+                ok = end != argv[i + 1 + k] && *end == '\0' && v >= 0 && v <= 0x7fffffffl;
+                focusPixel[k] = v;
+            }
+            if (!ok) {
+                cerr << "Usage: \"--focus-pixel\" expects the pixel X Y (two integers >= 0) whose surface the lens focuses on following it." << endl;
+                return -1;
+            }
+            haveFocusPixel = true; i += 2;
+            continue;
         } else if (token == "--split" || token == "--merge" || token == "--film-order") {
             if (i + 1 >= argc) {
                 cerr << "\"" << token << "\" expects a value." << endl;
@@ -228,6 +257,10 @@ int main(int argc, char **argv) {
         cerr << "Usage: \"--features\" renders on one device: feature frames over several GPUs are not supported (got --gpus " << gpus << ")." << endl;
         return -1;
     }
+    if (haveFocusPixel && haveFocusDistance) {
+        cerr << "Usage: \"--focus-pixel\" sets the focus distance itself and does not go with --focus-distance." << endl;
+        return -1;
+    }
     if (sceneName.empty()) {
         cerr << "Please provide the path to a .xml (or .exr) file." << endl;
         return -1;
@@ -236,6 +269,33 @@ int main(int argc, char **argv) {
         std::unique_ptr<NoriObject> root(loadFromXML(sceneName));
         if (root->getClassType() == NoriObject::EScene) {
             Scene *scene = static_cast<Scene *>(root.get());
+            if (haveAperture || haveFocusDistance || haveFocusPixel) {
+                const Camera *cam = scene->getCamera();
+                float radius = haveAperture ? aperture : cam->getApertureRadius();
+                float focus = haveFocusDistance ? focusDistance : cam->getFocusDistance();
+                if (haveFocusPixel) {
+                    /* the camera-space depth of what the PINHOLE ray through the pixel's centre hits: the twins of
+                       PerspectiveCamera::sampleRay and Accel::rayIntersect, no kernel of its own */
+                    if (focusPixel[0] >= cam->getOutputSize().x() || focusPixel[1] >= cam->getOutputSize().y())
+                        throw NoriException("--focus-pixel %d %d lies outside the %d x %d frame", (int) focusPixel[0], (int) focusPixel[1], cam->getOutputSize().x(), cam->getOutputSize().y());
+                    Device &dev = scene->device();
+                    const float ps[2] = {(float) focusPixel[0] + 0.5f, (float) focusPixel[1] + 0.5f};
+                    nori_ray r; nori_intersection its;
+                    dev.check(nori_hip_sample_rays(dev.ctx(), ps, 1, &r), "nori_hip_sample_rays");
+                    dev.check(nori_hip_intersect(dev.ctx(), &r, &its, 1, 0), "nori_hip_intersect");
+                    if (its.mesh == NORI_NO_HIT)
+                        throw NoriException("--focus-pixel %d %d: the camera ray through that pixel hits nothing to focus on", (int) focusPixel[0], (int) focusPixel[1]);
+                    /* d.z in camera space: the ray's direction against the camera's axis, column 2 of cameraToWorld */
+                    const float *m = scene->getDesc().camera.to_world;
+                    const float az[3] = {m[2], m[6], m[10]};
+                    const float dz = (az[0] * r.d[0] + az[1] * r.d[1] + az[2] * r.d[2]) / (az[0] * az[0] + az[1] * az[1] + az[2] * az[2]);
+                    focus = its.t * dz;
+                    if (!std::isfinite(focus) || !(focus > 0.0f))
+                        throw NoriException("--focus-pixel %d %d: no usable depth (%f)", (int) focusPixel[0], (int) focusPixel[1], focus);
+                    cout << "Focus distance " << focus << " (pixel " << focusPixel[0] << " " << focusPixel[1] << ")" << endl;
+                }
+                scene->setLens(radius, focus);
+            }
             cout << "Rendering .. ";
             cout.flush();
             Timer timer;

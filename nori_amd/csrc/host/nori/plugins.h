@@ -136,7 +136,13 @@ public:
     virtual void fill(nori_camera_desc &d) const = 0;
     virtual void setParent(NoriObject *parent);
     EClassType getClassType() const { return ECamera; }
+    /* thin lens (include/nori_hip.h, "Thin-lens camera"): aperture radius, 0 = the pinhole, and focus distance in camera space.
+       Not part of nori_camera_desc: the scene applies them with nori_hip_set_lens after its upload (Scene::device) */
+    float getApertureRadius() const { return m_apertureRadius; }
+    float getFocusDistance() const { return m_focusDistance; }
+    void setLens(float radius, float focusDistance) { m_apertureRadius = radius; m_focusDistance = focusDistance; }
 protected:
+    float m_apertureRadius = 0.0f, m_focusDistance = 1.0f;
     Vector2i m_outputSize;
     ReconstructionFilter *m_rfilter = nullptr;
     Scene *m_scene = nullptr;
@@ -245,6 +251,8 @@ public:
     Device &device() const;
     /* the same on the first n GPUs of the node, for renders shared over them (created on first use) */
     DeviceGroup &deviceGroup(int n) const;
+    /* the camera's lens, here and on whatever context or group of this scene exists already (those made later take it from the camera) */
+    void setLens(float radius, float focusDistance);
     /* printing the scene summary on activate (src/scene.cpp:41-43) can be silenced */
     static bool s_verbose;
 private:

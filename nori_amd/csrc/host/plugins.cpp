@@ -304,6 +304,11 @@ public:
         m_fov = propList.getFloat("fov", 30.0f);
         m_nearClip = propList.getFloat("nearClip", 1e-4f);
         m_farClip = propList.getFloat("farClip", 1e4f);
+        m_apertureRadius = propList.getFloat("apertureRadius", 0.0f);
+        m_focusDistance = propList.getFloat("focusDistance", 1.0f);
+        if (!std::isfinite(m_apertureRadius) || m_apertureRadius < 0.0f) throw NoriException("PerspectiveCamera: apertureRadius must be finite and not negative");
+        if (m_apertureRadius > 0.0f && (!std::isfinite(m_focusDistance) || !(m_focusDistance > 0.0f)))
+            throw NoriException("PerspectiveCamera: a lens (apertureRadius > 0) needs a finite, positive focusDistance");
         m_rfilter = NULL;
     }
     ~PerspectiveCamera() { delete m_rfilter; }
@@ -314,7 +319,7 @@ public:
         if (!m_rfilter)
             m_rfilter = static_cast<ReconstructionFilter *>(NoriObjectFactory::createInstance("gaussian", PropertyList()));
     }
-    Color3f sampleRay(Ray3f &ray, const Point2f &samplePosition, const Point2f &) const;
+    Color3f sampleRay(Ray3f &ray, const Point2f &samplePosition, const Point2f &apertureSample) const;
     void addChild(NoriObject *obj) {
         switch (obj->getClassType()) {
         case EReconstructionFilter:
@@ -477,11 +482,12 @@ bool Accel::rayIntersect(const Ray3f &ray, Intersection &its, bool shadowRay) co
     return true;
 }
 
-Color3f PerspectiveCamera::sampleRay(Ray3f &ray, const Point2f &samplePosition, const Point2f &) const {
+Color3f PerspectiveCamera::sampleRay(Ray3f &ray, const Point2f &samplePosition, const Point2f &apertureSample) const {
     if (!m_scene) throw NoriException("PerspectiveCamera::sampleRay(): the camera is not attached to a scene");
     Device &d = m_scene->device();
     nori_ray r;
-    d.check(nori_hip_sample_rays(d.ctx(), samplePosition.v, 1, &r), "nori_hip_sample_rays");
+    /* (the context's lens is this camera's: Scene::device; without one the bits of nori_hip_sample_rays) */
+    d.check(nori_hip_sample_rays_lens(d.ctx(), samplePosition.v, apertureSample.v, 1, &r), "nori_hip_sample_rays_lens");
     ray.o = Point3f(r.o[0], r.o[1], r.o[2]); ray.d = Vector3f(r.d[0], r.d[1], r.d[2]);
     ray.mint = r.mint; ray.maxt = r.maxt; ray.update();
     return Color3f(1.0f);
@@ -583,6 +589,8 @@ Device &Scene::device() const {
         const nori_scene_desc &desc = getDesc();
         d->check(nori_hip_upload_scene(d->ctx(), &desc), "nori_hip_upload_scene");
         d->check(nori_hip_build_accel(d->ctx(), NORI_ACCEL_AUTO), "nori_hip_build_accel");
+        if (m_camera->getApertureRadius() > 0.0f)      /* (the upload leaves the pinhole) */
+            d->check(nori_hip_set_lens(d->ctx(), m_camera->getApertureRadius(), m_camera->getFocusDistance()), "nori_hip_set_lens");
         m_device = std::move(d);
     }
     return *m_device;
@@ -592,9 +600,17 @@ DeviceGroup &Scene::deviceGroup(int n) const {
         std::unique_ptr<DeviceGroup> g(new DeviceGroup(n));
         const nori_scene_desc &desc = getDesc();
         g->check(nori_hip_group_upload_scene(g->group(), &desc, NORI_ACCEL_AUTO), "nori_hip_group_upload_scene");
+        if (m_camera->getApertureRadius() > 0.0f)
+            g->check(nori_hip_group_set_lens(g->group(), m_camera->getApertureRadius(), m_camera->getFocusDistance()), "nori_hip_group_set_lens");
         m_group = std::move(g);
     }
     return *m_group;
+}
+void Scene::setLens(float radius, float focusDistance) {
+    if (!m_camera) throw NoriException("Scene::setLens(): no camera");
+    m_camera->setLens(radius, focusDistance);
+    if (m_device) m_device->check(nori_hip_set_lens(m_device->ctx(), radius, focusDistance), "nori_hip_set_lens");
+    if (m_group) m_group->check(nori_hip_group_set_lens(m_group->group(), radius, focusDistance), "nori_hip_group_set_lens");
 }
 NORI_REGISTER_CLASS(Scene, "scene");
 

@@ -32,6 +32,7 @@ HOST_PROTOTYPES = {
     "nori_host_root_type": (C.c_int, [_P]),
     "nori_host_root_string": (C.c_char_p, [_P]),
     "nori_host_scene_desc": (C.c_int, [_P, C.POINTER(capi.SceneDesc)]),
+    "nori_host_lens": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "nori_host_test_info_get": (C.c_int, [_P, C.POINTER(TestInfo)]),
     "nori_host_test_bsdf": (C.c_int, [_P, C.c_uint32, C.POINTER(capi.BsdfDesc)]),
     "nori_host_test_scene_desc": (C.c_int, [_P, C.c_uint32, C.POINTER(capi.SceneDesc)]),
@@ -150,7 +151,16 @@ class HostRoot:
         d = capi.SceneDesc()
         if self._lib.nori_host_scene_desc(self._h, C.byref(d)) != 0:
             raise NoriError("root is not a <scene>")
-        return scene_from_desc(d)
+        sc = scene_from_desc(d)
+        sc.camera.aperture_radius, sc.camera.focus_distance = self.lens()      # (not part of the description: Renderer.upload applies them)
+        return sc
+
+    def lens(self):
+        """(apertureRadius, focusDistance) of the scene's camera; radius 0 is the pinhole."""
+        r, f = C.c_float(0.0), C.c_float(0.0)
+        if self._lib.nori_host_lens(self._h, C.byref(r), C.byref(f)) != 0:
+            raise NoriError("root is not a <scene>")
+        return float(r.value), float(f.value)
 
     def test(self) -> TestFile:
         info = TestInfo()

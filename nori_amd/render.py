@@ -97,9 +97,24 @@ class Renderer:
         self._check(self._lib.nori_hip_upload_scene(self._h, C.byref(desc)), "upload_scene")
         del keep
         self.scene = scene
+        if scene.camera.aperture_radius > 0:      # (the upload itself resets the context to the pinhole)
+            self.set_lens(scene.camera.aperture_radius, scene.camera.focus_distance)
         if build:
             self.build_accel(builder)
         return self
+
+    def set_lens(self, radius: float, focus_distance: float = 1.0):
+        """The thin lens of the uploaded scene's camera (include/nori_hip.h, "Thin-lens camera"): aperture radius and focus distance
+        in camera space.  radius 0 is the pinhole, bit for bit.  Holds until the next upload."""
+        self._check(self._lib.nori_hip_set_lens(self._h, float(radius), float(focus_distance)), "set_lens")
+        return self
+
+    @property
+    def lens(self):
+        """(radius, focus_distance) as set."""
+        r, f = C.c_float(0.0), C.c_float(0.0)
+        self._check(self._lib.nori_hip_get_lens(self._h, C.byref(r), C.byref(f)), "get_lens")
+        return float(r.value), float(f.value)
 
     def build_accel(self, builder: int = 0):
         self._check(self._lib.nori_hip_build_accel(self._h, int(builder)), "build_accel")
@@ -143,6 +158,16 @@ class Renderer:
         ps = _f32(pixel_samples, 2)
         rays = np.zeros(ps.shape[0], dtype=capi.RAY_DTYPE)
         self._check(self._lib.nori_hip_sample_rays(self._h, ptr(ps), ps.shape[0], ptr(rays)), "sample_rays")
+        return rays
+
+    def sample_rays_lens(self, pixel_samples, aperture_samples) -> np.ndarray:
+        """The camera ray the render kernels take for (pixelSample, apertureSample) with the context's lens; with radius 0 the
+        bits of sample_rays."""
+        ps, ap = _f32(pixel_samples, 2), _f32(aperture_samples, 2)
+        if ps.shape[0] != ap.shape[0]:
+            raise ValueError("sample_rays_lens: one aperture sample per pixel sample")
+        rays = np.zeros(ps.shape[0], dtype=capi.RAY_DTYPE)
+        self._check(self._lib.nori_hip_sample_rays_lens(self._h, ptr(ps), ptr(ap), ps.shape[0], ptr(rays)), "sample_rays_lens")
         return rays
 
     def li(self, rays, seed_state, seed_seq) -> np.ndarray:
@@ -864,6 +889,13 @@ class DeviceGroup:
         self._check(self._lib.nori_hip_group_upload_scene(self._h, C.byref(desc), int(builder)), "group_upload_scene")
         del keep
         self.scene = scene
+        if scene.camera.aperture_radius > 0:
+            self.set_lens(scene.camera.aperture_radius, scene.camera.focus_distance)
+        return self
+
+    def set_lens(self, radius: float, focus_distance: float = 1.0):
+        """Renderer.set_lens on every device of the group."""
+        self._check(self._lib.nori_hip_group_set_lens(self._h, float(radius), float(focus_distance)), "group_set_lens")
         return self
 
     def set_option(self, key: str, value) -> None:

@@ -105,6 +105,10 @@ class Camera:
     near_clip: float = 1e-4
     far_clip: float = 1e4
     to_world: np.ndarray = field(default_factory=lambda: np.eye(4, dtype=np.float32))
+    # thin lens (include/nori_hip.h, "Thin-lens camera"): radius 0 is the pinhole.  Not part of nori_camera_desc: Renderer.upload
+    # applies them with nori_hip_set_lens
+    aperture_radius: float = 0.0
+    focus_distance: float = 1.0
 
 
 @dataclass
@@ -220,6 +224,8 @@ class Scene:
                         **({"albedo_texture": m.albedo_texture} if m.albedo_texture is not None else {})}
                        for m in self.meshes],
         }
+        if self.camera.aperture_radius > 0:      # (pinhole scenes: the file of before, key for key)
+            meta["camera"].update(aperture_radius=float(self.camera.aperture_radius), focus_distance=float(self.camera.focus_distance))
         if self.textures:
             meta["textures"] = [dict(t.params(), texels=t.texels is not None) for t in self.textures]
         if base is not None:
