@@ -1070,6 +1070,80 @@ int nori_hip_group_set_lens(nori_hip_group *group, float radius, float focus_dis
 int nori_hip_group_render_host(nori_hip_group *group, const nori_render_params *params, int split, int merge,
                                int width, int height, float *rgbw, nori_render_stats *stats, float *merge_ms);
 
+/* ------------------------------------------- Environment-map emitter
+ *
+ * No counterpart in the reference, which lights a scene with area emitters on meshes only (Scene::addChild(EEmitter) throws).
+ * An environment is a state of the context, set after the upload like the lens and reset by the next upload; no struct of the
+ * scene description grows.  Without one every kernel is the kernel it was: the path integrators have a second set of
+ * instantiations (rt_path.h, kEnvLit) that only scenes with an environment run -- "every BSDF, textures, environment", and on
+ * the wavefront engine the full path record.  path_mats, path_ems and path_mis use it; normals, ao and simple ignore it as they
+ * ignore area emitters; whitted samples emitters and has no variant: NORI_ERR_UNSUPPORTED.  NORI_SEED_NORI_BLOCK renders
+ * refuse an environment (NORI_ERR_UNSUPPORTED): the mode exists for parity with the reference's sampler.  The feature pass is
+ * unchanged: a camera ray that leaves the scene has coverage 0.
+ *
+ * The map is OCTAHEDRAL, N x N texels of linear RGB, nearest lookup.  Everything below is float32 without FMA contraction;
+ * every / is the correctly rounded quotient, every sqrt the correctly rounded root; dot(a, b) = a.x b.x + (a.y b.y + a.z b.z);
+ * sgn(x) = +1 for x >= 0 (either zero), -1 otherwise; M = to_world, row-major.
+ *
+ *   Direction -> texel.   l = (dot(column 0 of M, d), dot(column 1, d), dot(column 2, d))                  (M^T d)
+ *                         s = (|l.x| + |l.y|) + |l.z|;   q = l / s              the point of the octahedron |x|+|y|+|z| = 1
+ *                         (px, py) = (q.x, q.y);  if q.z < 0:  (px, py) = ((1 - |q.y|) sgn(q.x), (1 - |q.x|) sgn(q.y))
+ *                         u = px 0.5 + 0.5;   v = py 0.5 + 0.5
+ *                         i = min((int) (u N), N - 1);   j = min((int) (v N), N - 1)          column i of row j  (and >= 0,
+ *                                                                                             which only a direction that is not finite needs)
+ *                         Le(d) = texels[3 (j N + i) + c] scale[c]
+ *   Tables.               texel centre: u = (i + 0.5) / N, v = (j + 0.5) / N;  px = u 2 - 1, py = v 2 - 1,
+ *                         pz = (1 - |px|) - |py|;  if pz < 0 the fold above on (px, py);  c = (px, py, pz)
+ *                         lum(r, g, b) = (r 0.212671 + g 0.715160) + b 0.072169              (Color3f::getLuminance)
+ *                         weight(i, j) = lum(Le of the texel) / cube(c),   cube(x) = n sqrt(n),  n = dot(x, x)     (|x|^3)
+ *                         Row j's CDF over its columns: cdf[0] = 0, cdf[i + 1] = cdf[i] + weight(i, j) in index order; the row's
+ *                         sum is cdf[N]; if it is > 0 every entry is divided by it (a row of zeros keeps its zeros).  The CDF
+ *                         over the rows is made the same way from the row sums (DiscretePDF::append / normalize, dpdf.h).
+ *   Density.              pdf(d) = (((rows[j+1] - rows[j]) (cols_j[i+1] - cols_j[i])) ((N N) 0.25)) cube(q), with q, i, j of d:
+ *                         the probability of d's texel, over the texel's area 4 / N^2 in the square, times the Jacobian |q|^3.
+ *   Sample(xi).           j = DiscretePDF::sample(rows, xi.y), i = DiscretePDF::sample(cols_j, xi.x) (std::lower_bound: the entry
+ *                         before the first cdf >= xi, clamped to [0, N - 1]); the sample is reused inside the texel:
+ *                         t = (xi - cdf[k]) / (cdf[k+1] - cdf[k]), or 0.5 where that difference is 0 (an entry of probability
+ *                         zero, which only xi = 0 selects);  u = (i + tx) / N, v = (j + ty) / N;  px = u 2 - 1, py = v 2 - 1,
+ *                         pz = (1 - |px|) - |py|;  if pz < 0 the fold;  l = normalized(px, py, pz);  d = M l (dot of M's rows).
+ *                         The Le and pdf returned are those of "Direction -> texel" and "Density" for this d: the sampled
+ *                         path and the BSDF-sampled path agree on the density of a direction, also at texel borders.
+ *   In Li (path_mats / path_ems / path_mis).  The number of lights is n_emitters + 1 in the emitter pick (index n_emitters is
+ *                         the environment), in pdfPick = 1 / n_lights and in the MIS term of an emitter hit.  An emitter
+ *                         sample still draws four numbers (xiE, xiT, xi): the environment takes its direction from xi, leaves
+ *                         xiT unused, has pdf_em = pdf(d) pdfPick, Ld = f Le (cosX / pdf_em) and a shadow ray with
+ *                         maxt = inf; a sample of density 0 adds nothing.  A ray that leaves the scene adds T Le(d) wMat with
+ *                         the wMat an emitter hit has: 1 for path_mats; for path_ems 1 after a discrete bounce (and for the
+ *                         camera ray), else 0; for path_mis pdf_mat / (pdf_mat + pdf(d) pdfPick) after a bounce that is not
+ *                         discrete.  A scene without area emitters samples the environment alone.
+ *
+ * nori_hip_set_environment   env == NULL: no environment (the kernels and bits of before).  Else the map is copied, its tables
+ *                            are built on the device (three kernels, no atomics: the same map gives the same tables) and it is
+ *                            used from the next launch on.  Synchronous.  NORI_ERR_NOT_READY before an upload;
+ *                            NORI_ERR_UNSUPPORTED for the whitted integrator; NORI_ERR_INVALID_ARGUMENT, with a message, for
+ *                            size 0 or above 4096, NULL texels, a texel or scale that is negative or not finite, a map whose
+ *                            scaled luminance is 0 everywhere, a to_world whose rows are not orthonormal within 1e-4.  A failed
+ *                            call leaves the context's environment as it was.
+ * nori_hip_get_environment   the size N of the environment set, 0: none.
+ * nori_hip_env_eval          Le (rgb: 3n) and, unless pdf is NULL, the density (n) of n world directions (dirs: 3n, unit length).
+ * nori_hip_env_sample        Sample for n pairs xi (2n): directions (3n), Le (3n), densities (n).
+ * nori_hip_debug_env_tables  the tables as the device holds them: row_cdf N + 1, col_cdf N (N + 1) row after row,
+ *                            texel_weight N N; any pointer may be NULL.
+ * The last three return NORI_ERR_NOT_READY, with a message, while no environment is set. */
+typedef struct nori_env_desc {
+    uint32_t size;         /* N: the map is N x N texels, 1 .. 4096 */
+    const float *texels;   /* 3*N*N floats, linear RGB, row-major, octahedral layout (above); finite, >= 0 */
+    float scale[3];        /* multiplies every texel */
+    float to_world[9];     /* row-major rotation: world = M * local */
+} nori_env_desc;
+int nori_hip_set_environment(nori_hip_ctx *ctx, const nori_env_desc *env);
+int nori_hip_get_environment(const nori_hip_ctx *ctx, uint32_t *size);
+int nori_hip_env_eval(nori_hip_ctx *ctx, const float *dirs, size_t n, float *rgb, float *pdf);
+int nori_hip_env_sample(nori_hip_ctx *ctx, const float *xi, size_t n, float *dirs, float *rgb, float *pdf);
+int nori_hip_debug_env_tables(nori_hip_ctx *ctx, float *row_cdf, float *col_cdf, float *texel_weight);
+/* nori_hip_set_environment on every device's context (the upload resets it, as on one context) */
+int nori_hip_group_set_environment(nori_hip_group *group, const nori_env_desc *env);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,10 @@ int nori_host_scene_desc(const nori_host_root *root, nori_scene_desc *out);
  * the <camera>'s property list).  Not part of nori_scene_desc: apply it with nori_hip_set_lens after the upload, as
  * nori_host_render does.  Either pointer may be NULL. */
 int nori_host_lens(const nori_host_root *root, float *radius, float *focus);
+/* Root is a <scene>: its environment map (<emitter type="envmap">), resampled to the octahedral layout nori_hip_set_environment
+ * takes; the texels are borrowed (valid until free).  Returns 1 and fills *out if the scene has one, 0 if it has none (out->size = 0),
+ * or a negative nori_status.  Not part of nori_scene_desc: apply it after the upload. */
+int nori_host_environment(const nori_host_root *root, nori_env_desc *out);
 
 /* Root is a <test>: kind 0 = ttest, 1 = chi2test. */
 typedef struct nori_host_test_info {

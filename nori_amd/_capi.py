@@ -158,6 +158,11 @@ ALLOC_MAX_LEVEL = 7                                             # J <= 7: eight 
 ALLOC_MAX_BUCKETS = ALLOC_MAX_LEVEL * (ALLOC_MAX_LEVEL + 1) // 2      # 28 pairs (i, j), i < j; bucket_begin has 29 words
 
 
+class EnvDesc(C.Structure):
+    """nori_env_desc"""
+    _fields_ = [("size", C.c_uint32), ("texels", C.c_void_p), ("scale", C.c_float * 3), ("to_world", C.c_float * 9)]
+
+
 class AccelInfo(C.Structure):
     _fields_ = [("n_triangles", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("max_depth", C.c_uint32), ("node_bytes", C.c_uint32), ("tri_bytes", C.c_uint32),
@@ -273,6 +278,12 @@ HIP_PROTOTYPES = {
     "nori_hip_group_upload_scene": (C.c_int, [_P, C.POINTER(SceneDesc), C.c_int]),
     "nori_hip_group_set_lens": (C.c_int, [_P, C.c_float, C.c_float]),
     "nori_hip_group_render_host": (C.c_int, [_P, C.POINTER(RenderParams), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.POINTER(RenderStats), C.POINTER(C.c_float)]),
+    "nori_hip_set_environment": (C.c_int, [_P, C.POINTER(EnvDesc)]),
+    "nori_hip_get_environment": (C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    "nori_hip_env_eval": (C.c_int, [_P, _P, C.c_size_t, _P, _P]),
+    "nori_hip_env_sample": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P]),
+    "nori_hip_debug_env_tables": (C.c_int, [_P, _P, _P, _P]),
+    "nori_hip_group_set_environment": (C.c_int, [_P, C.POINTER(EnvDesc)]),
 }
 
 

@@ -1,4 +1,4 @@
-/* ctx.h -- the context behind the C ABI and what the entry points of nori_hip.hip and frame_api.hip (those two units only) need
+/* ctx.h -- the context behind the C ABI and what the entry points of nori_hip.hip, frame_api.hip and env_map.hip (those units only) need
  * of it: the error mapping, the device guard, scratch buffers, the frame's sizes, the stats of a call. */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,6 +28,9 @@ struct nori_hip_ctx {
     HostBvh bvh;
     DevScene dev;
     std::vector<void *> allocs_scene, allocs_accel;
+    std::vector<void *> allocs_env;      /* the environment map (env_map.hip): texels, tables, the record DevScene::env points at */
+    uint32_t env_size = 0;               /* its N; 0 while dev.env is null */
+    const float *d_env_weight = nullptr; /* its texel weights (nori_hip_debug_env_tables; the path reads the CDFs only) */
     float *d_filter = nullptr;
     const uint32_t *d_tri_mesh = nullptr;
     unsigned long long *d_stats = nullptr;
@@ -140,6 +143,9 @@ static inline FilmLaunch film_launch_for(uint32_t tiles_x, uint32_t tiles_y, uin
 /* environment hooks of the launches shaped like the megakernel's: workgroups to aim for (plan_chunks), the film store's budget in samples (spp_per_launch) */
 static inline uint32_t env_target_wgs() { const char *e = getenv("NORI_HIP_TARGET_WGS"); return e ? (uint32_t) std::max(1, atoi(e)) : 16384u; }
 static inline size_t env_film_samples() { const char *e = getenv("NORI_HIP_FILM_SAMPLES"); return e ? (size_t) std::max(256ll, atoll(e)) : (size_t) 1 << 29; }
+
+/* env_map.hip: frees the context's environment map and clears DevScene::env (an upload, nori_hip_destroy, a new map) */
+void env_release(nori_hip_ctx *ctx);
 
 /* nori_hip.hip.  What a render refuses of its parameters, in order (features: the pass of nori_hip_render_features, which shares three of the
    refusals and has one of its own among them), and of them what a render by tile list refuses.  render_impl: every render -- share: the block rows of a

@@ -76,7 +76,8 @@ struct RenderArgs {
     const uint32_t *tile_list = nullptr;    /* a render by list (film_tiles.h): selected-tile ordinal -> tile, DEVICE memory; null: the progression */
 };
 
-/* MATSET = kAnyBsdf | kTextured (rt_path.h): the kernel of scenes with textured albedos; kAnyBsdf: every other scene */
+/* MATSET = kAnyBsdf | kTextured (rt_path.h): the kernel of scenes with textured albedos; kAnyBsdf | kTextured | kEnvLit: of scenes
+   with an environment map (path_mats / path_ems / path_mis; textured or not); kAnyBsdf: every other scene */
 template <int INTEG, int STACK, bool COUNT, int MATSET = kAnyBsdf>
 __global__ __launch_bounds__(kBlock, NORI_RENDER_MIN_WAVES) void render_kernel(DevScene sc, RenderArgs args, FilmStore film,
                                                         unsigned long long *stats) {
@@ -549,6 +550,7 @@ void nori_hip_destroy(nori_hip_ctx *ctx) {
     if (!ctx) return;
     DeviceGuard g(ctx->device);
     free_pool(ctx->allocs_scene); free_pool(ctx->allocs_accel);
+    env_release(ctx);
     wavefront_destroy(ctx->wf);
     film_release(ctx->film);
     film_moments_release(ctx->moments);
@@ -569,6 +571,7 @@ int nori_hip_upload_scene(nori_hip_ctx *ctx, const nori_scene_desc *scene) {
     if (!ctx || !scene) return NORI_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
     free_pool(ctx->allocs_scene); free_pool(ctx->allocs_accel);
+    env_release(ctx);      /* the environment map is set after an upload and lasts until the next (nori_hip_set_environment) */
     ctx->have_scene = ctx->have_accel = false;
     std::string err = prepare_scene(*scene, ctx->host);
     if (!err.empty()) { ctx->error = err; return NORI_ERR_INVALID_ARGUMENT; }
@@ -895,7 +898,11 @@ static void launch_li(nori_hip_ctx *ctx, const nori_ray *r, size_t n, const uint
 #define LI_CASE(I) case I: hipLaunchKernelGGL((li_kernel<I, STACK>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); break;
 #define LI_TEX(I) case I: if (ctx->dev.textured) { hipLaunchKernelGGL((li_kernel<I, STACK, kAnyBsdf | kTextured>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } \
                           else { hipLaunchKernelGGL((li_kernel<I, STACK>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } break;
-        LI_CASE(0) LI_CASE(1) LI_CASE(2) LI_TEX(3) LI_TEX(4) LI_TEX(5) LI_TEX(6)
+#define LI_ENV(I) case I: if (ctx->dev.env) { hipLaunchKernelGGL((li_kernel<I, STACK, kAnyBsdf | kTextured | kEnvLit>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } \
+                          else if (ctx->dev.textured) { hipLaunchKernelGGL((li_kernel<I, STACK, kAnyBsdf | kTextured>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } \
+                          else { hipLaunchKernelGGL((li_kernel<I, STACK>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } break;
+        LI_CASE(0) LI_CASE(1) LI_CASE(2) LI_TEX(3) LI_ENV(4) LI_ENV(5) LI_ENV(6)
+#undef LI_ENV
 #undef LI_TEX
 #undef LI_CASE
     }
@@ -1174,6 +1181,10 @@ static hipError_t launch_render_one(nori_hip_ctx *ctx, const RenderArgs &a, cons
     if constexpr (INTEG >= INT_WHITTED) {
         if (ctx->dev.textured) kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured>;
     }
+    /* the path integrators have one for scenes with an environment map: every BSDF, textures, environment (kEnvLit) */
+    if constexpr (INTEG >= INT_MATS) {
+        if (ctx->dev.env) kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured | kEnvLit>;
+    }
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         if (e != hipSuccess) return e;
@@ -1231,6 +1242,11 @@ int check_render_params(nori_hip_ctx *ctx, const nori_render_params *params, con
     if (params->seed_mode == NORI_SEED_NORI_BLOCK && ctx->host.camera.lens_radius > 0.0f) {
         ctx->error = "render: NORI_SEED_NORI_BLOCK renders the pinhole only (the mode exists for parity with the reference's sampler, and the reference has no lens); "
                      "set the lens radius to 0 or use NORI_SEED_PER_SAMPLE";
+        return NORI_ERR_UNSUPPORTED;
+    }
+    if (params->seed_mode == NORI_SEED_NORI_BLOCK && ctx->dev.env) {
+        ctx->error = "render: NORI_SEED_NORI_BLOCK renders no environment map (the mode exists for parity with the reference's sampler, and the reference has no "
+                     "environment emitter); unset it (nori_hip_set_environment with NULL) or use NORI_SEED_PER_SAMPLE";
         return NORI_ERR_UNSUPPORTED;
     }
     if (ctx->host.filter.border > 8) { ctx->error = "render: reconstruction filter radius too large for the LDS tile"; return NORI_ERR_UNSUPPORTED; }

@@ -18,6 +18,7 @@
 #pragma once
 #include "rt_sampling.h"
 #include "rt_texture.h"
+#include "env_map.h"
 #include "rt_trace.h"
 
 namespace nrt {
@@ -93,8 +94,18 @@ NORI_HD uint32_t emitter_pick(const Tab &tab, uint32_t nE, float xiE, float xiT,
     return mi;
 }
 
+/* MATSET bits beyond the BSDF types (path_on_closest below says what a MATSET is).
+   kTextured (bit 4): the kernel reads the albedo of a textured diffuse mesh from its texture (rt_texture.h) at the hit's uv;
+   without the bit no texture code is compiled -- the kernels of scenes without textures are the kernels of before.
+   kEnvLit (bit 5): the scene has an environment map (env_map.h; DevScene::env is not null).  It is one more light in the emitter
+   pick -- index n_emitters --, and a ray that leaves the scene collects it.  Without the bit none of that is compiled: the
+   kernels of scenes without an environment are the kernels of before.  path_mats / path_ems / path_mis only. */
+constexpr int kAnyBsdf = 0xf;
+constexpr int kTextured = 0x10;
+constexpr int kEnvLit = 0x20;
+
 struct NeeResult {
-    f3 Ld;          /* f * Le * cosX * cosY / (dist^2 * pdfA) */
+    f3 Ld;          /* f * Le * cosX * cosY / (dist^2 * pdfA); the environment: f * Le * cosX / pdf_em */
     f3 dir;
     float maxt;
     float pdf_em, pdf_bsdf;
@@ -103,14 +114,32 @@ struct NeeResult {
 /* Emitter sampling at surface `s`: uniform emitter, triangle by area, uniform
  * barycentrics (alpha = 1 - sqrt(1 - xi1), beta = xi2 sqrt(1 - xi1)).
  * Always consumes 4 random numbers.  Returns true if a shadow ray is needed. */
-template <class Tab>
+template <class Tab, int MATSET = kAnyBsdf>
 NORI_HD bool sample_direct(const DevScene &sc, const Tab &tab, Rng &rng, const Surface &s, const Frame &fr,
                            const Bsdf &bsdf, f3 wi, NeeResult &out) {
     const float xiE = rng_next_float(rng);
     const float xiT = rng_next_float(rng);
     const f2 xi = rng_next_2d(rng);
-    const uint32_t nE = sc.n_emitters;
+    const uint32_t nE = (MATSET & kEnvLit) ? sc.n_emitters + 1u : sc.n_emitters;      /* the lights: the environment is the last */
     if (nE == 0) return false;
+    if (MATSET & kEnvLit) {
+        uint32_t ei = (uint32_t) (xiE * (float) nE);      /* emitter_pick's index */
+        if (ei > nE - 1) ei = nE - 1;
+        if (ei == sc.n_emitters) {      /* the environment: a direction from xi, xiT unused */
+            f3 dir, le; float pdfW;
+            env_sample(*sc.env, xi, dir, le, pdfW);
+            if (!(pdfW > 0.0f)) return false;
+            const f3 wo = to_local(fr, dir);
+            const f3 f = bsdf_eval(bsdf, wi, wo);
+            if (is_zero(f)) return false;
+            out.pdf_em = pdfW * exact_rcp((float) nE);      /* pdfPick */
+            out.pdf_bsdf = bsdf_pdf(bsdf, wi, wo);
+            out.Ld = f * le * exact_div(wo.z, out.pdf_em);
+            out.dir = dir;
+            out.maxt = kInf;
+            return true;
+        }
+    }
     MeshRec m; uint32_t tri;
     (void) emitter_pick(tab, nE, xiE, xiT, m, tri);
     const float pdfPick = exact_rcp((float) nE);
@@ -153,11 +182,7 @@ NORI_HD void surface_from_record(bool has_normals, float u, float v, f3 p0, f3 p
 
 /* MATSET: the BSDF types the scene contains, bit t = nori_bsdf_type t (DevScene::bsdf_mask).  A kernel instantiated for a
    subset never compiles the other BSDFs' sample / eval / pdf (include/nori/bsdf.h:59-87): wf_shade of an all-diffuse scene
-   (src/diffuse.cpp:23-71) is a smaller kernel with more waves per SIMD.  kAnyBsdf: every type.
-   kTextured (bit 4): the kernel reads the albedo of a textured diffuse mesh from its texture (rt_texture.h) at the hit's uv;
-   without the bit no texture code is compiled -- the kernels of scenes without textures are the kernels of before. */
-constexpr int kAnyBsdf = 0xf;
-constexpr int kTextured = 0x10;
+   (src/diffuse.cpp:23-71) is a smaller kernel with more waves per SIMD.  kAnyBsdf: every type.  kTextured, kEnvLit: above. */
 template <int MATSET> NORI_HD int32_t bsdf_type_in_set(int32_t type) {
     if (MATSET == 1) return 0;                                      /* diffuse only: a constant */
     if (MATSET == 8) return 3;
@@ -167,7 +192,21 @@ template <int MATSET> NORI_HD int32_t bsdf_type_in_set(int32_t type) {
 }
 template <int INTEG, class Tab, int MATSET = kAnyBsdf>
 NORI_HD bool path_on_closest(const DevScene &sc, const Tab &tab, PathState &st, const Hit &hit, bool found, const f3 d) {
-    if (!found) return true;
+    if (!found) {
+        if ((MATSET & kEnvLit) && INTEG >= INT_MATS) {      /* the ray left the scene: the environment, weighted as an emitter hit is below */
+            const bool weighted = INTEG != INT_MATS && st.prev_measure != 2;
+            if (!(weighted && INTEG == INT_EMS)) {      /* (path_ems counts it at the vertex before: weight 0) */
+                float pdfW = 0.0f, wEnv = 1.0f;
+                const f3 le = env_eval(*sc.env, d, weighted ? &pdfW : nullptr);
+                if (weighted) {
+                    const float pdfEm = pdfW * exact_rcp((float) (sc.n_emitters + 1u));
+                    wEnv = (st.pdf_mat + pdfEm) > 0.0f ? exact_div(st.pdf_mat, st.pdf_mat + pdfEm) : 0.0f;
+                }
+                if (wEnv > 0.0f) st.L = st.L + st.T * le * wEnv;
+            }
+        }
+        return true;
+    }
     const MeshRec m = tab.mesh(hit.mesh);
     Surface sf;
     {
@@ -245,7 +284,7 @@ NORI_HD bool path_on_closest(const DevScene &sc, const Tab &tab, PathState &st, 
             float pdfEm = 0.0f;
             const float cosY = dot(sf.ns, -d);
             if (cosY > 0.0f) {
-                const float pdfA = exact_div(m.inv_area, (float) sc.n_emitters);
+                const float pdfA = exact_div(m.inv_area, (float) ((MATSET & kEnvLit) ? sc.n_emitters + 1u : sc.n_emitters));
                 pdfEm = exact_div(pdfA * hit.t * hit.t, cosY);
             }
             wMat = (st.pdf_mat + pdfEm) > 0.0f ? exact_div(st.pdf_mat, st.pdf_mat + pdfEm) : 0.0f;
@@ -263,7 +302,7 @@ NORI_HD bool path_on_closest(const DevScene &sc, const Tab &tab, PathState &st, 
     bool needShadow = false;
     NeeResult nee;
     if (EMS && bsdf_is_diffuse(bsdf.type)) {
-        needShadow = sample_direct(sc, tab, st.rng, sf, fr, bsdf, wi, nee);
+        needShadow = sample_direct<Tab, MATSET>(sc, tab, st.rng, sf, fr, bsdf, wi, nee);
         if (needShadow) {
             float w = 1.0f;
             if (MIS) w = (nee.pdf_em + nee.pdf_bsdf) > 0.0f ? exact_div(nee.pdf_em, nee.pdf_em + nee.pdf_bsdf) : 0.0f;

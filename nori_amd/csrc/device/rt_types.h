@@ -342,6 +342,7 @@ constexpr uint32_t kMeshHasNormals = 1u, kMeshHasUV = 2u, kMeshEmitter = 4u, kMe
 static_assert(sizeof(MeshRec) == 80, "the LDS shade tables (shade_tables.h) hold 80-B mesh records");
 
 struct TexRec;
+struct EnvRec;
 
 struct CameraRec {
     float sample_to_camera[16];   /* row-major */
@@ -402,6 +403,9 @@ struct DevScene {
     const f4 *texels;
     uint32_t n_textures;
     uint32_t textured;          /* some mesh has a textured albedo: the kernels compiled with kTextured run (rt_path.h) */
+    /* the environment map (env_map.h), set by nori_hip_set_environment, never by a scene description; null: none -- and then the
+       kernels compiled without kEnvLit run (rt_path.h), which never read it */
+    const EnvRec *env;
 };
 
 struct Hit {

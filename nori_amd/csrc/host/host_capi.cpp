@@ -70,6 +70,15 @@ int nori_host_lens(const nori_host_root *root, float *radius, float *focus) {
     return NORI_OK;
 }
 
+int nori_host_environment(const nori_host_root *root, nori_env_desc *out) {
+    if (!root || !out || root->root->getClassType() != NoriObject::EScene) return NORI_ERR_INVALID_ARGUMENT;
+    std::memset(out, 0, sizeof(*out));
+    const Emitter *env = static_cast<const Scene *>(root->root.get())->getEnvironment();
+    if (!env) return 0;
+    env->fillEnvironment(*out);
+    return 1;
+}
+
 int nori_host_test_info_get(const nori_host_root *root, nori_host_test_info *out) {
     if (!root || !out || root->root->getClassType() != NoriObject::ETest) return NORI_ERR_INVALID_ARGUMENT;
     std::memset(out, 0, sizeof(*out));

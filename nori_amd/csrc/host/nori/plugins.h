@@ -91,6 +91,10 @@ class Emitter : public NoriObject {
 public:
     EClassType getClassType() const { return EEmitter; }
     virtual Color3f getRadiance() const = 0;
+    /* an environment map (<emitter type="envmap">, a child of the <scene>): the record nori_hip_set_environment takes; the emitter
+       owns the texels.  Area lights are not one. */
+    virtual bool isEnvironment() const { return false; }
+    virtual void fillEnvironment(nori_env_desc &) const {}
 };
 
 /* ---------------------------------------------------------------- Sampler */
@@ -234,6 +238,7 @@ public:
     const Integrator *getIntegrator() const { return m_integrator; }
     Integrator *getIntegrator() { return m_integrator; }
     const Camera *getCamera() const { return m_camera; }
+    const Emitter *getEnvironment() const { return m_environment; }
     const Sampler *getSampler() const { return m_sampler; }
     Sampler *getSampler() { return m_sampler; }
     const std::vector<Mesh *> &getMeshes() const { return m_meshes; }
@@ -260,6 +265,7 @@ private:
     Integrator *m_integrator = nullptr;
     Sampler *m_sampler = nullptr;
     Camera *m_camera = nullptr;
+    Emitter *m_environment = nullptr;      /* the environment map, if any: applied after every upload (device(), deviceGroup()) */
     Accel *m_accel = nullptr;
     mutable nori_scene_desc m_desc;
     mutable std::vector<nori_mesh_desc> m_meshDescs;

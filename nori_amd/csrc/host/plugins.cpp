@@ -15,8 +15,12 @@
  * CPU: the virtuals forward to libnori_hip.
  */
 #include <nori/plugins.h>
+#include <nori/bitmap.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <fstream>
 
 NORI_NAMESPACE_BEGIN
 
@@ -181,6 +185,94 @@ private:
     Color3f m_radiance;
 };
 NORI_REGISTER_CLASS(AreaLight, "area");
+
+/* <emitter type="envmap"> as a child of <scene>: image-based lighting (include/nori_hip.h, "Environment-map emitter").
+ *   filename    a latitude-longitude OpenEXR image, y up: a local direction (x, y, z) is looked up at phi = atan2(x, -z) across
+ *               (the image's middle column looks down -z), theta = acos(y) down (row 0 is +y)
+ *   scale       colour, multiplies the map (default 1)
+ *   resolution  N of the octahedral map the device samples (default 512, 1 .. 4096)
+ *   toWorld     its rotation part turns the map (world = M local); anything else in it is ignored
+ * The device's map is octahedral, so the image is resampled here, once: at the centre of each of the N x N texels the direction is
+ * taken back to (phi, theta) and the image is read bilinearly (wrapping across, clamped at the poles), in double precision with
+ * the host's libm.  This is a choice of texel values, outside the path the parity claims cover: what the device does with the
+ * texels it is given is what the header pins. */
+class EnvironmentMap : public Emitter {
+public:
+    EnvironmentMap(const PropertyList &propList) {
+        m_filename = getFileResolver()->resolve(propList.getString("filename"));
+        if (m_filename.size() < 4 || toLower(m_filename.substr(m_filename.size() - 4)) != ".exr") throw NoriException("envmap: unsupported image \"%s\" (a latitude-longitude OpenEXR file)", m_filename);
+        m_scale = propList.getColor("scale", Color3f(1.0f));
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(m_scale[c]) || m_scale[c] < 0.0f) throw NoriException("envmap: scale must be finite and not negative");
+        const int res = propList.getInteger("resolution", 512);
+        if (res < 1 || res > 4096) throw NoriException("envmap: resolution must be 1 .. 4096 (got %d)", res);
+        m_size = (uint32_t) res;
+        const Transform t = propList.getTransform("toWorld", Transform());
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) m_toWorld[3 * r + c] = t.m[4 * r + c];
+        for (int a = 0; a < 3; ++a)
+            for (int b = a; b < 3; ++b) {
+                double d = 0.0;
+                for (int k = 0; k < 3; ++k) d += (double) m_toWorld[3 * a + k] * m_toWorld[3 * b + k];
+                if (!(std::fabs(d - (a == b ? 1.0 : 0.0)) <= 1e-4)) throw NoriException("envmap: toWorld must be a rotation (its upper 3 x 3 rows are not orthonormal)");
+            }
+        {
+            std::ifstream probe(m_filename, std::ios::binary);
+            if (probe.fail()) throw NoriException("cannot read image \"%s\"", m_filename);
+        }
+        Bitmap img(m_filename);
+        if (img.cols() <= 0 || img.rows() <= 0) throw NoriException("\"%s\": empty image", m_filename);
+        resample(img);
+    }
+    Color3f getRadiance() const { return Color3f(0.0f); }
+    bool isEnvironment() const { return true; }
+    void fillEnvironment(nori_env_desc &d) const {
+        std::memset(&d, 0, sizeof(d));
+        d.size = m_size; d.texels = m_texels.data();
+        for (int c = 0; c < 3; ++c) d.scale[c] = m_scale[c];
+        for (int k = 0; k < 9; ++k) d.to_world[k] = m_toWorld[k];
+    }
+    std::string toString() const { return format("EnvironmentMap[\n  filename = \"%s\",\n  resolution = %u,\n  scale = %s\n]", m_filename, m_size, m_scale.toString()); }
+private:
+    void resample(const Bitmap &img) {
+        const int W = img.cols(), H = img.rows(), N = (int) m_size;
+        m_texels.resize((size_t) N * N * 3);
+        double sum = 0.0;
+        for (int j = 0; j < N; ++j)
+            for (int i = 0; i < N; ++i) {
+                /* the texel centre's direction: the inverse of the header's "Direction -> texel" */
+                double px = 2.0 * ((i + 0.5) / N) - 1.0, py = 2.0 * ((j + 0.5) / N) - 1.0;
+                const double pz = 1.0 - std::fabs(px) - std::fabs(py);
+                if (pz < 0.0) {
+                    const double ox = px, oy = py;
+                    px = (1.0 - std::fabs(oy)) * (ox >= 0.0 ? 1.0 : -1.0);
+                    py = (1.0 - std::fabs(ox)) * (oy >= 0.0 ? 1.0 : -1.0);
+                }
+                const double len = std::sqrt(px * px + py * py + pz * pz);
+                const double x = px / len, y = py / len, z = pz / len;
+                const double phi = std::atan2(x, -z), theta = std::acos(std::min(1.0, std::max(-1.0, y)));
+                const double fx = (phi / (2.0 * M_PI) + 0.5) * W - 0.5, fy = theta / M_PI * H - 0.5;
+                const double x0 = std::floor(fx), y0 = std::floor(fy), ax = fx - x0, ay = fy - y0;
+                auto col = [W](int c) { c %= W; return c < 0 ? c + W : c; };
+                auto row = [H](int r) { return r < 0 ? 0 : (r > H - 1 ? H - 1 : r); };
+                const int c0 = col((int) x0), c1 = col((int) x0 + 1), r0 = row((int) y0), r1 = row((int) y0 + 1);
+                for (int c = 0; c < 3; ++c) {
+                    const double top = (1.0 - ax) * img.coeff(r0, c0)[c] + ax * img.coeff(r0, c1)[c];
+                    const double bot = (1.0 - ax) * img.coeff(r1, c0)[c] + ax * img.coeff(r1, c1)[c];
+                    const float v = (float) ((1.0 - ay) * top + ay * bot);
+                    if (!std::isfinite(v) || v < 0.0f) throw NoriException("\"%s\": a pixel is negative or not finite", m_filename);
+                    m_texels[((size_t) j * N + i) * 3 + c] = v;
+                    sum += (double) v * m_scale[c];
+                }
+            }
+        if (!(sum > 0.0)) throw NoriException("envmap: \"%s\" times scale is black everywhere (nothing to light the scene with)", m_filename);
+    }
+    std::string m_filename;
+    Color3f m_scale;
+    uint32_t m_size = 0;
+    float m_toWorld[9];
+    std::vector<float> m_texels;
+};
+NORI_REGISTER_CLASS(EnvironmentMap, "envmap");
 
 /* ================================================================ Sampler */
 /* src/independent.cpp:21-67.  The pcg32 arithmetic runs on the device
@@ -499,7 +591,7 @@ bool Scene::s_verbose = true;
 Scene::Scene(const PropertyList &) { m_accel = new Accel(this); std::memset(&m_desc, 0, sizeof(m_desc)); }
 
 Scene::~Scene() {
-    delete m_accel; delete m_sampler; delete m_camera; delete m_integrator;
+    delete m_accel; delete m_sampler; delete m_camera; delete m_integrator; delete m_environment;
     for (Mesh *m : m_meshes) delete m;       /* the reference leaks these (src/scene.cpp:20-25) */
 }
 
@@ -507,6 +599,12 @@ void Scene::activate() {
     m_accel->build();
     if (!m_integrator) throw NoriException("No integrator was specified!");
     if (!m_camera) throw NoriException("No camera was specified!");
+    if (m_environment) {      /* what nori_hip_set_environment would refuse, said before a device is asked for */
+        nori_integrator_desc id;
+        m_integrator->fill(id);
+        if (id.type == NORI_INTEGRATOR_WHITTED)
+            throw NoriException("An environment map cannot be rendered by the whitted integrator (use path_mats, path_ems or path_mis)");
+    }
     if (!m_sampler)
         m_sampler = static_cast<Sampler *>(NoriObjectFactory::createInstance("independent", PropertyList()));
     if (s_verbose) {
@@ -524,8 +622,13 @@ void Scene::addChild(NoriObject *obj) {
         m_meshes.push_back(mesh);
     } break;
     case EEmitter:
-        /* src/scene.cpp:55-59 throws here too: emitters are attached to meshes */
-        throw NoriException("Scene::addChild(): emitters must be children of a <mesh> (area lights)");
+        /* src/scene.cpp:55-59 throws here: the reference attaches emitters to meshes.  An environment map is the one emitter
+           that belongs to the scene (a departure: INTEGRATION.md) */
+        if (!static_cast<Emitter *>(obj)->isEnvironment())
+            throw NoriException("Scene::addChild(): emitters must be children of a <mesh> (area lights); only <emitter type=\"envmap\"> belongs to the scene");
+        if (m_environment) throw NoriException("There can only be one environment map per scene!");
+        m_environment = static_cast<Emitter *>(obj);
+        break;
     case ESampler:
         if (m_sampler) throw NoriException("There can only be one sampler per scene!");
         m_sampler = static_cast<Sampler *>(obj);
@@ -591,6 +694,11 @@ Device &Scene::device() const {
         d->check(nori_hip_build_accel(d->ctx(), NORI_ACCEL_AUTO), "nori_hip_build_accel");
         if (m_camera->getApertureRadius() > 0.0f)      /* (the upload leaves the pinhole) */
             d->check(nori_hip_set_lens(d->ctx(), m_camera->getApertureRadius(), m_camera->getFocusDistance()), "nori_hip_set_lens");
+        if (m_environment) {      /* (nor an environment) */
+            nori_env_desc env;
+            m_environment->fillEnvironment(env);
+            d->check(nori_hip_set_environment(d->ctx(), &env), "nori_hip_set_environment");
+        }
         m_device = std::move(d);
     }
     return *m_device;
@@ -602,6 +710,11 @@ DeviceGroup &Scene::deviceGroup(int n) const {
         g->check(nori_hip_group_upload_scene(g->group(), &desc, NORI_ACCEL_AUTO), "nori_hip_group_upload_scene");
         if (m_camera->getApertureRadius() > 0.0f)
             g->check(nori_hip_group_set_lens(g->group(), m_camera->getApertureRadius(), m_camera->getFocusDistance()), "nori_hip_group_set_lens");
+        if (m_environment) {
+            nori_env_desc env;
+            m_environment->fillEnvironment(env);
+            g->check(nori_hip_group_set_environment(g->group(), &env), "nori_hip_group_set_environment");
+        }
         m_group = std::move(g);
     }
     return *m_group;

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _capi as capi
 from ._capi import NoriError
-from .scene import Bsdf, Camera, Integrator, Mesh, RFilter, Scene, Texture
+from .scene import Bsdf, Camera, Environment, Integrator, Mesh, RFilter, Scene, Texture
 
 DEFER_TESTS, QUIET = 1, 2
 _P = C.c_void_p
@@ -33,6 +33,7 @@ HOST_PROTOTYPES = {
     "nori_host_root_string": (C.c_char_p, [_P]),
     "nori_host_scene_desc": (C.c_int, [_P, C.POINTER(capi.SceneDesc)]),
     "nori_host_lens": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "nori_host_environment": (C.c_int, [_P, C.POINTER(capi.EnvDesc)]),
     "nori_host_test_info_get": (C.c_int, [_P, C.POINTER(TestInfo)]),
     "nori_host_test_bsdf": (C.c_int, [_P, C.c_uint32, C.POINTER(capi.BsdfDesc)]),
     "nori_host_test_scene_desc": (C.c_int, [_P, C.c_uint32, C.POINTER(capi.SceneDesc)]),
@@ -153,7 +154,20 @@ class HostRoot:
             raise NoriError("root is not a <scene>")
         sc = scene_from_desc(d)
         sc.camera.aperture_radius, sc.camera.focus_distance = self.lens()      # (not part of the description: Renderer.upload applies them)
+        sc.environment = self.environment()                                    # (nor is this)
         return sc
+
+    def environment(self):
+        """The scene's environment map (<emitter type="envmap">) as a scene.Environment, the texels copied; None without one."""
+        d = capi.EnvDesc()
+        rc = self._lib.nori_host_environment(self._h, C.byref(d))
+        if rc < 0:
+            raise NoriError("root is not a <scene>")
+        if rc == 0:
+            return None
+        n = int(d.size)
+        texels = np.ctypeslib.as_array(C.cast(d.texels, C.POINTER(C.c_float)), shape=(n, n, 3)).copy()
+        return Environment(texels, tuple(float(x) for x in d.scale), np.array(list(d.to_world), np.float32).reshape(3, 3))
 
     def lens(self):
         """(apertureRadius, focusDistance) of the scene's camera; radius 0 is the pinhole."""

@@ -99,9 +99,52 @@ class Renderer:
         self.scene = scene
         if scene.camera.aperture_radius > 0:      # (the upload itself resets the context to the pinhole)
             self.set_lens(scene.camera.aperture_radius, scene.camera.focus_distance)
+        if getattr(scene, "environment", None) is not None:      # (the upload itself resets the context to none)
+            self.set_environment(scene.environment)
         if build:
             self.build_accel(builder)
         return self
+
+    # ------------------------------------------------------------ environment map
+    def set_environment(self, env):
+        """The environment-map emitter of the uploaded scene (include/nori_hip.h, "Environment-map emitter"): a scene.Environment, or
+        None for no environment -- the kernels and the bits of a context that never had one.  Holds until the next upload."""
+        if env is None:
+            self._check(self._lib.nori_hip_set_environment(self._h, None), "set_environment")
+        else:
+            d = env.desc()
+            self._check(self._lib.nori_hip_set_environment(self._h, C.byref(d)), "set_environment")
+        return self
+
+    @property
+    def environment_size(self) -> int:
+        """N of the environment map set, 0: none."""
+        n = C.c_uint32(0)
+        self._check(self._lib.nori_hip_get_environment(self._h, C.byref(n)), "get_environment")
+        return int(n.value)
+
+    def env_eval(self, dirs, pdf: bool = True):
+        """(Le (n, 3), pdf (n,)) of the (n, 3) world directions -- or Le alone with pdf=False -- by the lookup the path uses."""
+        d = _f32(dirs, 3)
+        rgb = np.zeros((d.shape[0], 3), np.float32)
+        p = np.zeros(d.shape[0], np.float32) if pdf else None
+        self._check(self._lib.nori_hip_env_eval(self._h, ptr(d), d.shape[0], ptr(rgb), ptr(p)), "env_eval")
+        return (rgb, p) if pdf else rgb
+
+    def env_sample(self, xi):
+        """(directions (n, 3), Le (n, 3), pdf (n,)) the (n, 2) samples select, as an emitter sample of the path draws them."""
+        x = _f32(xi, 2)
+        n = x.shape[0]
+        d, rgb, p = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+        self._check(self._lib.nori_hip_env_sample(self._h, ptr(x), n, ptr(d), ptr(rgb), ptr(p)), "env_sample")
+        return d, rgb, p
+
+    def env_tables(self):
+        """(row_cdf (N + 1,), col_cdf (N, N + 1), texel_weight (N, N)) as the device built and holds them."""
+        n = self.environment_size
+        rows, cols, w = np.zeros(n + 1, np.float32), np.zeros((n, n + 1), np.float32), np.zeros((n, n), np.float32)
+        self._check(self._lib.nori_hip_debug_env_tables(self._h, ptr(rows), ptr(cols), ptr(w)), "debug_env_tables")
+        return rows, cols, w
 
     def set_lens(self, radius: float, focus_distance: float = 1.0):
         """The thin lens of the uploaded scene's camera (include/nori_hip.h, "Thin-lens camera"): aperture radius and focus distance
@@ -891,6 +934,14 @@ class DeviceGroup:
         self.scene = scene
         if scene.camera.aperture_radius > 0:
             self.set_lens(scene.camera.aperture_radius, scene.camera.focus_distance)
+        if getattr(scene, "environment", None) is not None:
+            self.set_environment(scene.environment)
+        return self
+
+    def set_environment(self, env):
+        """Renderer.set_environment on every device of the group."""
+        d = env.desc() if env is not None else None
+        self._check(self._lib.nori_hip_group_set_environment(self._h, C.byref(d) if d is not None else None), "group_set_environment")
         return self
 
     def set_lens(self, radius: float, focus_distance: float = 1.0):

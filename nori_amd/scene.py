@@ -78,6 +78,29 @@ class Texture:
 
 
 @dataclass
+class Environment:
+    """An environment-map emitter (nori_env_desc in include/nori_hip.h, which states the lookup, the density and the sampling).
+    Not part of nori_scene_desc: Renderer.upload applies it with nori_hip_set_environment."""
+    texels: np.ndarray                      # (N, N, 3) float32 linear RGB, OCTAHEDRAL layout: texels[j, i] is column i of row j
+    scale: tuple = (1.0, 1.0, 1.0)
+    to_world: np.ndarray = field(default_factory=lambda: np.eye(3, dtype=np.float32))      # rotation, world = M local
+
+    def __post_init__(self):
+        self.texels = np.ascontiguousarray(self.texels, dtype=np.float32)
+        assert self.texels.ndim == 3 and self.texels.shape[0] == self.texels.shape[1] and self.texels.shape[2] == 3, "texels: (N, N, 3)"
+        self.to_world = np.ascontiguousarray(self.to_world, dtype=np.float32).reshape(3, 3)
+
+    def desc(self) -> capi.EnvDesc:
+        """The ctypes struct; it borrows self.texels."""
+        d = capi.EnvDesc()
+        d.size = int(self.texels.shape[0])
+        d.texels = self.texels.ctypes.data
+        d.scale[:] = [float(x) for x in self.scale]
+        d.to_world[:] = [float(x) for x in self.to_world.reshape(9)]
+        return d
+
+
+@dataclass
 class Mesh:
     positions: np.ndarray                   # (nV, 3) float32, world space
     indices: np.ndarray                     # (nF, 3) uint32
@@ -135,6 +158,7 @@ class Scene:
     integrator: Integrator = field(default_factory=Integrator)
     sample_count: int = 1
     textures: List[Texture] = field(default_factory=list)
+    environment: Optional[Environment] = None      # path_mats / path_ems / path_mis; applied after the upload
 
     # ------------------------------------------------------------ C view
     def c_desc(self):
@@ -228,7 +252,10 @@ class Scene:
             meta["camera"].update(aperture_radius=float(self.camera.aperture_radius), focus_distance=float(self.camera.focus_distance))
         if self.textures:
             meta["textures"] = [dict(t.params(), texels=t.texels is not None) for t in self.textures]
+        if self.environment is not None:      # (scenes without one: the file of before, key for key)
+            meta["environment"] = {"scale": list(map(float, self.environment.scale))}
         if base is not None:
+            assert self.environment is None, "a variant fixture (base=...) stores no arrays: save a scene with an environment whole"
             assert not self.textures, "a variant fixture (base=...) stores no arrays: save a textured scene whole"
             meta["base"], meta["geometry_digest"] = base, self.geometry_digest()
             np.savez_compressed(path, meta=np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8))
@@ -244,6 +271,8 @@ class Scene:
         for k, t in enumerate(self.textures):
             if t.texels is not None:
                 arrays[f"t{k}_texels"] = t.texels
+        if self.environment is not None:
+            arrays["env_texels"], arrays["env_to_world"] = self.environment.texels, self.environment.to_world
         arrays["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
         np.savez_compressed(path, **arrays)
 
@@ -287,4 +316,6 @@ class Scene:
             has_texels = p.pop("texels")
             p["color0"], p["color1"] = tuple(p["color0"]), tuple(p["color1"])
             sc.textures.append(Texture(texels=z[f"t{k}_texels"] if has_texels else None, **p))
+        if "environment" in meta:
+            sc.environment = Environment(z["env_texels"], tuple(meta["environment"]["scale"]), z["env_to_world"])
         return sc
