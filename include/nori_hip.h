@@ -1144,6 +1144,82 @@ int nori_hip_debug_env_tables(nori_hip_ctx *ctx, float *row_cdf, float *col_cdf,
 /* nori_hip_set_environment on every device's context (the upload resets it, as on one context) */
 int nori_hip_group_set_environment(nori_hip_group *group, const nori_env_desc *env);
 
+/* ------------------------------------------- Homogeneous participating medium
+ *
+ * No counterpart in the reference, whose class enum names EMedium and EPhaseFunction (include/nori/object.h:25,27) and ships neither.
+ * There is ONE medium per context and it fills all space; the camera is inside it.  It is a state of the context, set after the
+ * upload like the lens and the environment and reset by the next upload; no struct of the scene description grows.  Without one
+ * every kernel is the kernel it was: the path integrators have a third set of instantiations (rt_path.h, kMedium) that only
+ * contexts with a medium run -- "every BSDF, textures, medium", and on the wavefront engine the full path record.  path_mats,
+ * path_ems and path_mis render it; every other integrator refuses it (NORI_ERR_UNSUPPORTED), and so do a context with an
+ * environment map (a medium that fills all space has zero transmittance to infinity; nori_hip_set_environment refuses likewise
+ * while a medium is set) and NORI_SEED_NORI_BLOCK renders.  The feature pass is unchanged: it reports the first SURFACE a camera
+ * ray meets, whatever lies between.
+ *
+ * Parameters: a scalar (grey) extinction sigma_t, a single-scattering albedo[3], the Henyey-Greenstein asymmetry g (g > 0 scatters
+ * forward, along the ray's direction of travel).  A grey sigma_t makes the weights of distance sampling cancel exactly: a
+ * scattering vertex multiplies the throughput by albedo and by nothing else, reaching a surface multiplies it by 1.
+ *
+ * Everything below is float32 without FMA contraction; every / is the correctly rounded quotient, every sqrt the correctly rounded
+ * root; log, exp, sin and cos are the pinned ones; dot(a, b) = a.x b.x + (a.y b.y + a.z b.z).
+ *
+ *   Derived once.         g2 = g g;  A = 1 - g2;  B = 1 + g2;  G2 = 2 g;  C = 1 - g.  A g with |g| < 1e-3 is stored as exactly 0.
+ *   Density.              HG(c) = (kInvFourPi A) / (k sqrt(k)),  k = B - G2 c;  with g = 0 this is kInvFourPi exactly.
+ *   Transmittance.        Tr(dist) = exp(-(sigma_t dist)).
+ *   Distance.             s(xi) = (-log(1 - xi)) / sigma_t + 0   (the addition changes one value: xi = 0 gives +0, not -0).
+ *   Phase sample(d, xi).  g = 0: local = squareToUniformSphere(xi).  Otherwise sq = A / (C + G2 xi.x);  c = (B - sq sq) / G2, clamped
+ *                         to [-1, 1];  r = sqrt(max(0, 1 - c c));  (sn, cs) = sincos((2 kPi) xi.y);  local = (r cs, r sn, c).
+ *                         wo = Frame(d).toWorld(local), not renormalised;  pdf = HG(dot(d, wo)), RE-EVALUATED from the final
+ *                         direction: sampling and emitter sampling agree on the density of a direction.
+ *   In Li (path_mats / path_ems / path_mis).  When the answer of a closest-hit query for the ray (o, d) is consumed, before
+ *                         anything else: one number xi_d is drawn (camera rays and continuation rays alike, so it follows the
+ *                         camera sample's four draws) and s = s(xi_d).  The vertex is a MEDIUM vertex iff nothing was hit or
+ *                         s < hit.t; otherwise it is the surface vertex of before.
+ *     Surface vertex.     As without a medium, with one change: the emitter sample's Ld is the product of before, then
+ *                         multiplied per component by Tr(dist), dist being the distance to the sampled point (before - kEpsilon).
+ *                         Weights and densities are unchanged: the balance-heuristic weights ignore Tr in both strategies and
+ *                         still sum to 1 per path.
+ *     Medium vertex at p = o + d s  (per component: multiply, then add).  In this order:
+ *                         1. T = T albedo; if T is zero in every component the path ends here and draws nothing more.
+ *                         2. Russian roulette at depth >= 3 exactly as at a surface: one draw, p = min(max3(T) eta^2, 0.99).
+ *                         3. path_ems / path_mis: an emitter sample, always four draws (xiE, xiT, xi); the pick and the point
+ *                            as at a surface; dvec, dist2, dist, dir, cosY as there, rejected unless cosY > 0;
+ *                            ph = HG(dot(d, dir));  pdfA = inv_area pdfPick;  pdf_em = (pdfA dist2) / cosY;  pdf_bsdf = ph;
+ *                            Ld_c = ((ph rad_c) (cosY / (dist2 pdfA))) Tr(dist);  what the unoccluded shadow ray adds is
+ *                            (T Ld) w, w = pdf_em / (pdf_em + ph) under path_mis and 1 under path_ems.  The shadow ray starts
+ *                            at p with mint = kEpsilon and maxt = dist - kEpsilon.
+ *                         4. a phase sample with two draws; pdf_mat = its pdf, the measure is solid angle, eta and T are
+ *                            unchanged, depth += 1.
+ *                         5. the next queries leave p with mint = kEpsilon, the shadow ray first, as at a surface.
+ *                         An emitter hit after a medium vertex takes the wMat of before, with pdf_mat the phase density.
+ *
+ * nori_hip_set_medium           medium == NULL: no medium (the kernels and bits of before).  Else it is used from the next launch on;
+ *                               nothing is allocated or launched.  NORI_ERR_NOT_READY before an upload; NORI_ERR_INVALID_ARGUMENT,
+ *                               with a message, for a sigma_t that is not finite or outside [1e-4, 1e4], an albedo component that
+ *                               is not finite or outside [0, 1], |g| > 0.99 (the bounds keep every quotient above inside the
+ *                               verified domain of the device's division); NORI_ERR_UNSUPPORTED, with a message, for an
+ *                               integrator other than the three path integrators and for a context with an environment map.  A
+ *                               failed call leaves the context's medium as it was.
+ * nori_hip_get_medium           1 and the medium as stored (g: 0 where |g| < 1e-3) if one is set, 0 if none, or a negative status.
+ * nori_hip_medium_distance      s(xi) of n samples.
+ * nori_hip_medium_transmittance Tr(dist) of n distances.
+ * nori_hip_phase_eval           HG(dot(d, wo)) of n pairs of directions (d, wo: 3n each, unit length).
+ * nori_hip_phase_sample         the phase sample of n directions d (3n) and pairs xi (2n): wo (3n) and pdf (n).
+ * The last four return NORI_ERR_NOT_READY, with a message, while no medium is set. */
+typedef struct nori_medium_desc {
+    float sigma_t;         /* extinction, grey: 1e-4 .. 1e4 */
+    float albedo[3];       /* single-scattering albedo, each 0 .. 1 */
+    float g;               /* Henyey-Greenstein asymmetry, |g| <= 0.99; 0: isotropic */
+} nori_medium_desc;
+int nori_hip_set_medium(nori_hip_ctx *ctx, const nori_medium_desc *medium);
+int nori_hip_get_medium(const nori_hip_ctx *ctx, nori_medium_desc *medium);
+int nori_hip_medium_distance(nori_hip_ctx *ctx, const float *xi, size_t n, float *s);
+int nori_hip_medium_transmittance(nori_hip_ctx *ctx, const float *dist, size_t n, float *tr);
+int nori_hip_phase_eval(nori_hip_ctx *ctx, const float *d, const float *wo, size_t n, float *pdf);
+int nori_hip_phase_sample(nori_hip_ctx *ctx, const float *d, const float *xi, size_t n, float *wo, float *pdf);
+/* nori_hip_set_medium on every device's context (the upload resets it, as on one context) */
+int nori_hip_group_set_medium(nori_hip_group *group, const nori_medium_desc *medium);
+
 #ifdef __cplusplus
 }
 #endif

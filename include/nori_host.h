@@ -43,6 +43,10 @@ int nori_host_lens(const nori_host_root *root, float *radius, float *focus);
  * takes; the texels are borrowed (valid until free).  Returns 1 and fills *out if the scene has one, 0 if it has none (out->size = 0),
  * or a negative nori_status.  Not part of nori_scene_desc: apply it after the upload. */
 int nori_host_environment(const nori_host_root *root, nori_env_desc *out);
+/* Root is a <scene>: its medium (<medium type="homogeneous">, with its <phase> child's g), the record nori_hip_set_medium takes.
+ * Returns 1 and fills *out if the scene has one, 0 if it has none, or a negative nori_status.  Not part of nori_scene_desc: apply
+ * it after the upload. */
+int nori_host_medium(const nori_host_root *root, nori_medium_desc *out);
 
 /* Root is a <test>: kind 0 = ttest, 1 = chi2test. */
 typedef struct nori_host_test_info {

@@ -163,6 +163,11 @@ class EnvDesc(C.Structure):
     _fields_ = [("size", C.c_uint32), ("texels", C.c_void_p), ("scale", C.c_float * 3), ("to_world", C.c_float * 9)]
 
 
+class MediumDesc(C.Structure):
+    """nori_medium_desc"""
+    _fields_ = [("sigma_t", C.c_float), ("albedo", C.c_float * 3), ("g", C.c_float)]
+
+
 class AccelInfo(C.Structure):
     _fields_ = [("n_triangles", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("max_depth", C.c_uint32), ("node_bytes", C.c_uint32), ("tri_bytes", C.c_uint32),
@@ -284,6 +289,13 @@ HIP_PROTOTYPES = {
     "nori_hip_env_sample": (C.c_int, [_P, _P, C.c_size_t, _P, _P, _P]),
     "nori_hip_debug_env_tables": (C.c_int, [_P, _P, _P, _P]),
     "nori_hip_group_set_environment": (C.c_int, [_P, C.POINTER(EnvDesc)]),
+    "nori_hip_set_medium": (C.c_int, [_P, C.POINTER(MediumDesc)]),
+    "nori_hip_get_medium": (C.c_int, [_P, C.POINTER(MediumDesc)]),
+    "nori_hip_medium_distance": (C.c_int, [_P, _P, C.c_size_t, _P]),
+    "nori_hip_medium_transmittance": (C.c_int, [_P, _P, C.c_size_t, _P]),
+    "nori_hip_phase_eval": (C.c_int, [_P, _P, _P, C.c_size_t, _P]),
+    "nori_hip_phase_sample": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P]),
+    "nori_hip_group_set_medium": (C.c_int, [_P, C.POINTER(MediumDesc)]),
 }
 
 

@@ -1,4 +1,4 @@
-/* ctx.h -- the context behind the C ABI and what the entry points of nori_hip.hip, frame_api.hip and env_map.hip (those units only) need
+/* ctx.h -- the context behind the C ABI and what the entry points of nori_hip.hip, frame_api.hip, env_map.hip and medium.hip (those units only) need
  * of it: the error mapping, the device guard, scratch buffers, the frame's sizes, the stats of a call. */
 #pragma once
 #include <hip/hip_runtime.h>

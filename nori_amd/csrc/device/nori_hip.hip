@@ -77,7 +77,8 @@ struct RenderArgs {
 };
 
 /* MATSET = kAnyBsdf | kTextured (rt_path.h): the kernel of scenes with textured albedos; kAnyBsdf | kTextured | kEnvLit: of scenes
-   with an environment map (path_mats / path_ems / path_mis; textured or not); kAnyBsdf: every other scene */
+   with an environment map (path_mats / path_ems / path_mis; textured or not); kAnyBsdf | kTextured | kMedium: of contexts with a
+   medium (the same three; never together with an environment); kAnyBsdf: every other scene */
 template <int INTEG, int STACK, bool COUNT, int MATSET = kAnyBsdf>
 __global__ __launch_bounds__(kBlock, NORI_RENDER_MIN_WAVES) void render_kernel(DevScene sc, RenderArgs args, FilmStore film,
                                                         unsigned long long *stats) {
@@ -148,7 +149,10 @@ __global__ __launch_bounds__(kBlock, NORI_RENDER_MIN_WAVES) void render_kernel(D
             if (!gen) {
                 bool done;
                 if (st.phase == PH_SHADOW) done = path_on_shadow(st, tv.hit.tri != kNoHit, tv.o);
-                else done = path_on_closest<INTEG, MATSET>(sc, st, tv.hit, tv.hit.tri != kNoHit, tv.d);
+                else {
+                    if (MATSET & kMedium) st.ray.o = tv.o;      /* (the origin of the ray whose answer this is: rt_path.h) */
+                    done = path_on_closest<INTEG, MATSET>(sc, st, tv.hit, tv.hit.tri != kNoHit, tv.d);
+                }
                 if (done) {
                     /* block.put(pixelSample, value), src/main.cpp:52: the sample goes to the film's
                        store (20 B); film_gather applies the reconstruction filter afterwards */
@@ -245,6 +249,7 @@ __global__ __launch_bounds__(kBlock) void li_kernel(DevScene sc, const nori_ray 
             Hit hit;
             const f3 qo = st.ray.o, qd = st.ray.d;
             const bool found = traverse<false>(sc, st.ray, any, stack, hit, tc);
+            if (MATSET & kMedium) st.ray.o = qo;
             const bool done = any ? path_on_shadow(st, found, qo) : path_on_closest<INTEG, MATSET>(sc, st, hit, found, qd);
             if (done) break;
         }
@@ -572,6 +577,7 @@ int nori_hip_upload_scene(nori_hip_ctx *ctx, const nori_scene_desc *scene) {
     DeviceGuard g(ctx->device);
     free_pool(ctx->allocs_scene); free_pool(ctx->allocs_accel);
     env_release(ctx);      /* the environment map is set after an upload and lasts until the next (nori_hip_set_environment) */
+    memset(&ctx->dev.medium, 0, sizeof(ctx->dev.medium));      /* and so is the medium (nori_hip_set_medium) */
     ctx->have_scene = ctx->have_accel = false;
     std::string err = prepare_scene(*scene, ctx->host);
     if (!err.empty()) { ctx->error = err; return NORI_ERR_INVALID_ARGUMENT; }
@@ -898,7 +904,8 @@ static void launch_li(nori_hip_ctx *ctx, const nori_ray *r, size_t n, const uint
 #define LI_CASE(I) case I: hipLaunchKernelGGL((li_kernel<I, STACK>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); break;
 #define LI_TEX(I) case I: if (ctx->dev.textured) { hipLaunchKernelGGL((li_kernel<I, STACK, kAnyBsdf | kTextured>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } \
                           else { hipLaunchKernelGGL((li_kernel<I, STACK>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } break;
-#define LI_ENV(I) case I: if (ctx->dev.env) { hipLaunchKernelGGL((li_kernel<I, STACK, kAnyBsdf | kTextured | kEnvLit>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } \
+#define LI_ENV(I) case I: if (ctx->dev.medium.on) { hipLaunchKernelGGL((li_kernel<I, STACK, kAnyBsdf | kTextured | kMedium>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } \
+                          else if (ctx->dev.env) { hipLaunchKernelGGL((li_kernel<I, STACK, kAnyBsdf | kTextured | kEnvLit>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } \
                           else if (ctx->dev.textured) { hipLaunchKernelGGL((li_kernel<I, STACK, kAnyBsdf | kTextured>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } \
                           else { hipLaunchKernelGGL((li_kernel<I, STACK>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } break;
         LI_CASE(0) LI_CASE(1) LI_CASE(2) LI_TEX(3) LI_ENV(4) LI_ENV(5) LI_ENV(6)
@@ -1184,6 +1191,8 @@ static hipError_t launch_render_one(nori_hip_ctx *ctx, const RenderArgs &a, cons
     /* the path integrators have one for scenes with an environment map: every BSDF, textures, environment (kEnvLit) */
     if constexpr (INTEG >= INT_MATS) {
         if (ctx->dev.env) kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured | kEnvLit>;
+        /* and one for contexts with a medium: every BSDF, textures, the medium (kMedium; never with an environment) */
+        if (ctx->dev.medium.on) kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured | kMedium>;
     }
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
@@ -1247,6 +1256,11 @@ int check_render_params(nori_hip_ctx *ctx, const nori_render_params *params, con
     if (params->seed_mode == NORI_SEED_NORI_BLOCK && ctx->dev.env) {
         ctx->error = "render: NORI_SEED_NORI_BLOCK renders no environment map (the mode exists for parity with the reference's sampler, and the reference has no "
                      "environment emitter); unset it (nori_hip_set_environment with NULL) or use NORI_SEED_PER_SAMPLE";
+        return NORI_ERR_UNSUPPORTED;
+    }
+    if (params->seed_mode == NORI_SEED_NORI_BLOCK && ctx->dev.medium.on) {
+        ctx->error = "render: NORI_SEED_NORI_BLOCK renders no medium (the mode exists for parity with the reference's sampler, and the reference has no "
+                     "medium); unset it (nori_hip_set_medium with NULL) or use NORI_SEED_PER_SAMPLE";
         return NORI_ERR_UNSUPPORTED;
     }
     if (ctx->host.filter.border > 8) { ctx->error = "render: reconstruction filter radius too large for the LDS tile"; return NORI_ERR_UNSUPPORTED; }

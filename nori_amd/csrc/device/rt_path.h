@@ -19,6 +19,7 @@
 #include "rt_sampling.h"
 #include "rt_texture.h"
 #include "env_map.h"
+#include "medium.h"
 #include "rt_trace.h"
 
 namespace nrt {
@@ -99,10 +100,16 @@ NORI_HD uint32_t emitter_pick(const Tab &tab, uint32_t nE, float xiE, float xiT,
    without the bit no texture code is compiled -- the kernels of scenes without textures are the kernels of before.
    kEnvLit (bit 5): the scene has an environment map (env_map.h; DevScene::env is not null).  It is one more light in the emitter
    pick -- index n_emitters --, and a ray that leaves the scene collects it.  Without the bit none of that is compiled: the
-   kernels of scenes without an environment are the kernels of before.  path_mats / path_ems / path_mis only. */
+   kernels of scenes without an environment are the kernels of before.  path_mats / path_ems / path_mis only.
+   kMedium (bit 6): the context has a homogeneous medium (medium.h; DevScene::medium.on).  Every closest-hit answer first draws a
+   free-flight distance; a scattering event before the surface is a vertex of its own kind (`med` in path_on_closest: it runs
+   through the surface vertex's code with the phase function in the BSDF's place), and an emitter sample is attenuated by the
+   transmittance.  path_on_closest then needs the ORIGIN of the ray whose answer it consumes: the caller
+   leaves it in st.ray.o.  Without the bit none of that is compiled or read.  path_mats / path_ems / path_mis only. */
 constexpr int kAnyBsdf = 0xf;
 constexpr int kTextured = 0x10;
 constexpr int kEnvLit = 0x20;
+constexpr int kMedium = 0x40;
 
 struct NeeResult {
     f3 Ld;          /* f * Le * cosX * cosY / (dist^2 * pdfA); the environment: f * Le * cosX / pdf_em */
@@ -114,9 +121,12 @@ struct NeeResult {
 /* Emitter sampling at surface `s`: uniform emitter, triangle by area, uniform
  * barycentrics (alpha = 1 - sqrt(1 - xi1), beta = xi2 sqrt(1 - xi1)).
  * Always consumes 4 random numbers.  Returns true if a shadow ray is needed. */
+/* Under kMedium the vertex may be a scattering event in the medium (med; s.p is its position, d the ray's direction of travel, fr /
+ * bsdf / wi are not read): the pick and the point are the same, the phase function stands in the BSDF's place and there is no
+ * cosine at the vertex.  One body for both kinds of vertex: the kernel holds ONE copy of the pick, the point and Tr. */
 template <class Tab, int MATSET = kAnyBsdf>
 NORI_HD bool sample_direct(const DevScene &sc, const Tab &tab, Rng &rng, const Surface &s, const Frame &fr,
-                           const Bsdf &bsdf, f3 wi, NeeResult &out) {
+                           const Bsdf &bsdf, f3 wi, NeeResult &out, const bool med = false, const f3 d = f3()) {
     const float xiE = rng_next_float(rng);
     const float xiT = rng_next_float(rng);
     const f2 xi = rng_next_2d(rng);
@@ -154,6 +164,19 @@ NORI_HD bool sample_direct(const DevScene &sc, const Tab &tab, Rng &rng, const S
     const f3 dir = dvec / dist;
     const float cosY = dot(n, -dir);
     if (!(cosY > 0.0f)) return false;
+    float tr = 1.0f;      /* (evaluated here, where the fewest values are alive: it runs in binary64) */
+    if (MATSET & kMedium) tr = medium_tr(sc.medium, dist);
+    if ((MATSET & kMedium) && med) {
+        const float ph = hg_eval(sc.medium, dot(d, dir));
+        const float pdfA = m.inv_area * pdfPick;
+        out.pdf_em = exact_div(pdfA * dist2, cosY);
+        out.pdf_bsdf = ph;
+        const f3 rad = mk3(m.radiance[0], m.radiance[1], m.radiance[2]);
+        out.Ld = ((ph * rad) * exact_div(cosY, dist2 * pdfA)) * tr;
+        out.dir = dir;
+        out.maxt = dist - kEpsilon;
+        return true;
+    }
     const f3 wo = to_local(fr, dir);
     const f3 f = bsdf_eval(bsdf, wi, wo);
     if (is_zero(f)) return false;
@@ -163,6 +186,7 @@ NORI_HD bool sample_direct(const DevScene &sc, const Tab &tab, Rng &rng, const S
     const float cosX = wo.z;
     const f3 rad = mk3(m.radiance[0], m.radiance[1], m.radiance[2]);
     out.Ld = f * rad * exact_div(cosX * cosY, dist2 * pdfA);
+    if (MATSET & kMedium) out.Ld = out.Ld * tr;      /* (the MIS weights ignore Tr in both strategies) */
     out.dir = dir;
     out.maxt = dist - kEpsilon;
     return true;
@@ -192,7 +216,17 @@ template <int MATSET> NORI_HD int32_t bsdf_type_in_set(int32_t type) {
 }
 template <int INTEG, class Tab, int MATSET = kAnyBsdf>
 NORI_HD bool path_on_closest(const DevScene &sc, const Tab &tab, PathState &st, const Hit &hit, bool found, const f3 d) {
-    if (!found) {
+    /* kMedium: the free flight -- a scattering event before the surface, or past every surface, is a MEDIUM vertex (med).  It
+       shares the surface vertex's Russian roulette, emitter sample and tail below; what only a surface has is skipped */
+    bool med = false;
+    f3 pm = mk3(0.0f);
+    if ((MATSET & kMedium) && INTEG >= INT_MATS) {
+        const float s = medium_distance(sc.medium, rng_next_float(st.rng));
+        med = !found || s < hit.t;
+        pm = st.ray.o + d * s;
+    }
+    const bool MED = (MATSET & kMedium) && med;      /* (false at compile time without the bit) */
+    if (!found && !MED) {
         if ((MATSET & kEnvLit) && INTEG >= INT_MATS) {      /* the ray left the scene: the environment, weighted as an emitter hit is below */
             const bool weighted = INTEG != INT_MATS && st.prev_measure != 2;
             if (!(weighted && INTEG == INT_EMS)) {      /* (path_ems counts it at the vertex before: weight 0) */
@@ -207,9 +241,10 @@ NORI_HD bool path_on_closest(const DevScene &sc, const Tab &tab, PathState &st, 
         }
         return true;
     }
-    const MeshRec m = tab.mesh(hit.mesh);
+    const MeshRec m = MED ? MeshRec() : tab.mesh(hit.mesh);      /* (a medium vertex: no mesh -- not an emitter, nothing textured) */
     Surface sf;
-    {
+    if (MED) { sf.p = pm; sf.ns = d; }      /* the frame below is then the frame of the direction of travel, which the phase sample needs */
+    else {
         const f4 *rec = sc.shade_tris + (size_t) hit.tri * kShadeQuads;
         const bool hn = (m.flags & kMeshHasNormals) != 0u;
         const f3 z = mk3(0.0f);
@@ -294,6 +329,10 @@ NORI_HD bool path_on_closest(const DevScene &sc, const Tab &tab, PathState &st, 
         const f3 le = dot(sf.ns, -d) > 0.0f ? rad : mk3(0.0f);
         st.L = st.L + st.T * le * wMat;
     }
+    if (MED) {      /* a scattering event: the albedo and nothing else (a grey extinction cancels against the distance's density) */
+        st.T = st.T * mk3(sc.medium.albedo[0], sc.medium.albedo[1], sc.medium.albedo[2]);
+        if (is_zero(st.T)) return true;
+    }
     if (st.depth >= 3) {
         const float p = fminf(max3(st.T) * st.eta * st.eta, 0.99f);
         if (!(rng_next_float(st.rng) < p)) return true;
@@ -301,13 +340,28 @@ NORI_HD bool path_on_closest(const DevScene &sc, const Tab &tab, PathState &st, 
     }
     bool needShadow = false;
     NeeResult nee;
-    if (EMS && bsdf_is_diffuse(bsdf.type)) {
-        needShadow = sample_direct<Tab, MATSET>(sc, tab, st.rng, sf, fr, bsdf, wi, nee);
+    if (EMS && (MED || bsdf_is_diffuse(bsdf.type))) {
+        needShadow = sample_direct<Tab, MATSET>(sc, tab, st.rng, sf, fr, bsdf, wi, nee, MED, d);
         if (needShadow) {
             float w = 1.0f;
             if (MIS) w = (nee.pdf_em + nee.pdf_bsdf) > 0.0f ? exact_div(nee.pdf_em, nee.pdf_em + nee.pdf_bsdf) : 0.0f;
             st.Ld = st.T * nee.Ld * w;
         }
+    }
+    if (MED) {      /* the phase sample: two draws; its density re-evaluated from the direction it made; solid angle; T and eta stay */
+        st.cont_d = to_world(fr, hg_sample_local(sc.medium, rng_next_2d(st.rng)));
+        st.prev_measure = 1;
+        st.pdf_mat = MIS ? hg_eval(sc.medium, dot(d, st.cont_d)) : 0.0f;
+        st.depth++;
+        st.ray.o = sf.p; st.ray.mint = kEpsilon;
+        if (needShadow) {
+            st.ray.d = nee.dir; st.ray.maxt = nee.maxt;
+            st.phase = PH_SHADOW; st.end_after_shadow = 0;
+            return false;
+        }
+        st.ray.d = st.cont_d; st.ray.maxt = kInf;
+        st.phase = PH_CLOSEST;
+        return false;
     }
     f3 wo; float e; int measure;
     const f3 f = bsdf_sample(bsdf, wi, rng_next_2d(st.rng), wo, e, measure);

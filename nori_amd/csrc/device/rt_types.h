@@ -344,6 +344,16 @@ static_assert(sizeof(MeshRec) == 80, "the LDS shade tables (shade_tables.h) hold
 struct TexRec;
 struct EnvRec;
 
+/* the homogeneous participating medium of the context (medium.h; include/nori_hip.h, "Homogeneous participating medium"): it fills all
+   space.  Set by nori_hip_set_medium, never by a scene description.  g, and what is derived from it once in float32:
+   a = 1 - g g, b = 1 + g g, g2 = 2 g, c = 1 - g.  on = 0: none -- every other word is zero then. */
+struct MediumRec {
+    float sigma_t = 0.0f;
+    float albedo[3] = {0.0f, 0.0f, 0.0f};
+    float g = 0.0f, a = 0.0f, b = 0.0f, g2 = 0.0f, c = 0.0f;
+    uint32_t on = 0u;
+};
+
 struct CameraRec {
     float sample_to_camera[16];   /* row-major */
     float camera_to_world[16];
@@ -406,6 +416,8 @@ struct DevScene {
     /* the environment map (env_map.h), set by nori_hip_set_environment, never by a scene description; null: none -- and then the
        kernels compiled without kEnvLit run (rt_path.h), which never read it */
     const EnvRec *env;
+    /* the medium (above), by value; medium.on = 0: none -- and then the kernels compiled without kMedium run (rt_path.h), which never read it */
+    MediumRec medium;
 };
 
 struct Hit {

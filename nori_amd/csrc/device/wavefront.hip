@@ -48,6 +48,9 @@ namespace nrt {
    this unit's WfBuf and WfBatch (wf_device.h, which both units include; the types live in each unit's unnamed namespace). */
 void wf_env_launch_shade(const DevScene &sc, const void *wf_buf, int cur, const void *batch, int mode, int grid, hipStream_t s);
 void wf_env_launch_finish(const DevScene &sc, const void *wf_buf, int cur, const void *batch, bool count, int grid, hipStream_t s);
+/* wavefront_medium.hip: the same for contexts with a medium -- MATSET kAnyBsdf | kTextured | kMedium */
+void wf_medium_launch_shade(const DevScene &sc, const void *wf_buf, int cur, const void *batch, int mode, int grid, hipStream_t s);
+void wf_medium_launch_finish(const DevScene &sc, const void *wf_buf, int cur, const void *batch, bool count, int grid, hipStream_t s);
 }
 
 namespace {
@@ -563,11 +566,13 @@ void launch_extend_dyn(const DevScene &sc, const WfBuf &b, int cur, int refill, 
 bool record_compact(const DevScene &sc) {
     static const bool full = [] { const char *e = getenv("NORI_HIP_WF_RECORD"); return e && std::string(e) == "full"; }();
     if (sc.env) return false;      /* an environment map: the one general variant, on the full record (wavefront_env.hip) */
+    if (sc.medium.on) return false;      /* a medium: likewise (wavefront_medium.hip) */
     return !full && sc.integrator.type >= INT_MATS && sc.bsdf_mask == 1u && !getenv("NORI_HIP_SHADE_ANY_BSDF");
 }
 
 void launch_shade(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt, int mode, int grid_, bool compact, hipStream_t s) {
     if (sc.env && sc.integrator.type >= INT_MATS) { wf_env_launch_shade(sc, &b, cur, &bt, mode, grid_, s); return; }      /* kEnvLit: wavefront_env.hip */
+    if (sc.medium.on && sc.integrator.type >= INT_MATS) { wf_medium_launch_shade(sc, &b, cur, &bt, mode, grid_, s); return; }      /* kMedium: wavefront_medium.hip */
     const dim3 grid(grid_ * (kB / kSB)), block(kSB);
     const bool lds_tables = shade_tables_fit(sc);
     /* the material set the kernel is compiled for: all-diffuse scenes (the Cornell box of the headline), scenes without a
@@ -598,6 +603,7 @@ void launch_shade(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt
 
 void launch_finish(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt, bool count, int grid_, bool compact, hipStream_t s) {
     if (sc.env && sc.integrator.type >= INT_MATS) { wf_env_launch_finish(sc, &b, cur, &bt, count, grid_, s); return; }
+    if (sc.medium.on && sc.integrator.type >= INT_MATS) { wf_medium_launch_finish(sc, &b, cur, &bt, count, grid_, s); return; }
     const dim3 grid(grid_), block(kB);
     const size_t lds = (size_t) LdsStackW<16, true>::kLdsEntries * kB * sizeof(int);
     switch (sc.integrator.type) {

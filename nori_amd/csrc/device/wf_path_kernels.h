@@ -60,6 +60,7 @@ __global__ __launch_bounds__(kSB, NORI_SHADE_WGS) void NORI_WF_SHADE_KERNEL(DevS
         if (FRESH ? i < n : i < n_s) {
             /* the path's state: from HBM, or -- first vertex -- recomputed from the sample index */
             uint32_t fl; f4 L4, d4, t4; Rng rng0; rng0.state = 0; rng0.inc = 0;
+            f3 org = mk3(0.0f);      /* kMedium: the origin of the ray whose answer this vertex consumes (rt_path.h) */
             if (FRESH) {
                 f2 ps; RayIn cam;
                 sidx = shape.s0 + (i - shape.n_f0);
@@ -67,6 +68,7 @@ __global__ __launch_bounds__(kSB, NORI_SHADE_WGS) void NORI_WF_SHADE_KERNEL(DevS
                 L4.x = L4.y = L4.z = L4.w = 0.0f;                  /* L = 0, pdf_mat = 0 */
                 t4.x = t4.y = t4.z = t4.w = 1.0f;                  /* T = 1, eta = 1 */
                 d4.x = cam.d.x; d4.y = cam.d.y; d4.z = cam.d.z; d4.w = 0.0f;
+                if (MATSET & kMedium) org = cam.o;
             } else {
                 d4 = c_d;               /* the continuation direction and, in its w, the flags (wf_records.h) */
                 fl = state_flags(d4);
@@ -103,6 +105,10 @@ __global__ __launch_bounds__(kSB, NORI_SHADE_WGS) void NORI_WF_SHADE_KERNEL(DevS
                     if (kNoEta && !FRESH) vertex_unpack_diffuse(st, fl, p3_of(L4), t4, rng_state, ((uint64_t) (s_first + sl) << 1u) | 1u);
                     else
                     vertex_unpack(st, fl, L4, t4, rng_state, ((uint64_t) (s_first + sl) << 1u) | 1u);
+                    if (MATSET & kMedium) {
+                        if (!FRESH) { const P3 o3 = ld_p3<2>(&S.o[i]); org = mk3(o3.x, o3.y, o3.z); }
+                        st.ray.o = org;
+                    }
                     done = path_on_closest<INTEG, typename ShadeTab<LDSTAB>::type, MATSET>(sc, tab, st, hit, found, mk3(d4.x, d4.y, d4.z));
                     if (!done) {
                         survive = true;
@@ -260,6 +266,7 @@ __global__ __launch_bounds__(kB) void NORI_WF_FINISH_KERNEL(DevScene sc, WfBuf b
                 if (found) hit.mesh = f2u(sc.shade_tris[(size_t) hit.tri * kShadeQuads].w);
                 PathState st;
                 vertex_unpack(st, fl, L, T, rng_state, ((uint64_t) (bt.s_first + ((sidx % per_tile) >> 8)) << 1u) | 1u);
+                if (MATSET & kMedium) st.ray.o = ray.o;
                 fin = path_on_closest<INTEG, MATSET>(sc, st, hit, found, ray.d);
                 L.x = st.L.x; L.y = st.L.y; L.z = st.L.z;
                 if (!fin) {

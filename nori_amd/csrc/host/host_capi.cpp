@@ -79,6 +79,15 @@ int nori_host_environment(const nori_host_root *root, nori_env_desc *out) {
     return 1;
 }
 
+int nori_host_medium(const nori_host_root *root, nori_medium_desc *out) {
+    if (!root || !out || root->root->getClassType() != NoriObject::EScene) return NORI_ERR_INVALID_ARGUMENT;
+    std::memset(out, 0, sizeof(*out));
+    const Medium *m = static_cast<const Scene *>(root->root.get())->getMedium();
+    if (!m) return 0;
+    m->fillMedium(*out);
+    return 1;
+}
+
 int nori_host_test_info_get(const nori_host_root *root, nori_host_test_info *out) {
     if (!root || !out || root->root->getClassType() != NoriObject::ETest) return NORI_ERR_INVALID_ARGUMENT;
     std::memset(out, 0, sizeof(*out));

@@ -97,6 +97,22 @@ public:
     virtual void fillEnvironment(nori_env_desc &) const {}
 };
 
+/* ------------------------------------------------- Medium, PhaseFunction */
+/* The reference names both classes in its enum (include/nori/object.h:25,27) and ships neither; these are this project's
+   (include/nori_hip.h, "Homogeneous participating medium").  <phase type="isotropic"/> or <phase type="hg"> with a float "g". */
+class PhaseFunction : public NoriObject {
+public:
+    EClassType getClassType() const { return EPhaseFunction; }
+    virtual float getAsymmetry() const = 0;      /* Henyey-Greenstein g; 0: isotropic */
+};
+
+/* <medium type="homogeneous"> as a child of <scene>: it fills all space */
+class Medium : public NoriObject {
+public:
+    EClassType getClassType() const { return EMedium; }
+    virtual void fillMedium(nori_medium_desc &) const = 0;      /* the record nori_hip_set_medium takes */
+};
+
 /* ---------------------------------------------------------------- Sampler */
 /* include/nori/sampler.h:56-95 */
 class Sampler : public NoriObject {
@@ -239,6 +255,7 @@ public:
     Integrator *getIntegrator() { return m_integrator; }
     const Camera *getCamera() const { return m_camera; }
     const Emitter *getEnvironment() const { return m_environment; }
+    const Medium *getMedium() const { return m_medium; }
     const Sampler *getSampler() const { return m_sampler; }
     Sampler *getSampler() { return m_sampler; }
     const std::vector<Mesh *> &getMeshes() const { return m_meshes; }
@@ -266,6 +283,7 @@ private:
     Sampler *m_sampler = nullptr;
     Camera *m_camera = nullptr;
     Emitter *m_environment = nullptr;      /* the environment map, if any: applied after every upload (device(), deviceGroup()) */
+    Medium *m_medium = nullptr;            /* the medium, if any: likewise */
     Accel *m_accel = nullptr;
     mutable nori_scene_desc m_desc;
     mutable std::vector<nori_mesh_desc> m_meshDescs;

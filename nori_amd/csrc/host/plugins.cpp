@@ -274,6 +274,65 @@ private:
 };
 NORI_REGISTER_CLASS(EnvironmentMap, "envmap");
 
+/* ================================================= Medium, PhaseFunction */
+/* <phase type="isotropic"/> */
+class IsotropicPhase : public PhaseFunction {
+public:
+    IsotropicPhase(const PropertyList &) {}
+    float getAsymmetry() const { return 0.0f; }
+    std::string toString() const { return "Isotropic[]"; }
+};
+NORI_REGISTER_CLASS(IsotropicPhase, "isotropic");
+
+/* <phase type="hg"><float name="g" value="..."/></phase>: Henyey-Greenstein, g > 0 scatters forward; |g| <= 0.99 */
+class HenyeyGreensteinPhase : public PhaseFunction {
+public:
+    HenyeyGreensteinPhase(const PropertyList &propList) {
+        m_g = propList.getFloat("g", 0.0f);
+        if (!(std::fabs(m_g) <= 0.99f)) throw NoriException("phase hg: g must lie in [-0.99, 0.99] (got %f)", m_g);
+    }
+    float getAsymmetry() const { return m_g; }
+    std::string toString() const { return format("HenyeyGreenstein[g = %f]", m_g); }
+private:
+    float m_g;
+};
+NORI_REGISTER_CLASS(HenyeyGreensteinPhase, "hg");
+
+/* <medium type="homogeneous"> as a child of <scene> (include/nori_hip.h, "Homogeneous participating medium"): it fills all space.
+ *   sigmaT    float, the grey extinction, 1e-4 .. 1e4
+ *   albedo    color, the single-scattering albedo, each component 0 .. 1 (default 1)
+ *   <phase>   an optional child: isotropic (the default) or hg */
+class HomogeneousMedium : public Medium {
+public:
+    HomogeneousMedium(const PropertyList &propList) {
+        m_sigmaT = propList.getFloat("sigmaT");
+        if (!(std::isfinite(m_sigmaT) && m_sigmaT >= 1e-4f && m_sigmaT <= 1e4f)) throw NoriException("medium: sigmaT must lie in [1e-4, 1e4] (got %f)", m_sigmaT);
+        m_albedo = propList.getColor("albedo", Color3f(1.0f));
+        for (int c = 0; c < 3; ++c)
+            if (!(std::isfinite(m_albedo[c]) && m_albedo[c] >= 0.0f && m_albedo[c] <= 1.0f)) throw NoriException("medium: every albedo component must lie in [0, 1]");
+    }
+    ~HomogeneousMedium() { delete m_phase; }
+    void addChild(NoriObject *obj) {
+        if (obj->getClassType() != EPhaseFunction) throw NoriException("Medium::addChild(<%s>) is not supported!", classTypeName(obj->getClassType()));
+        if (m_phase) throw NoriException("There can only be one phase function per medium!");
+        m_phase = static_cast<PhaseFunction *>(obj);
+    }
+    void fillMedium(nori_medium_desc &d) const {
+        d.sigma_t = m_sigmaT;
+        for (int c = 0; c < 3; ++c) d.albedo[c] = m_albedo[c];
+        d.g = m_phase ? m_phase->getAsymmetry() : 0.0f;
+    }
+    std::string toString() const {
+        return format("HomogeneousMedium[\n  sigmaT = %f,\n  albedo = %s,\n  phase = %s\n]", m_sigmaT, m_albedo.toString(),
+                      m_phase ? indent(m_phase->toString()) : std::string("Isotropic[]"));
+    }
+private:
+    float m_sigmaT;
+    Color3f m_albedo;
+    PhaseFunction *m_phase = nullptr;
+};
+NORI_REGISTER_CLASS(HomogeneousMedium, "homogeneous");
+
 /* ================================================================ Sampler */
 /* src/independent.cpp:21-67.  The pcg32 arithmetic runs on the device
    (nori_hip_pcg32_floats_at); the host keeps the stream key, how many numbers of the stream it has
@@ -591,7 +650,7 @@ bool Scene::s_verbose = true;
 Scene::Scene(const PropertyList &) { m_accel = new Accel(this); std::memset(&m_desc, 0, sizeof(m_desc)); }
 
 Scene::~Scene() {
-    delete m_accel; delete m_sampler; delete m_camera; delete m_integrator; delete m_environment;
+    delete m_accel; delete m_sampler; delete m_camera; delete m_integrator; delete m_environment; delete m_medium;
     for (Mesh *m : m_meshes) delete m;       /* the reference leaks these (src/scene.cpp:20-25) */
 }
 
@@ -604,6 +663,14 @@ void Scene::activate() {
         m_integrator->fill(id);
         if (id.type == NORI_INTEGRATOR_WHITTED)
             throw NoriException("An environment map cannot be rendered by the whitted integrator (use path_mats, path_ems or path_mis)");
+    }
+    if (m_medium) {           /* what nori_hip_set_medium would refuse, likewise */
+        nori_integrator_desc id;
+        m_integrator->fill(id);
+        if (id.type != NORI_INTEGRATOR_PATH_MATS && id.type != NORI_INTEGRATOR_PATH_EMS && id.type != NORI_INTEGRATOR_PATH_MIS)
+            throw NoriException("A medium is rendered by path_mats, path_ems and path_mis only");
+        if (m_environment)
+            throw NoriException("A medium that fills all space cannot be lit by an environment map (its transmittance to infinity is zero)");
     }
     if (!m_sampler)
         m_sampler = static_cast<Sampler *>(NoriObjectFactory::createInstance("independent", PropertyList()));
@@ -628,6 +695,10 @@ void Scene::addChild(NoriObject *obj) {
             throw NoriException("Scene::addChild(): emitters must be children of a <mesh> (area lights); only <emitter type=\"envmap\"> belongs to the scene");
         if (m_environment) throw NoriException("There can only be one environment map per scene!");
         m_environment = static_cast<Emitter *>(obj);
+        break;
+    case EMedium:
+        if (m_medium) throw NoriException("There can only be one medium per scene!");
+        m_medium = static_cast<Medium *>(obj);
         break;
     case ESampler:
         if (m_sampler) throw NoriException("There can only be one sampler per scene!");
@@ -699,6 +770,11 @@ Device &Scene::device() const {
             m_environment->fillEnvironment(env);
             d->check(nori_hip_set_environment(d->ctx(), &env), "nori_hip_set_environment");
         }
+        if (m_medium) {
+            nori_medium_desc md;
+            m_medium->fillMedium(md);
+            d->check(nori_hip_set_medium(d->ctx(), &md), "nori_hip_set_medium");
+        }
         m_device = std::move(d);
     }
     return *m_device;
@@ -714,6 +790,11 @@ DeviceGroup &Scene::deviceGroup(int n) const {
             nori_env_desc env;
             m_environment->fillEnvironment(env);
             g->check(nori_hip_group_set_environment(g->group(), &env), "nori_hip_group_set_environment");
+        }
+        if (m_medium) {
+            nori_medium_desc md;
+            m_medium->fillMedium(md);
+            g->check(nori_hip_group_set_medium(g->group(), &md), "nori_hip_group_set_medium");
         }
         m_group = std::move(g);
     }

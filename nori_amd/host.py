@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _capi as capi
 from ._capi import NoriError
-from .scene import Bsdf, Camera, Environment, Integrator, Mesh, RFilter, Scene, Texture
+from .scene import Bsdf, Camera, Environment, Integrator, Medium, Mesh, RFilter, Scene, Texture
 
 DEFER_TESTS, QUIET = 1, 2
 _P = C.c_void_p
@@ -34,6 +34,7 @@ HOST_PROTOTYPES = {
     "nori_host_scene_desc": (C.c_int, [_P, C.POINTER(capi.SceneDesc)]),
     "nori_host_lens": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "nori_host_environment": (C.c_int, [_P, C.POINTER(capi.EnvDesc)]),
+    "nori_host_medium": (C.c_int, [_P, C.POINTER(capi.MediumDesc)]),
     "nori_host_test_info_get": (C.c_int, [_P, C.POINTER(TestInfo)]),
     "nori_host_test_bsdf": (C.c_int, [_P, C.c_uint32, C.POINTER(capi.BsdfDesc)]),
     "nori_host_test_scene_desc": (C.c_int, [_P, C.c_uint32, C.POINTER(capi.SceneDesc)]),
@@ -155,7 +156,16 @@ class HostRoot:
         sc = scene_from_desc(d)
         sc.camera.aperture_radius, sc.camera.focus_distance = self.lens()      # (not part of the description: Renderer.upload applies them)
         sc.environment = self.environment()                                    # (nor is this)
+        sc.medium = self.medium()                                              # (nor this)
         return sc
+
+    def medium(self):
+        """The scene's medium (<medium type="homogeneous">) as a scene.Medium; None without one."""
+        d = capi.MediumDesc()
+        rc = self._lib.nori_host_medium(self._h, C.byref(d))
+        if rc < 0:
+            raise NoriError("root is not a <scene>")
+        return Medium(float(d.sigma_t), tuple(float(x) for x in d.albedo), float(d.g)) if rc == 1 else None
 
     def environment(self):
         """The scene's environment map (<emitter type="envmap">) as a scene.Environment, the texels copied; None without one."""

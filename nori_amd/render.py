@@ -101,9 +101,59 @@ class Renderer:
             self.set_lens(scene.camera.aperture_radius, scene.camera.focus_distance)
         if getattr(scene, "environment", None) is not None:      # (the upload itself resets the context to none)
             self.set_environment(scene.environment)
+        if getattr(scene, "medium", None) is not None:
+            self.set_medium(scene.medium)
         if build:
             self.build_accel(builder)
         return self
+
+    # ------------------------------------------------------------ homogeneous medium
+    def set_medium(self, medium):
+        """The homogeneous medium of the uploaded scene (include/nori_hip.h, "Homogeneous participating medium"): a scene.Medium, or
+        None for no medium -- the kernels and the bits of a context that never had one.  Holds until the next upload."""
+        d = medium.desc() if medium is not None else None
+        self._check(self._lib.nori_hip_set_medium(self._h, C.byref(d) if d is not None else None), "set_medium")
+        return self
+
+    @property
+    def medium(self):
+        """The medium set, as the context stores it (g is 0 where |g| < 1e-3): a scene.Medium, or None."""
+        from .scene import Medium
+        d = capi.MediumDesc()
+        rc = self._lib.nori_hip_get_medium(self._h, C.byref(d))
+        if rc < 0:
+            self._check(rc, "get_medium")
+        return Medium(float(d.sigma_t), tuple(float(x) for x in d.albedo), float(d.g)) if rc == 1 else None
+
+    def medium_distance(self, xi):
+        """Free-flight distances -log(1 - xi) / sigma_t of the (n,) samples, as Li draws them."""
+        x = np.ascontiguousarray(xi, dtype=np.float32).reshape(-1)
+        s = np.zeros(x.shape[0], np.float32)
+        self._check(self._lib.nori_hip_medium_distance(self._h, ptr(x), x.shape[0], ptr(s)), "medium_distance")
+        return s
+
+    def medium_transmittance(self, dist):
+        """Tr(dist) = exp(-sigma_t dist) of the (n,) distances."""
+        x = np.ascontiguousarray(dist, dtype=np.float32).reshape(-1)
+        t = np.zeros(x.shape[0], np.float32)
+        self._check(self._lib.nori_hip_medium_transmittance(self._h, ptr(x), x.shape[0], ptr(t)), "medium_transmittance")
+        return t
+
+    def phase_eval(self, d, wo):
+        """The phase density HG(dot(d, wo)) of (n, 3) directions of travel d and scattered directions wo."""
+        a, b = _f32(d, 3), _f32(wo, 3)
+        assert a.shape == b.shape
+        p = np.zeros(a.shape[0], np.float32)
+        self._check(self._lib.nori_hip_phase_eval(self._h, ptr(a), ptr(b), a.shape[0], ptr(p)), "phase_eval")
+        return p
+
+    def phase_sample(self, d, xi):
+        """(wo (n, 3), pdf (n,)): the phase sample the (n, 2) numbers xi select for the (n, 3) directions of travel d."""
+        a, x = _f32(d, 3), _f32(xi, 2)
+        assert a.shape[0] == x.shape[0]
+        wo, p = np.zeros((a.shape[0], 3), np.float32), np.zeros(a.shape[0], np.float32)
+        self._check(self._lib.nori_hip_phase_sample(self._h, ptr(a), ptr(x), a.shape[0], ptr(wo), ptr(p)), "phase_sample")
+        return wo, p
 
     # ------------------------------------------------------------ environment map
     def set_environment(self, env):
@@ -936,6 +986,14 @@ class DeviceGroup:
             self.set_lens(scene.camera.aperture_radius, scene.camera.focus_distance)
         if getattr(scene, "environment", None) is not None:
             self.set_environment(scene.environment)
+        if getattr(scene, "medium", None) is not None:
+            self.set_medium(scene.medium)
+        return self
+
+    def set_medium(self, medium):
+        """Renderer.set_medium on every device of the group."""
+        d = medium.desc() if medium is not None else None
+        self._check(self._lib.nori_hip_group_set_medium(self._h, C.byref(d) if d is not None else None), "group_set_medium")
         return self
 
     def set_environment(self, env):

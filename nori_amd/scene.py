@@ -101,6 +101,22 @@ class Environment:
 
 
 @dataclass
+class Medium:
+    """The homogeneous participating medium of a scene (nori_medium_desc in include/nori_hip.h, which states every operation): it
+    fills all space.  Not part of nori_scene_desc: Renderer.upload applies it with nori_hip_set_medium."""
+    sigma_t: float                          # grey extinction, 1e-4 .. 1e4
+    albedo: tuple = (1.0, 1.0, 1.0)         # single-scattering albedo, each 0 .. 1
+    g: float = 0.0                          # Henyey-Greenstein asymmetry, |g| <= 0.99; > 0 scatters forward
+
+    def desc(self) -> capi.MediumDesc:
+        d = capi.MediumDesc()
+        d.sigma_t = float(self.sigma_t)
+        d.albedo[:] = [float(x) for x in self.albedo]
+        d.g = float(self.g)
+        return d
+
+
+@dataclass
 class Mesh:
     positions: np.ndarray                   # (nV, 3) float32, world space
     indices: np.ndarray                     # (nF, 3) uint32
@@ -159,6 +175,7 @@ class Scene:
     sample_count: int = 1
     textures: List[Texture] = field(default_factory=list)
     environment: Optional[Environment] = None      # path_mats / path_ems / path_mis; applied after the upload
+    medium: Optional[Medium] = None                # likewise; never together with an environment
 
     # ------------------------------------------------------------ C view
     def c_desc(self):
@@ -254,6 +271,8 @@ class Scene:
             meta["textures"] = [dict(t.params(), texels=t.texels is not None) for t in self.textures]
         if self.environment is not None:      # (scenes without one: the file of before, key for key)
             meta["environment"] = {"scale": list(map(float, self.environment.scale))}
+        if self.medium is not None:           # (likewise)
+            meta["medium"] = {"sigma_t": float(self.medium.sigma_t), "albedo": list(map(float, self.medium.albedo)), "g": float(self.medium.g)}
         if base is not None:
             assert self.environment is None, "a variant fixture (base=...) stores no arrays: save a scene with an environment whole"
             assert not self.textures, "a variant fixture (base=...) stores no arrays: save a textured scene whole"
@@ -318,4 +337,6 @@ class Scene:
             sc.textures.append(Texture(texels=z[f"t{k}_texels"] if has_texels else None, **p))
         if "environment" in meta:
             sc.environment = Environment(z["env_texels"], tuple(meta["environment"]["scale"]), z["env_to_world"])
+        if "medium" in meta:
+            sc.medium = Medium(meta["medium"]["sigma_t"], tuple(meta["medium"]["albedo"]), meta["medium"]["g"])
         return sc
