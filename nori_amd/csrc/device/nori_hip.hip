@@ -96,8 +96,10 @@ __global__ __launch_bounds__(kBlock, NORI_RENDER_MIN_WAVES) void render_kernel(D
     const uint32_t sel = blockIdx.x / args.n_chunks, chunk = blockIdx.x % args.n_chunks;
     const uint32_t tile_id = args.tile_list ? args.tile_list[sel] : args.tile_rem + sel * args.tile_mod;
     const int x0 = (int) (tile_id % args.tiles_x) * kTile, y0 = (int) (tile_id / args.tiles_x) * kTile;
-    const uint32_t s0 = args.spp_begin + chunk * args.chunk_spp;
-    const uint32_t s1 = min(s0 + args.chunk_spp, args.spp_begin + args.spp_count);
+    /* the chunk's samples RELATIVE to spp_begin, [r0, r1): spp_begin + spp_count itself may be 2^32 (the frame of sample 2^32 - 1) */
+    const uint32_t r0 = min(chunk * args.chunk_spp, args.spp_count);
+    const uint32_t r1 = r0 + min(args.chunk_spp, args.spp_count - r0);
+    const uint32_t s0 = args.spp_begin + r0;
 
     /* wave w covers the 8x8 quad (w&1, w>>1) of the tile; lane l the pixel (l&7, l>>3) */
     const int wave = tid >> 6, lane = tid & 63;
@@ -164,7 +166,7 @@ __global__ __launch_bounds__(kBlock, NORI_RENDER_MIN_WAVES) void render_kernel(D
                 }
             }
             if (gen) {
-                if (s >= s1) {
+                if (s - args.spp_begin >= r1) {
                     finished = true;
                 } else {
                     /* renderBlock, src/main.cpp:41-46: jitter, aperture draw, sampleRay */

@@ -3,7 +3,10 @@ triangle soups and spheres with random BSDFs, one or more area lights, every int
 ragged frame sizes, LBVH or SAH trees, small path budgets that force batching and wf_finish early or
 never -- must give the same ray counts and the same frame (float summation order aside).
 
-    python tests/fuzz_engines.py [--seconds 60] [--seed 0]
+    python tests/fuzz_engines.py [--seconds 60] [--seed 0] [--features]
+
+--features also draws what tests/path_fuzz.py draws -- albedo textures with and without texcoords, a thin lens, and under the path
+integrators a fog or a sky; the comparison is the same.
 
 `tests/test_gpu_wavefront.py::test_fuzz_engines_short` runs a few rounds of it."""
 from __future__ import annotations
@@ -35,7 +38,28 @@ def random_bsdf(rng):
     return Bsdf("microfacet", tuple(rng.uniform(0.05, 0.6, 3)), float(rng.uniform(0.05, 0.6)))
 
 
-def random_scene(rng):
+def add_features(rng, sc):
+    """tests/path_fuzz.py's texture, texcoord, lens, fog and sky draws, on a scene of random_scene"""
+    from tests import path_fuzz as pf
+    k = 0
+    for m in sc.meshes:
+        if m.bsdf.type == "diffuse" and m.radiance is None and rng.random() < 0.5:
+            sc.textures.append(pf.draw_texture(rng))
+            m.albedo_texture = len(sc.textures) - 1
+            if k % 2 == 0:
+                m.texcoords = pf.draw_texcoords(rng, m, tuple(m.positions.astype(np.float64).mean(axis=0)) if m.name == "sphere" else None)
+            k += 1
+    lens = pf.draw_lens(rng)
+    if lens is not None:
+        sc.camera.aperture_radius, sc.camera.focus_distance = lens
+    if sc.integrator.type.startswith("path_"):
+        kind = pf.KINDS[int(rng.integers(3))]
+        sc.medium = pf.draw_medium(rng, closed=False) if kind == "fog" else None
+        sc.environment = pf.draw_environment(rng) if kind == "sky" else None
+    return sc
+
+
+def random_scene(rng, features=False):
     meshes = []
     for _ in range(rng.integers(1, 4)):
         if rng.random() < 0.5:
@@ -54,12 +78,13 @@ def random_scene(rng):
     cam = Camera(w, h, float(rng.uniform(25, 70)), to_world=scenes.lookat(tuple(rng.uniform(-1, 1, 3) + [0, 0.5, 4]), (0, 0, 0), (0, 1, 0)))
     integ = Integrator(INTEGRATORS[int(rng.integers(0, len(INTEGRATORS)))])
     integ.position, integ.energy = (0.3, 1.5, 0.5), (30.0, 25.0, 20.0)
-    return Scene(meshes, cam, RFilter(FILTERS[int(rng.integers(0, 4))]), integ, int(rng.integers(1, 9)))
+    sc = Scene(meshes, cam, RFilter(FILTERS[int(rng.integers(0, 4))]), integ, int(rng.integers(1, 9)))
+    return add_features(rng, sc) if features else sc
 
 
-def one_round(seed, renderer_cls, oracle=False):
+def one_round(seed, renderer_cls, oracle=False, features=False):
     rng = np.random.default_rng(seed)
-    sc = random_scene(rng)
+    sc = random_scene(rng, features)
     builder = int(rng.integers(0, 3))      # host SAH, device radix tree, device PLOC
     mk = renderer_cls(0).upload(sc, builder=builder)
     wf = renderer_cls(0).upload(sc, builder=builder)
@@ -109,11 +134,13 @@ def main():
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--oracle", action="store_true", help="also compare every frame with the CPU oracle's render")
+    ap.add_argument("--features", action="store_true", help="also draw textures, texcoords, a lens, a fog or a sky (tests/path_fuzz.py's draws)")
     a = ap.parse_args()
+    assert not (a.oracle and a.features), "the CPU oracle renders no texture, lens, fog or sky"
     from nori_amd.render import Renderer
     t0, n, rays = time.time(), 0, 0
     while time.time() - t0 < a.seconds:
-        rays += one_round(a.seed + n, Renderer, a.oracle)
+        rays += one_round(a.seed + n, Renderer, a.oracle, a.features)
         n += 1
     print(f"fuzz_engines: {n} rounds from seed {a.seed}, {rays} rays, both engines agree" + (" with each other and with the oracle" if a.oracle else ""))
 

@@ -96,6 +96,10 @@ SHOWN_ON = {"roulette_without_eta": ("fog_box", "sky_box"), "emitter_hit_pdf_wit
             "no_nee_at_microfacet": ("sky_box", "fog_r3", "sky_r4"), "geometric_normal_on_emitters": ("fog_box", "sky_box")}
 
 
+# the counters these cases are about: path_ref.EVENTS without the ones that tests/path_fuzz.py's rounds are there to reach
+COUNTERS = tuple(k for k in pr.EVENTS if k not in pr.FUZZ_EVENTS)
+
+
 def applicable(sc, integrator):
     """The counters of path_ref.EVENTS whose branch exists in the scene under the integrator, from what the scene holds: a fog or
     a sky, the BSDF types, area lights, vertex normals on surfaces and on lights, a texture.  tests/test_path_ref_cpu.py requires
@@ -120,8 +124,8 @@ def applicable(sc, integrator):
         "pick_light_normals": ems and any(m.normals is not None and m.radiance is not None for m in sc.meshes),
         "shadow_tr_surface": ems and fog and area,
     }
-    assert set(has) == set(pr.EVENTS)
-    return tuple(k for k in pr.EVENTS if has[k])
+    assert set(has) == set(COUNTERS)
+    return tuple(k for k in COUNTERS if has[k])
 
 
 @functools.lru_cache(maxsize=None)
@@ -133,12 +137,17 @@ def scene_of(case, integrator):
 def inputs(case):
     """(idx, seq, floats [n, 4 + CAP * 8], rays): the streams pcg32(pixel index, S) and the camera rays of sample S of every pixel --
     the oracle's camera, or tests/lens_ref.py's thin lens"""
-    sc = scene_of(case, "path_mis")
-    idx = np.arange(N_PATHS, dtype=np.uint64)
-    seq = np.full(idx.shape, S, np.uint64)
+    return inputs_of(scene_of(case, "path_mis"), S)
+
+
+def inputs_of(sc, s):
+    """inputs() of any scene's frame at sample index s (tests/path_fuzz.py's rounds too)"""
+    w, h = sc.camera.width, sc.camera.height
+    idx = np.arange(w * h, dtype=np.uint64)
+    seq = np.full(idx.shape, s, np.uint64)
     f = Oracle.pcg32_floats(idx, seq, 4 + CAP * pr.DRAWS_PER_VERTEX)
-    ps, ap = lr.camera_samples(W, H, S)
-    assert ps.tobytes() == np.stack([(idx % W).astype(F) + f[:, 0], (idx // W).astype(F) + f[:, 1]], 1).tobytes() and ap.tobytes() == f[:, 2:4].tobytes()
+    ps, ap = lr.camera_samples(w, h, s)
+    assert ps.tobytes() == np.stack([(idx % w).astype(F) + f[:, 0], (idx // w).astype(F) + f[:, 1]], 1).tobytes() and ap.tobytes() == f[:, 2:4].tobytes()
     cam = sc.camera
     if cam.aperture_radius > 0:
         rays = lr.as_rays(lr.lens_rays(sc, ps, ap, cam.aperture_radius, cam.focus_distance))
@@ -157,9 +166,13 @@ def oracle_of(case):
 def walk(case, integrator, from_start=False, mutate=None):
     """path_ref.walk on the case's inputs: the frame's paths (the stream after the camera sample's four draws), or with
     from_start Li of the same rays with the stream drawn from the start, as nori_hip_li draws it"""
-    sc = scene_of(case, integrator)
-    _, _, f, rays = inputs(case)
-    return pr.walk(oracle_of(case), sc, integrator, rays, f if from_start else f[:, 4:], medium=sc.medium, env=sc.environment, max_vertices=CAP, mutate=mutate)
+    return walk_scene(scene_of(case, integrator), oracle_of(case), inputs(case), integrator, from_start, mutate)
+
+
+def walk_scene(sc, oracle, inp, integrator, from_start=False, mutate=None):
+    """path_ref.walk of any scene on its inputs_of()"""
+    _, _, f, rays = inp
+    return pr.walk(oracle, sc, integrator, rays, f if from_start else f[:, 4:], medium=sc.medium, env=sc.environment, max_vertices=CAP, mutate=mutate)
 
 
 @functools.lru_cache(maxsize=None)

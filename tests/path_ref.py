@@ -34,7 +34,15 @@ EVENTS = (
     "hit_vertex_normals",              # surface vertices on meshes with vertex normals
     "pick_light_normals",              # picks of a light with vertex normals
     "shadow_tr_surface",               # shadow rays of a surface vertex whose Ld was multiplied by the transmittance
+    # the branches tests/path_fuzz.py's rounds reach (FUZZ_EVENTS); the hand-made cases of tests/path_cases.py reach none but,
+    # by accident of their geometry, emitter_hit_backface
+    "textured_vertex_mesh_uv",         # textured vertices on meshes with texcoords: hit_uv interpolates the corners' (rt_trace.h)
+    "nee_env_only",                    # emitter samples where the environment is the only light (n_emitters = 0)
+    "emitter_hit_backface",            # emitter hits with dot(ns, -d) <= 0: no emission
+    "emitter_vertex_reflects",         # a path continues from a light whose BSDF reflects (albedo > 0)
+    "medium_vertex_lens",              # medium vertices of frames seen through a thin lens
 )
+FUZZ_EVENTS = EVENTS[-5:]
 MUTATIONS = {      # name -> the counter that is non-zero on every path the departure can change
     "roulette_without_eta": "rr_eta",
     "emitter_hit_pdf_without_env_in_count": "emitter_hit_env_count",
@@ -44,7 +52,16 @@ MUTATIONS = {      # name -> the counter that is non-zero on every path the depa
     "texture_not_in_nee": "nee_textured",
     "no_nee_at_microfacet": ("nee_microfacet_area", "nee_microfacet_env"),
     "geometric_normal_on_emitters": "pick_light_normals",
+    # FUZZ_MUTATIONS: shown on tests/path_fuzz.py's rounds
+    "barycentric_uv_on_meshes_with_texcoords": "textured_vertex_mesh_uv",      # hit_uv returns (u, v) as if the mesh had no texcoords
+    "texcoords_of_rotated_corners": "textured_vertex_mesh_uv",                 # ... interpolates the uv of the vertices (1, 2, 0)
+    "env_pick_divides_by_n_emitters": "nee_env_only",      # the light count without the + 1 where the environment is the only
+                                                           # light: 0, sample_direct's early-out, no emitter sample
+    "emission_from_both_sides": "emitter_hit_backface",
+    "paths_end_at_emitters": "emitter_vertex_reflects",
 }
+FUZZ_MUTATIONS = tuple(MUTATIONS)[-5:]
+UV_MUTATIONS = FUZZ_MUTATIONS[:2]
 
 def emitter_tables(scene):
     """Emu(scene).emitter_tables(): the tables scene_prep.cpp makes on the host"""
@@ -99,6 +116,7 @@ def walk(backend, scene, integrator, rays, floats, medium=None, env=None, max_ve
     assert medium is None or env is None
     EMS, MIS = integrator != "path_mats", integrator == "path_mis"
     MEDIUM, ENV = medium is not None, env is not None
+    LENS = scene.camera.aperture_radius > 0
     n = rays.shape[0]
     floats = np.ascontiguousarray(floats, F)
     assert floats.shape[0] == n and floats.shape[1] >= max_vertices * DRAWS_PER_VERTEX
@@ -115,6 +133,12 @@ def walk(backend, scene, integrator, rays, floats, medium=None, env=None, max_ve
     textured = np.array([m.albedo_texture is not None for m in meshes])
     assert not (textured & (btype != 0)).any()
     has_normals = np.array([m.normals is not None for m in meshes])
+    has_uv = np.array([m.texcoords is not None for m in meshes])
+    reflects = np.array([m.radiance is not None and any(x > 0 for x in m.bsdf.albedo) for m in meshes])
+    plain = None      # (the two uv departures need the hit's barycentrics: the same scene without texcoords answers with them)
+    if mutate in UV_MUTATIONS:
+        import dataclasses
+        plain = Oracle(dataclasses.replace(scene, meshes=[dataclasses.replace(m, texcoords=None) for m in meshes]), use_bvh=True)
     albedo_of = np.array([m.bsdf.albedo for m in meshes], F)
     rad_of = np.array([m.radiance if m.radiance is not None else (0, 0, 0) for m in meshes], F)
     is_em = np.array([m.radiance is not None for m in meshes])
@@ -139,6 +163,11 @@ def walk(backend, scene, integrator, rays, floats, medium=None, env=None, max_ve
         q = np.zeros(idx.shape[0], rays.dtype)
         q["o"], q["d"], q["mint"], q["maxt"] = org, dirs, lo, hi
         return backend.intersect(q, shadow=shadow)
+
+    def rays_of(g):
+        q = np.zeros(g.shape[0], rays.dtype)
+        q["o"], q["d"], q["mint"], q["maxt"] = o[g], d[g], mint[g], maxt[g]
+        return q
 
     def roulette(idx, Tn):
         """Russian roulette of the paths idx (all at depth >= 3) on their throughputs Tn: (kept, Tn / p)"""
@@ -172,7 +201,9 @@ def walk(backend, scene, integrator, rays, floats, medium=None, env=None, max_ve
         ok = np.zeros(k, bool)
         dirs, hi, Ld = np.zeros((k, 3), F), np.zeros(k, F), np.zeros((k, 3), F)
         pdf_em, pdf_bsdf = np.zeros(k, F), np.zeros(k, F)
-        if nL == 0:
+        if ENV and nE == 0:
+            events["nee_env_only"][idx] += 1
+        if nL == 0 or (mutate == "env_pick_divides_by_n_emitters" and nE == 0):
             return ok, dirs, hi, Ld, pdf_em, pdf_bsdf
         ei = np.minimum((xs[:, 0] * F(nL)).astype(np.int64), nL - 1)
         pdfPick = one / F(nL)
@@ -297,6 +328,8 @@ def walk(backend, scene, integrator, rays, floats, medium=None, env=None, max_ve
             events["medium_vertex_prev_discrete"][ga[was_discrete]] += 1
             events["medium_vertex_after_specular"][ga[was_discrete & (depth[ga] > 0)]] += 1
             events["medium_vertex_inside_glass"][ga[inside[ga]]] += 1
+            if LENS:
+                events["medium_vertex_lens"][ga] += 1
             Tn[a] = Tn[a] * medium.albedo[None, :]
             black = _is_zero(Tn[a])
             ends[a[black]] = True
@@ -337,7 +370,19 @@ def walk(backend, scene, integrator, rays, floats, medium=None, env=None, max_ve
             alb = albedo_of[mesh].copy()
             for mi in np.unique(mesh[textured[mesh]]):                     # the albedo of bsdf_eval / pdf / sample and sample_direct alike
                 sel = mesh == mi
-                alb[sel] = texture_ref.lookup(scene.textures[meshes[int(mi)].albedo_texture], its["uv"][b][sel])
+                uv = its["uv"][b][sel]
+                if has_uv[mi]:                                             # the oracle's interpolation is hit_uv's: oracle_scene.h, Accel::fill
+                    events["textured_vertex_mesh_uv"][gb[sel]] += 1
+                    if plain is not None:
+                        bary = plain.intersect(rays_of(idx[b][sel]), shadow=False)
+                        assert (bary["mesh"] == mi).all() and (bary["tri"] == its["tri"][b][sel]).all()
+                        u, v = bary["uv"][:, 0], bary["uv"][:, 1]
+                        uv = np.stack([u, v], 1)
+                        if mutate == "texcoords_of_rotated_corners":
+                            tc = meshes[int(mi)].texcoords[meshes[int(mi)].indices[its["tri"][b][sel]].astype(np.int64)][:, [1, 2, 0]]
+                            b0 = one - (u + v)
+                            uv = ((b0[:, None] * tc[:, 0] + u[:, None] * tc[:, 1]) + v[:, None] * tc[:, 2]).astype(F)
+                alb[sel] = texture_ref.lookup(scene.textures[meshes[int(mi)].albedo_texture], uv)
             # weight of emission reached by BSDF / phase sampling
             wMat = np.ones(b.size, F)
             weighted = (prev[gb] != 2) if EMS else np.zeros(b.size, bool)
@@ -354,10 +399,13 @@ def walk(backend, scene, integrator, rays, floats, medium=None, env=None, max_ve
                 if ENV:
                     events["emitter_hit_env_count"][gb[sel & front]] += 1
             add = em & (wMat > 0)
-            le = np.where(front[:, None], rad_of[mesh], zero).astype(F)
+            events["emitter_hit_backface"][gb[em & ~front]] += 1
+            le = rad_of[mesh] if mutate == "emission_from_both_sides" else np.where(front[:, None], rad_of[mesh], zero).astype(F)
             Lb = L[gb]
             Lb[add] = (Lb[add] + (Tn[b][add] * le[add]) * wMat[add][:, None]).astype(F)
             L[gb] = Lb
+            if mutate == "paths_end_at_emitters":
+                ends[b[em]] = True
             rr = b[depth[gb] >= 3]
             if rr.size:
                 keep, Tn[rr] = roulette(idx[rr], Tn[rr])
@@ -404,6 +452,7 @@ def walk(backend, scene, integrator, rays, floats, medium=None, env=None, max_ve
                 inside[idx[g2]] = (bt[k2] == 2) & (wo[k2][:, 2] < 0)
                 pm[g2] = np.where(meas[k2] != 2, pdf[k2], zero) if MIS else zero
                 depth[idx[g2]] += 1
+                events["emitter_vertex_reflects"][idx[g2][reflects[mesh[k2]]]] += 1
 
         # ---------------- the shadow rays, then what goes on
         sh = np.nonzero(shadow & ~ends)[0]

@@ -115,11 +115,11 @@ def test_inputs_of_the_gpu_cases_reach_every_branch(case, integrator):
     assert lc.fits(lc.table_counts(sc)) == (case not in pc.OUTSIDE_LDS)
     L, nc, ns, ev = pc.reference(case, integrator)
     assert L.shape == (pc.N_PATHS, 3) and (L > 0).any()
-    counts = {k: int((ev[k] > 0).sum()) for k in pr.EVENTS}
+    counts = {k: int((ev[k] > 0).sum()) for k in pc.COUNTERS}
     li_longest = int(pc.reference(case, integrator, True)[3]["vertices"].max())      # the stream drawn from the start (nori_hip_li) walks other paths
     print(case, integrator, "longest path", int(ev["vertices"].max()), "/", li_longest, counts)
     wanted = pc.applicable(sc, integrator)
-    for k in pr.EVENTS:
+    for k in pc.COUNTERS:
         if k in wanted:
             assert counts[k] >= 8, (case, integrator, k, counts[k])      # paths, not events: at least 8 PATHS take the branch
         else:
@@ -131,8 +131,8 @@ def test_every_branch_is_reached_outside_the_lds_too():
     """what the two boxes reach between them is every counter; the LDSTAB = false scenes have no glass, texture or light with
     normals, and reach every other one"""
     reach = lambda cases: {k for c in cases for i in PATHS for k in pc.applicable(pc.scene_of(c, i), i)}
-    assert reach(["fog_box", "sky_box"]) == set(pr.EVENTS)
-    assert reach(pc.OUTSIDE_LDS) == set(pr.EVENTS) - {"rr_eta", "medium_vertex_after_specular", "medium_vertex_inside_glass", "env_escape_after_discrete",
+    assert reach(["fog_box", "sky_box"]) == set(pc.COUNTERS) == set(pr.EVENTS) - set(pr.FUZZ_EVENTS)
+    assert reach(pc.OUTSIDE_LDS) == set(pc.COUNTERS) - {"rr_eta", "medium_vertex_after_specular", "medium_vertex_inside_glass", "env_escape_after_discrete",
                                                      "nee_textured", "pick_light_normals"}
 
 
@@ -148,7 +148,7 @@ def test_every_kind_of_case_is_there():
 
 
 # ------------------------------------------------------------------ 4. a wrong branch changes these paths
-@pytest.mark.parametrize("name", list(pr.MUTATIONS))
+@pytest.mark.parametrize("name", list(pc.SHOWN_ON))      # (path_ref.FUZZ_MUTATIONS: tests/test_path_fuzz_cpu.py, on its rounds)
 def test_every_departure_changes_paths_the_gpu_renders(name):
     counters = pr.MUTATIONS[name]
     counters = (counters,) if isinstance(counters, str) else counters
