@@ -581,6 +581,7 @@ int nori_hip_upload_scene(nori_hip_ctx *ctx, const nori_scene_desc *scene) {
     env_release(ctx);      /* the environment map is set after an upload and lasts until the next (nori_hip_set_environment) */
     memset(&ctx->dev.medium, 0, sizeof(ctx->dev.medium));      /* and so is the medium (nori_hip_set_medium) */
     ctx->have_scene = ctx->have_accel = false;
+    wavefront_invalidate(ctx->wf);      /* what the engine keeps per (tree, camera) */
     std::string err = prepare_scene(*scene, ctx->host);
     if (!err.empty()) { ctx->error = err; return NORI_ERR_INVALID_ARGUMENT; }
     HostScene &h = ctx->host;
@@ -630,6 +631,7 @@ int nori_hip_build_accel(nori_hip_ctx *ctx, int builder) {
     DeviceGuard g(ctx->device);
     free_pool(ctx->allocs_accel);
     ctx->have_accel = false;
+    wavefront_invalidate(ctx->wf);
     int layout = ctx->accel_layout;
     if (const char *e = getenv("NORI_HIP_ACCEL_LAYOUT")) layout = std::string(e) == "bvh4q" ? 1 : (std::string(e) == "bvh2" ? 0 : -1);
     /* measured (wf_extend, BVH2 walked as 32-B records by the hand-written loop against wide nodes): 328 k triangles 9.7 against
@@ -885,6 +887,7 @@ int nori_hip_set_lens(nori_hip_ctx *ctx, float radius, float focus_distance) {
     }
     ctx->host.camera.lens_radius = ctx->dev.camera.lens_radius = radius;
     ctx->host.camera.focus_distance = ctx->dev.camera.focus_distance = focus_distance;
+    wavefront_invalidate(ctx->wf);
     return NORI_OK;
 }
 

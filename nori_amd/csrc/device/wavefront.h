@@ -69,6 +69,30 @@ std::string wavefront_trace(WfEngine &engine, const DevScene &sc, int stack_dept
 /* node records of the LDS image (rt_top.h) that fit next to wf_extend's traversal stacks, per node layout */
 int wf_top_capacity(bool wide_nodes, bool records_32b, bool deeper_than_lds_stack);
 
+/* The first pass by per-tile candidate lists (wavefront_first.hip, first_lists.h): a pinhole camera, a BVH2 tree, no counting.
+   The engine keeps the lists of its context; they are rebuilt when what they were built for changes (the tree, the camera record,
+   the frame's tiles, the filter border, K) and dropped by wavefront_invalidate, which the context calls on every upload and
+   acceleration-structure build.  A call with more than one of its selected tiles in sixteen on overflow keeps the old kernel
+   (wavefront_render: a ray of an overflow tile costs several times the old kernel's average, a ray of a list tile a third).  Read once per process:
+   NORI_HIP_WF_FIRST=0 the old first pass, =2 the lists whatever share of the tiles overflows (tests, A/B); NORI_HIP_WF_FIRST_K=n the
+   cap of a list (0: every tile overflows); NORI_HIP_WF_FIRST_REBUILD=1 the lists are built again in every render call. */
+struct WfFirstLists;
+struct WfFirstInfo { uint32_t K = 0, list_tiles = 0, overflow_tiles = 0; float build_ms = 0.0f; bool rebuilt = false; };
+WfFirstLists *wf_first_create();
+void wf_first_destroy(WfFirstLists *);
+void wf_first_invalidate(WfFirstLists *);
+bool wf_first_applies(const DevScene &sc, bool count_traversal);
+bool wf_first_forced();
+/* builds the lists if they are not the ones of (sc, frame); synchronises `stream` when it builds.  Returns "" or an error message. */
+std::string wf_first_prepare(WfFirstLists &lists, const DevScene &sc, uint32_t tiles_x, uint32_t tiles_y, int32_t tile_w, void *stream, WfFirstInfo &info);
+/* list / overflow tiles among the tiles a call selects (the progression tile_rem + k tile_mod; a render by tile list, whose list lies in
+   device memory, gets the whole frame's counts) */
+void wf_first_selected(const WfFirstLists &lists, uint32_t tile_mod, uint32_t tile_rem, uint32_t n_sel, bool by_list, uint32_t &list_tiles, uint32_t &overflow_tiles);
+/* in the place of wf_extend<..., kFreshOnly, ...>: wf_buf, batch as for wf_env_launch_shade; grid: workgroups of 256 threads, at most
+   as many lanes as the traversal-stack spill buffer was sized for */
+void wf_first_launch_extend(const WfFirstLists &lists, const DevScene &sc, const void *wf_buf, int cur, const void *batch, int grid, void *stream);
+void wavefront_invalidate(WfEngine *engine);
+
 /* -DNORI_COUNT_EXCURSIONS builds: adds this translation unit's excursion counters (rt_types.h) to out[4], optionally
    resetting them; false in the product build */
 bool wavefront_excursions(unsigned long long out[4], bool reset);

@@ -691,6 +691,7 @@ struct WfEngine {
     hipEvent_t tail_events[3] = {nullptr, nullptr, nullptr};      /* the side copy is filled / the tail is done / the tail is about to be dispatched */
     hipStream_t tail_stream = nullptr;
     int tail_stream_cus = 0;
+    WfFirstLists *first = nullptr;      /* the per-tile candidate lists of the first pass (wavefront_first.hip), made when first needed */
 };
 
 /* The stream of the overlapped tails: it owns the CUs of the first `cus` mask bits.  The driver hands bit i of a queue's mask to
@@ -784,8 +785,11 @@ void wavefront_destroy(WfEngine *e) {
     for (hipEvent_t &ev : e->tail_events) if (ev) { (void) hipEventDestroy(ev); ev = nullptr; }
     park_stream(e->device, kStreamTail, e->tail_stream_cus, e->tail_stream);
     e->tail.release();
+    wf_first_destroy(e->first);
     delete e;
 }
+
+void wavefront_invalidate(WfEngine *e) { if (e) wf_first_invalidate(e->first); }
 
 bool wavefront_excursions(unsigned long long out[4], bool reset) {
 #if defined(NORI_COUNT_EXCURSIONS)
@@ -1080,6 +1084,28 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
     bool use_finish = true;
     if (const char *e = getenv("NORI_HIP_WF_FINISH")) use_finish = atoi(e) != 0;
     const bool force_mixed = getenv("NORI_HIP_WF_FORCE_MIXED") != nullptr && atoi(getenv("NORI_HIP_WF_FORCE_MIXED")) != 0;      /* A/B, tests: every pass but the first as a pass that may hold new paths (both wf_extend launches, the kMixed wf_shade) */
+    /* the new paths of a pass by per-tile candidate lists (wavefront_first.hip) where they apply: a pinhole, a BVH2 tree, no counting */
+    bool first_lists = wf_first_applies(sc, L.count_traversal);
+    if (first_lists) {
+        if (!eng.first) eng.first = wf_first_create();
+        WfFirstInfo fi;
+        err = wf_first_prepare(*eng.first, sc, L.tiles_x, L.tiles_y, L.tile_w, s, fi);
+        if (!err.empty()) return err;
+        /* Worth it while few tiles overflow: a ray of an overflow tile walks the tree by the generic traverse<>, at several times the
+           old kernel's cost per ray (headline: 4.4 times its average, a list tile 0.36).  Measured, share of the call's tiles on overflow:
+           headline 2 % -2.0 ms; the pa5 table scene 7.6 % +12 ms (1 %) of its 1120; the AO icosphere 54 % +1.2 ms of 12.9
+           (DESIGN.md section 7).  The lists run up to one tile in sixteen. */
+        uint32_t sel_list = 0, sel_overflow = 0;      /* among the tiles this call renders */
+        wf_first_selected(*eng.first, L.tile_mod, L.tile_rem, L.n_sel_tiles, L.tile_list != nullptr, sel_list, sel_overflow);
+        if (!wf_first_forced() && (size_t) sel_overflow * 16 > (size_t) sel_list + sel_overflow) {
+            first_lists = false;
+            if (census) fprintf(stderr, "[wavefront first pass] walk (wf_extend): %u of %u tiles overflow at K %u\n", sel_overflow, sel_list + sel_overflow, fi.K);
+        } else
+        if (census) fprintf(stderr, "[wavefront first pass] lists: K %u, %u list tiles, %u overflow tiles, build %.3f ms (%s)\n", fi.K, fi.list_tiles, fi.overflow_tiles,
+                            fi.build_ms, fi.rebuilt ? "built in this call" : "kept");
+    } else if (census) fprintf(stderr, "[wavefront first pass] walk (wf_extend)\n");
+    /* workgroups of 256 threads on the lanes the persistent grid of the first pass would take (and the spill buffer is sized for) */
+    const int first_grid = extend_grid_first * (kExtendBlockBvh2 / kB);
 
     KernelTimer timer(L.time_kernels);
     unsigned long long *d_census = nullptr;
@@ -1137,7 +1163,8 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
                 }
                 if (P.mode != kStoredOnly) {
                     timer.begin(KC_TRACE, P.extend_stream);
-                    launch_extend_dyn(sc, P.b, P.cur, thresholds, lds_stack, spill, L.count_traversal, kFreshOnly, extend_grid_first, P.bt, P.extend_stream);
+                    if (first_lists) wf_first_launch_extend(*eng.first, sc, &P.b, P.cur, &P.bt, first_grid, P.extend_stream);
+                    else launch_extend_dyn(sc, P.b, P.cur, thresholds, lds_stack, spill, L.count_traversal, kFreshOnly, extend_grid_first, P.bt, P.extend_stream);
                     WF_TRY(hipGetLastError());
                     timer.end(P.extend_stream);
                     stats.n_launches++;
