@@ -33,12 +33,12 @@ struct WfStats {
     size_t state_bytes = 0;
     float class_ms[4] = {0.0f, 0.0f, 0.0f, 0.0f};      /* KernelClass: trace, shade, film, overlapped tails */
     uint32_t class_launches[4] = {0, 0, 0, 0};
-    uint32_t trace_cus = 0;                      /* CUs wf_extend's stream owned (fewer than the device has: shading, or the tails of earlier batches, ran beside it) */
+    uint32_t trace_cus = 0;                      /* CUs wf_extend's persistent grid fills: the device's */
     uint32_t tail_cus = 0;                       /* CUs set aside for the tails of the batches (0: tails run on the bulk's stream) */
     uint32_t record = 0;                         /* NORI_WF_RECORD_*: the path record this call's kernels used (wf_records.h) */
 };
 
-/* The engine's per-context resources (path-state pool, pipe streams / events, device properties);
+/* The engine's per-context resources (path-state pool, streams / events, device properties);
  * created on the context's device, owned by nori_hip_ctx, never shared between contexts. */
 struct WfEngine;
 WfEngine *wavefront_create();

@@ -455,12 +455,6 @@ __global__ __launch_bounds__(kB) void wf_tail_copy(WfBuf b, int cur, WfState D, 
 
 /* ----------------------------------------------------------- host driver */
 constexpr int kShadeGridMax = 4096;
-/* CUs of the shading side when the device is split (wavefront_render), and the job size from which it is */
-#ifndef NORI_SPLIT_CUS_DEFAULT
-#define NORI_SPLIT_CUS_DEFAULT 0
-#endif
-constexpr int kSplitCusDefault = NORI_SPLIT_CUS_DEFAULT;
-constexpr size_t kSplitMinSamples = (size_t) 1 << 24;
 
 int shade_grid(size_t paths) { return (int) std::min<size_t>(kShadeGridMax, std::max<size_t>(64, (paths + kShadeChunk - 1) / kShadeChunk)); }
 
@@ -473,11 +467,11 @@ size_t state_capacity(size_t paths) {
 
 struct Pool {
     std::vector<void *> allocs;
-    size_t capacity = 0;       /* records per copy, all pipes */
+    size_t capacity = 0;       /* records per copy */
     size_t bytes = 0;
     WfBuf buf;
     uint32_t *h_ctr = nullptr; /* pinned */
-    int *spill = nullptr;      /* traversal-stack overflow of wf_extend, one column per lane and pipe */
+    int *spill = nullptr;      /* traversal-stack overflow of wf_extend, one column per lane */
     size_t spill_ints = 0;
     void release() {
         for (void *p : allocs) (void) hipFree(p);
@@ -512,9 +506,9 @@ std::string ensure_pool(Pool &pool, size_t records) {
         A(st[k].sidx, records); A(st[k].rng, records);
     }
     A(hit, records);
-    A(ctr, (size_t) 2 * C_COUNT); A(stats, (size_t) 2 * S_COUNT);
+    A(ctr, (size_t) C_COUNT); A(stats, (size_t) S_COUNT);
 #undef A
-    WF_TRY(hipHostMalloc((void **) &pool.h_ctr, 2 * C_COUNT * sizeof(uint32_t)));
+    WF_TRY(hipHostMalloc((void **) &pool.h_ctr, C_COUNT * sizeof(uint32_t)));
     pool.capacity = records;
     return std::string();
 }
@@ -636,7 +630,7 @@ int wf_top_capacity(bool wide_nodes, bool records_32b, bool deeper_than_lds_stac
 }
 
 
-/* Everything a context keeps between render calls: the path-state pool, the pipes' streams and
+/* Everything a context keeps between render calls: the path-state pool, its streams and
    events, what the device offers.  One per nori_hip_ctx (= per GPU); nothing here is process-global,
    so contexts on different devices, or two contexts on one device, never share or free each
    other's buffers. */
@@ -647,7 +641,7 @@ int wf_top_capacity(bool wide_nodes, bool records_32b, bool deeper_than_lds_stac
    array on them, destroy them, fill the device, ask for more).  The same program survives when the streams are kept.  The
    out-of-memory retry of render_impl depends on that failure being an error code, and a process renders through many contexts.
    Parked streams are idle (synchronised before they are parked) and belong to nobody; one mutex guards the list. */
-enum StreamKind { kStreamPlain = 0, kStreamSplitExtend = 1, kStreamSplitShade = 2, kStreamTail = 3 };
+enum StreamKind { kStreamPlain = 0, kStreamTail = 1 };
 struct ParkedStream { int device, kind, cus; hipStream_t stream; };
 std::mutex g_parked_mutex;
 std::vector<ParkedStream> g_parked;
@@ -674,15 +668,10 @@ hipStream_t unpark_stream(int device, int kind, int cus) {
 struct WfEngine {
     int device = 0;                 /* the context's device: parked streams are handed out per device */
     Pool pool;
-    hipStream_t streams[2] = {nullptr, nullptr};
-    hipEvent_t events[3] = {nullptr, nullptr, nullptr};
+    hipStream_t stream = nullptr;   /* tail overlap: the bulk's (non-blocking; otherwise the bulk runs on the caller's stream) */
+    hipEvent_t events[2] = {nullptr, nullptr};      /* tail overlap: the caller's work is queued / the bulk is done */
     int n_cus = 0;                  /* hipDeviceProp_t::multiProcessorCount of the context's device */
-    /* the CUs of the device shared out between the two kinds of work (wavefront_render, "split"): [0] the stream of the
-       traversal kernels, on all CUs but split_cus, [1] the stream of the shading and film kernels, on split_cus CUs */
-    hipStream_t split_streams[2] = {nullptr, nullptr};
-    int split_cus = 0;
-    hipEvent_t pipe_events[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};      /* per pipe: its traversal / its shading is done */
-    /* tail overlap: the side copy of a batch's last live paths (wf_tail_copy), walked by wf_finish on split_streams[1] */
+    /* tail overlap: the side copy of a batch's last live paths (wf_tail_copy), walked by wf_finish on tail_stream */
     struct TailSide {
         WfState st; uint32_t *ctr = nullptr; size_t capacity = 0; std::vector<void *> allocs;
         int *spill = nullptr; size_t spill_ints = 0;
@@ -733,39 +722,6 @@ std::string ensure_tail_side(WfEngine &e, size_t records, size_t spill_ints) {
     return std::string();
 }
 
-/* Two streams whose kernels run on disjoint sets of CUs (hipExtStreamCreateWithCUMask).  The shading side gets `cus` CUs (a
-   multiple of 8) as whole ROWS of eight consecutive mask bits, rows spread evenly over the mask: the driver hands bit i of a
-   queue's mask to XCD i mod 8 and walks an XCD's shader engines with the bits it gets, so a row is one CU of every XCD and the
-   two sets are even over XCDs and shader engines.  Returns false (and leaves the engine unsplit) if the runtime refuses. */
-bool ensure_split_streams(WfEngine &e, int cus) {
-    if (e.split_cus == cus && e.split_streams[0] && e.split_streams[1]) return true;
-    park_stream(e.device, kStreamSplitExtend, e.split_cus, e.split_streams[0]); park_stream(e.device, kStreamSplitShade, e.split_cus, e.split_streams[1]);
-    e.split_cus = 0;
-    {      /* a parked pair of this device and share */
-        hipStream_t a = unpark_stream(e.device, kStreamSplitExtend, cus), b = a ? unpark_stream(e.device, kStreamSplitShade, cus) : nullptr;
-        if (a && b) { e.split_streams[0] = a; e.split_streams[1] = b; e.split_cus = cus; return true; }
-        if (a) park_stream(e.device, kStreamSplitExtend, cus, a);
-    }
-    const int rows_total = e.n_cus / 8, rows = cus / 8;
-    if (rows < 1 || rows >= rows_total) return false;
-    const uint32_t words = (uint32_t) ((e.n_cus + 31) / 32);
-    std::vector<uint32_t> shade(words, 0u), extend(words, 0u);
-    std::vector<char> taken((size_t) rows_total, 0);
-    for (int j = 0; j < rows; ++j) taken[(size_t) ((long long) j * rows_total / rows)] = 1;
-    for (int i = 0; i < e.n_cus; ++i) {
-        const bool in_row = i / 8 < rows_total && taken[(size_t) (i / 8)];
-        (in_row ? shade : extend)[(size_t) i / 32] |= 1u << (i % 32);
-    }
-    if (hipExtStreamCreateWithCUMask(&e.split_streams[0], words, extend.data()) != hipSuccess ||
-        hipExtStreamCreateWithCUMask(&e.split_streams[1], words, shade.data()) != hipSuccess) {
-        (void) hipGetLastError();
-        for (hipStream_t &st : e.split_streams) if (st) { (void) hipStreamDestroy(st); st = nullptr; }      /* (never ran a kernel) */
-        return false;
-    }
-    e.split_cus = cus;
-    return true;
-}
-
 WfEngine *wavefront_create() {
     WfEngine *e = new WfEngine();
     int dev = 0; hipDeviceProp_t prop;
@@ -778,10 +734,8 @@ WfEngine *wavefront_create() {
 void wavefront_destroy(WfEngine *e) {
     if (!e) return;
     e->pool.release();
-    for (hipStream_t &st : e->streams) park_stream(e->device, kStreamPlain, 0, st);
-    park_stream(e->device, kStreamSplitExtend, e->split_cus, e->split_streams[0]); park_stream(e->device, kStreamSplitShade, e->split_cus, e->split_streams[1]);
+    park_stream(e->device, kStreamPlain, 0, e->stream);
     for (hipEvent_t &ev : e->events) if (ev) { (void) hipEventDestroy(ev); ev = nullptr; }
-    for (auto &pe : e->pipe_events) for (hipEvent_t &ev : pe) if (ev) { (void) hipEventDestroy(ev); ev = nullptr; }
     for (hipEvent_t &ev : e->tail_events) if (ev) { (void) hipEventDestroy(ev); ev = nullptr; }
     park_stream(e->device, kStreamTail, e->tail_stream_cus, e->tail_stream);
     e->tail.release();
@@ -812,40 +766,6 @@ size_t wavefront_held_bytes(const WfEngine *e, const FilmStore &film) {
     return (e ? e->pool.bytes : 0) + film.capacity * (sizeof(f2) + sizeof(P3));
 }
 
-/* A pipe works through its own list of batches with its own slice of the state pool, on its own
-   HIP stream.  Two pipes interleave so that one pipe's wf_shade (HBM-bound) overlaps the other
-   pipe's wf_extend (VALU-bound); the persistent extend grid is sized to leave room for it. */
-struct Pipe {
-    hipStream_t stream = nullptr;            /* shading, film, counters: everything but ... */
-    hipStream_t extend_stream = nullptr;     /* ... the traversal kernels (the same stream unless the CUs are split) */
-    hipEvent_t ev_extend = nullptr, ev_shade = nullptr;      /* split: the hand-over between the two streams */
-    WfBuf b;
-    FilmStore film;
-    uint32_t *h_ctr = nullptr;
-    uint32_t tile_lo = 0, tile_hi = 0;      /* selected-tile ordinals owned by this pipe */
-    uint32_t tiles_b = 0, spp_b = 0;        /* batch geometry */
-    uint32_t t0 = 0, s0 = 0;                /* next batch */
-    bool active = false, finished = false;
-    int mode = kFreshOnly;                   /* of the next pass's kernels */
-    uint32_t batch_samples = 0;              /* camera samples of the current batch */
-    uint32_t batch_rounds = 0;               /* host-loop rounds spent on the current batch */
-    WfBatch bt;
-    int cur = 0;
-};
-
-static WfBuf slice(const WfBuf &b, size_t off, size_t records, int k) {
-    WfBuf v = b;
-    for (int c = 0; c < 2; ++c) {
-        WfState &t = v.st[c];
-        t.o += off; t.dA += off; t.dB += off; t.T_eta += off; t.L_pdf += off; t.Ld += off;
-        t.sidx += off; t.rng += off;
-    }
-    v.hit += off;
-    v.ctr += (size_t) k * C_COUNT; v.stats += (size_t) k * S_COUNT;
-    v.capacity = (uint32_t) records;
-    return v;
-}
-
 /* How a context launches wf_extend on a scene's tree -- what launch_extend_dyn and WfBatch are handed, the knobs of the environment
    included -- decided in ONE place for the two callers: a render's passes (wavefront_render) and the rays a caller brings itself
    (wavefront_trace), so that the second is held to the launch the first makes. */
@@ -858,11 +778,10 @@ struct ExtendPlan {
     int inner_repeat = 24;
     uint32_t batch_flags = 0;       /* kBatchNoAsmLoop | kBatchCountQ */
     int finish_paths = 0, finish_grid = 0;      /* fewer live paths than this: wf_finish ends the batch; its grid */
-    size_t spill_ints_per_pipe = 0; /* of pool.spill, allocated here (0: no walk leaves the LDS stack) */
+    size_t spill_ints = 0;          /* of pool.spill, allocated here (0: no walk leaves the LDS stack) */
 };
 
-static std::string plan_extend(const WfEngine &eng, Pool &g_pool, const DevScene &sc, int stack_depth, bool count_traversal, int n_pipes, int split_cus, ExtendPlan &plan) {
-    const bool split = split_cus > 0;
+static std::string plan_extend(const WfEngine &eng, Pool &g_pool, const DevScene &sc, int stack_depth, bool count_traversal, ExtendPlan &plan) {
     int refill = 32;
     if (const char *e = getenv("NORI_HIP_WF_REFILL")) refill = std::min(64, std::max(1, atoi(e)));
     /* lanes at a leaf before a triangle step runs: 16 on BVH2 trees; 8 on wide trees, whose node steps are twice as long and whose
@@ -874,8 +793,6 @@ static std::string plan_extend(const WfEngine &eng, Pool &g_pool, const DevScene
     if (const char *e = getenv("NORI_HIP_WF_STATIC")) static_per_wave = std::min(4095, std::max(0, atoi(e)));
     if (const char *e = getenv("NORI_HIP_WF_DYNDIV")) dyn_div = std::min(15, std::max(1, atoi(e)));
     plan.thresholds = refill | (leaf_th << 8) | (static_per_wave << 16) | (dyn_div << 28);
-    /* persistent extend grid: fill the CUs, but with two pipes leave half of the wave slots to
-       the other pipe's kernels */
     /* traversal stack: what the tree needs, at most `lds_stack` entries of it in LDS */
     /* 16 entries in LDS, deeper walks spill to HBM: a stack of 24 entries costs three of the eight workgroups per CU, and walks
        rarely hold more than 16 deferred subtrees however deep the tree (measured, trace ms at 16 / 24 entries: table scene,
@@ -913,25 +830,23 @@ static std::string plan_extend(const WfEngine &eng, Pool &g_pool, const DevScene
        128 spp at 4 / 5 / 6 / 7 / 8 workgroups per CU: 65.7 / 57.8 / 53.9 / 53.6 / 54.2 -- the last two with the first pass still on the
        same grid; how many records the LDS image holds does not matter there: 113, 40 or none, profiles/r4_07_c5_occupancy.txt.) */
     if (sc.wide) per_cu = std::min(per_cu, kExtendWgsWide);
-    if (n_pipes > 1 && !split) per_cu = std::max(1, per_cu / 2);
     if (const char *e = getenv("NORI_HIP_WF_EXTEND_WGS_PER_CU")) per_cu = std::min(2048 / extend_block, std::max(1, atoi(e)));
-    const int extend_cus = eng.n_cus - split_cus;      /* the persistent grid fills the CUs its stream owns (a tail beside it: some of its
-                                                          workgroups start when the tail's have left -- handing them their first chunk in
-                                                          the order they start instead of by position was measured and is no faster,
-                                                          profiles/r5_11_tail_overlap_c4.txt) */
+    const int extend_cus = eng.n_cus;      /* the persistent grid fills the device (a tail beside it: some of its workgroups start when
+                                              the tail's have left -- handing them their first chunk in the order they start instead of
+                                              by position was measured and is no faster, profiles/r5_11_tail_overlap_c4.txt) */
     plan.extend_cus = extend_cus;
     plan.grid_first = extend_cus * (sc.wide ? std::min(per_cu, kExtendWgsWideFirst) : per_cu);
     plan.grid = extend_cus * per_cu;
-    plan.spill_ints_per_pipe = 0;
+    plan.spill_ints = 0;
     if (stack_depth > 16) {      /* wf_finish keeps 16 entries in LDS */
-        const size_t per_pipe_ints = (size_t) (stack_depth - 16) * std::max(plan.grid * extend_block, finish_grid * kB), ints = per_pipe_ints * n_pipes;
+        const size_t ints = (size_t) (stack_depth - 16) * std::max(plan.grid * extend_block, finish_grid * kB);
         if (g_pool.spill_ints < ints) {
             if (g_pool.spill) (void) hipFree(g_pool.spill);
             g_pool.spill = nullptr; g_pool.spill_ints = 0;
             WF_TRY(hipMalloc((void **) &g_pool.spill, ints * sizeof(int)));
             g_pool.spill_ints = ints;
         }
-        plan.spill_ints_per_pipe = per_pipe_ints;
+        plan.spill_ints = ints;
     }
     /* node steps repeat in a tight loop while >= 24 lanes of the wave are at inner nodes -- without the refill test, the leaf
        vote and the rest of the trip's bookkeeping, which cost as much as the node step itself (measured, wf_extend: Cornell
@@ -948,122 +863,80 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
                              float *d_rgbw, void *stream_, WfStats &stats) {
     hipStream_t s = (hipStream_t) stream_;
     Pool &g_pool = eng.pool;
-    hipStream_t (&g_streams)[2] = eng.streams;
-    hipEvent_t (&g_events)[3] = eng.events;
     stats = WfStats();
     if (L.n_sel_tiles == 0 || L.spp_count == 0) return std::string();
 
-    int n_pipes = 1;        /* measured: 2 pipes are 5 % slower (wf_extend wants all 8 waves/SIMD); NORI_HIP_WF_PIPES=2 to try */
-    if (const char *e = getenv("NORI_HIP_WF_PIPES")) n_pipes = std::min(2, std::max(1, atoi(e)));
-    /* Split: the device's CUs shared out between the two kinds of work.  wf_extend is bound by the vector ALU (its time follows
-       the number of CUs it runs on), wf_shade and the film by the memory system (theirs does not, down to a few dozen CUs): run
-       one after the other, each leaves idle what the other needs.  Two pipes -- each half of the tiles -- with the traversal
-       kernels of both on a stream that owns all CUs but `split_cus`, shading and film on a stream that owns those: while one
-       pipe's paths are traversed the other pipe's are shaded, both kernels at their full occupancy on their own CUs (two pipes
-       that SHARE every CU halve each kernel's waves per SIMD and gain nothing: profiles/r4_05).  NORI_HIP_WF_SPLIT_CUS: CUs of
-       the shading side (a multiple of 8; 0: no split). */
-    int split_cus = kSplitCusDefault;
-    if (const char *e = getenv("NORI_HIP_WF_SPLIT_CUS")) split_cus = std::max(0, atoi(e)) & ~7;
-    if (getenv("NORI_HIP_WF_PIPES")) split_cus = 0;
-    size_t split_min = kSplitMinSamples;
-    if (const char *e = getenv("NORI_HIP_WF_SPLIT_MIN")) split_min = (size_t) std::max(0ll, atoll(e));
-    if (L.n_sel_tiles < 2 || (size_t) L.n_sel_tiles * 256 * L.spp_count < split_min || L.film_reference || L.count_traversal) split_cus = 0;
-    if (L.n_sel_tiles < 2 || (size_t) L.n_sel_tiles * 256 * L.spp_count < ((size_t) 1 << 22)) n_pipes = 1;
-    if (split_cus >= eng.n_cus) split_cus = 0;
-    if (split_cus > 0 && ensure_split_streams(eng, split_cus)) n_pipes = 2; else split_cus = 0;
-    const bool split = split_cus > 0;
-
-    /* per pipe: a batch = a range of the pipe's tiles x as many samples per pixel as the film's sample store may hold
+    /* a batch = a range of the call's tiles x as many samples per pixel as the film's sample store may hold
        (max_samples); the paths in flight -- the state pool -- are bounded separately (max_paths): a batch bigger than the pool
        starts its samples pass by pass, in the slots its finished paths leave (regeneration, WfBatch::pool) */
-    const size_t budget = std::min<size_t>(std::max<size_t>(std::max(L.max_samples, L.max_paths) / n_pipes, 256), (size_t) 1 << 31);
-    Pipe pipes[2];
-    size_t need[2] = {0, 0};
-    for (int k = 0; k < n_pipes; ++k) {
-        Pipe &P = pipes[k];
-        P.tile_lo = (uint32_t) ((uint64_t) L.n_sel_tiles * k / n_pipes);
-        P.tile_hi = (uint32_t) ((uint64_t) L.n_sel_tiles * (k + 1) / n_pipes);
-        const uint32_t nt = P.tile_hi - P.tile_lo;
-        if ((size_t) nt * 256 > budget) { P.tiles_b = (uint32_t) (budget / 256); P.spp_b = 1; }
-        else { P.tiles_b = nt; P.spp_b = (uint32_t) std::min<size_t>(L.spp_count, std::max<size_t>(1, budget / ((size_t) nt * 256))); }
-        need[k] = (size_t) P.tiles_b * 256 * P.spp_b;
-        P.t0 = P.tile_lo; P.s0 = 0;
-    }
+    const size_t budget = std::min<size_t>(std::max<size_t>(std::max(L.max_samples, L.max_paths), 256), (size_t) 1 << 31);
+    uint32_t tiles_b = L.n_sel_tiles, spp_b = 1;      /* batch geometry */
+    if ((size_t) L.n_sel_tiles * 256 > budget) tiles_b = (uint32_t) (budget / 256);
+    else spp_b = (uint32_t) std::min<size_t>(L.spp_count, std::max<size_t>(1, budget / ((size_t) L.n_sel_tiles * 256)));
+    const size_t batch_max = (size_t) tiles_b * 256 * spp_b;      /* camera samples of a batch */
     /* Tail overlap.  A batch ends with wf_finish walking its last <= finish_paths live paths to their ends: a launch as long as the
        batch's longest path (inside glass ~1300 vertices, one after the other) during which the device is next to idle -- 12 % of
        the pa5 table scene at 2048^2 x 1024 spp.  In a call of two or more batches the tail of batch k runs BESIDE the kernels of
        batch k + 1 instead: its records are copied out of the state pool (wf_tail_copy) and the persistent form of wf_finish walks
-       them on a stream that owns `tail_cus` CUs (ensure_tail_stream) while the bulk of the next batch goes on on the caller's
+       them on a stream that owns `tail_cus` CUs (ensure_tail_stream) while the bulk of the next batch goes on on the engine's
        stream -- on the CUs the tail leaves it while it lasts (46 ms on 32 CUs), on all of them afterwards; the film gather of
        batch k -- which needs the tail's radiance -- is queued behind the bulk of batch k + 1.  The sample store has two halves,
        one per batch in flight.  Gathers stay in batch order, so the frame keeps its bits.  NORI_HIP_WF_TAIL_CUS (a multiple of 8;
        0: tails on the bulk's stream, as a call of one batch runs them). */
     int tail_cus = 32;
     if (const char *e = getenv("NORI_HIP_WF_TAIL_CUS")) tail_cus = std::max(0, atoi(e)) & ~7;
-    {
-        const Pipe &P0 = pipes[0];
-        const uint64_t nt0 = P0.tile_hi - P0.tile_lo;
-        const uint64_t batches = ((nt0 + P0.tiles_b - 1) / std::max(1u, P0.tiles_b)) * ((L.spp_count + P0.spp_b - 1) / std::max(1u, P0.spp_b));
-        if (n_pipes != 1 || split || batches < 2 || L.film_reference || L.count_traversal || tail_cus >= eng.n_cus) tail_cus = 0;
-        if (getenv("NORI_HIP_WF_FINISH") && atoi(getenv("NORI_HIP_WF_FINISH")) == 0) tail_cus = 0;
-        if (tail_cus > 0 && !ensure_tail_stream(eng, tail_cus)) tail_cus = 0;
-    }
+    const uint64_t batches = (uint64_t) ((L.n_sel_tiles + tiles_b - 1) / tiles_b) * ((L.spp_count + spp_b - 1) / spp_b);
+    if (batches < 2 || L.film_reference || L.count_traversal || tail_cus >= eng.n_cus) tail_cus = 0;
+    if (getenv("NORI_HIP_WF_FINISH") && atoi(getenv("NORI_HIP_WF_FINISH")) == 0) tail_cus = 0;
+    if (tail_cus > 0 && !ensure_tail_stream(eng, tail_cus)) tail_cus = 0;
     const bool overlap = tail_cus > 0;
-    if (L.film_reference && (n_pipes != 1 || pipes[0].tiles_b != L.n_sel_tiles || pipes[0].spp_b != L.spp_count || L.tile_mod != 1))
+    if (L.film_reference && (tiles_b != L.n_sel_tiles || spp_b != L.spp_count || L.tile_mod != 1))
         return "wavefront: film_order = reference needs the whole frame in one batch (tile_mod 1, wavefront_samples >= pixels x samples)";
-    const size_t per_pipe = std::max(need[0], need[1]);         /* camera samples of a batch */
-    size_t pool_paths = std::min(per_pipe, std::max<size_t>(L.max_paths / n_pipes, 256));      /* paths in flight */
-    if (const char *e = getenv("NORI_HIP_WF_POOL")) pool_paths = std::min(per_pipe, (size_t) std::max(256ll, atoll(e)));      /* experiments */
-    const size_t records = state_capacity(pool_paths);          /* per pipe, per state copy */
+    size_t pool_paths = std::min(batch_max, std::max<size_t>(L.max_paths, 256));      /* paths in flight */
+    if (const char *e = getenv("NORI_HIP_WF_POOL")) pool_paths = std::min(batch_max, (size_t) std::max(256ll, atoll(e)));      /* experiments */
+    const size_t records = state_capacity(pool_paths);          /* per state copy */
     const int sh_grid = shade_grid(pool_paths);
     if (records >= ((size_t) 1 << 30)) return "wavefront: wavefront_paths too large (state index is 30 bits)";
-    std::string err = ensure_pool(g_pool, records * n_pipes);
+    std::string err = ensure_pool(g_pool, records);
     if (!err.empty()) return err;
     FilmStore film;
-    err = film_prepare(film_store, per_pipe * (overlap ? 2 : n_pipes), L.n_sel_tiles, L.tile_w, s, film);
+    err = film_prepare(film_store, batch_max * (overlap ? 2 : 1), L.n_sel_tiles, L.tile_w, s, film);
     if (!err.empty()) return err;
     const bool moments = L.d_m2 != nullptr && L.moments != nullptr;
     if (moments) {
         err = film_moments_prepare(*L.moments, film, L.n_sel_tiles, L.tile_w, s);
         if (!err.empty()) return err;
     }
-    stats.state_bytes = g_pool.bytes + per_pipe * (overlap ? 2 : n_pipes) * (sizeof(f2) + sizeof(P3));
-    WF_TRY(hipMemsetAsync(g_pool.buf.stats, 0, 2 * S_COUNT * sizeof(unsigned long long), s));
+    stats.state_bytes = g_pool.bytes + batch_max * (overlap ? 2 : 1) * (sizeof(f2) + sizeof(P3));
+    WF_TRY(hipMemsetAsync(g_pool.buf.stats, 0, S_COUNT * sizeof(unsigned long long), s));
 
-    for (int k = 0; k < 3; ++k) if (!g_events[k]) WF_TRY(hipEventCreateWithFlags(&g_events[k], hipEventDisableTiming));
-    for (int k = 0; k < n_pipes; ++k) {
-        Pipe &P = pipes[k];
-        if (split) {
-            P.extend_stream = eng.split_streams[0]; P.stream = eng.split_streams[1];
-            for (hipEvent_t &ev : eng.pipe_events[k]) if (!ev) WF_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            P.ev_extend = eng.pipe_events[k][0]; P.ev_shade = eng.pipe_events[k][1];
-        } else if (n_pipes == 1 && !overlap) P.stream = P.extend_stream = s;
-        else {      /* (overlap: the bulk on a stream of the engine's own, too -- the caller's may be the legacy default stream, which
-                       runs nothing beside the work of another stream) */
-            if (!g_streams[k]) g_streams[k] = unpark_stream(eng.device, kStreamPlain, 0);
-            if (!g_streams[k]) WF_TRY(hipStreamCreateWithFlags(&g_streams[k], hipStreamNonBlocking));
-            P.stream = P.extend_stream = g_streams[k];
-        }
-        P.b = slice(g_pool.buf, records * k, records, k);
-        P.film = film; P.film.pos += per_pipe * k; P.film.L += per_pipe * k;
-        P.b.samp_pos = P.film.pos; P.b.samp_L = P.film.L;
-        P.h_ctr = g_pool.h_ctr + (size_t) k * C_COUNT;
+    for (hipEvent_t &ev : eng.events) if (!ev) WF_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    /* the stream of the bulk -- everything but the overlapped tails: the caller's, or with overlap one of the engine's own (the
+       caller's may be the legacy default stream, which runs nothing beside the work of another stream) */
+    hipStream_t bulk = s;
+    if (overlap) {
+        if (!eng.stream) eng.stream = unpark_stream(eng.device, kStreamPlain, 0);
+        if (!eng.stream) WF_TRY(hipStreamCreateWithFlags(&eng.stream, hipStreamNonBlocking));
+        bulk = eng.stream;
     }
-    const bool own_streams = n_pipes > 1 || overlap;
+    WfBuf b = g_pool.buf;
+    b.capacity = (uint32_t) records;
+    b.samp_pos = film.pos; b.samp_L = film.L;
+    uint32_t *const h_ctr = g_pool.h_ctr;
     hipStream_t tail_stream = overlap ? eng.tail_stream : nullptr;
-    if (own_streams) {      /* the pipes start after whatever the caller queued on its stream */
-        WF_TRY(hipEventRecord(g_events[2], s));
-        for (int k = 0; k < n_pipes; ++k) { WF_TRY(hipStreamWaitEvent(pipes[k].stream, g_events[2], 0)); if (split) WF_TRY(hipStreamWaitEvent(pipes[k].extend_stream, g_events[2], 0)); }
+    if (overlap) {      /* the bulk starts after whatever the caller queued on its stream */
+        WF_TRY(hipEventRecord(eng.events[0], s));
+        WF_TRY(hipStreamWaitEvent(bulk, eng.events[0], 0));
     }
 
     /* how wf_extend is launched on this scene (plan_extend: the knobs, the stack, the persistent grid, the spill buffer) */
     ExtendPlan plan;
-    err = plan_extend(eng, g_pool, sc, L.stack_depth, L.count_traversal, n_pipes, split_cus, plan);
+    err = plan_extend(eng, g_pool, sc, L.stack_depth, L.count_traversal, plan);
     if (!err.empty()) return err;
     const int thresholds = plan.thresholds, lds_stack = plan.lds_stack, extend_cus = plan.extend_cus, extend_grid = plan.grid, extend_grid_first = plan.grid_first;
     const bool spill = plan.spill;
     const int finish_paths = plan.finish_paths, finish_grid = plan.finish_grid;
-    for (int k = 0; k < n_pipes && plan.spill_ints_per_pipe != 0; ++k) pipes[k].b.stack_spill = g_pool.spill + plan.spill_ints_per_pipe * k;
+    if (plan.spill_ints != 0) b.stack_spill = g_pool.spill;
     stats.trace_cus = (uint32_t) extend_cus; stats.tail_cus = (uint32_t) tail_cus;
     const bool compact = record_compact(sc);
     stats.record = compact ? NORI_WF_RECORD_COMPACT : NORI_WF_RECORD_FULL;
@@ -1113,153 +986,136 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
         WF_TRY(hipMalloc((void **) &d_census, Z_COUNT * sizeof(unsigned long long)));
         WF_TRY(hipMemsetAsync(d_census, 0, Z_COUNT * sizeof(unsigned long long), s));
     }
-    for (int k = 0; k < n_pipes; ++k) pipes[k].b.census = d_census;
+    b.census = d_census;
     FilmLaunch fl;
     fl.tile_mod = L.tile_mod; fl.tile_rem = L.tile_rem; fl.tiles_x = L.tiles_x; fl.tiles_y = L.tiles_y; fl.tile_w = L.tile_w;
     fl.tile_list = L.tile_list; fl.tile_inverse = L.tile_inverse;
 
-    while (true) {
-        bool any = false;
-        for (int k = 0; k < n_pipes; ++k) {         /* start the next batch of idle pipes */
-            Pipe &P = pipes[k];
-            if (P.active || P.finished) { any |= P.active; continue; }
-            if (P.t0 >= P.tile_hi) { P.finished = true; continue; }
-            const uint32_t nt = std::min(P.tiles_b, P.tile_hi - P.t0), ns = std::min(P.spp_b, L.spp_count - P.s0);
-            P.bt.tile_first = P.t0; P.bt.n_tiles = nt; P.bt.s_first = L.spp_begin + P.s0; P.bt.n_spp = ns;
-            P.bt.tile_mod = L.tile_mod; P.bt.tile_rem = L.tile_rem; P.bt.tiles_x = L.tiles_x; P.bt.tile_w = L.tile_w;
-            P.bt.tile_list = L.tile_list;
-            P.bt.inner_repeat = plan.inner_repeat;
-            P.bt.flags = plan.batch_flags;
-            P.bt.pool = (uint32_t) pool_paths;
-            P.batch_samples = nt * 256u * ns;
-            WF_TRY(hipMemsetAsync(P.b.ctr, 0, C_COUNT * sizeof(uint32_t), P.stream));
-            if (split) WF_TRY(hipEventRecord(P.ev_shade, P.stream));      /* (and the film of the pipe's last batch, which read the sample store) */
-            if (overlap) {      /* the sample store's halves alternate: the previous batch's tail and gather still use the other one */
-                const size_t half = (size_t) (stats.n_batches & 1u) * per_pipe;
-                P.film = film; P.film.pos += half; P.film.L += half;
-                P.b.samp_pos = P.film.pos; P.b.samp_L = P.film.L;
-            }
-            stats.n_batches++;
-            P.cur = 0; P.mode = kFreshOnly; P.active = true; any = true; P.batch_rounds = 0;
+    /* one wf_extend launch of a pass: over its stored paths or over its new ones (pass_shape) */
+    auto extend_pass = [&](int mode, const WfBatch &bt, int cur) -> std::string {
+        timer.begin(KC_TRACE, bulk);
+        if (mode == kFreshOnly && first_lists) wf_first_launch_extend(*eng.first, sc, &b, cur, &bt, first_grid, bulk);
+        else launch_extend_dyn(sc, b, cur, thresholds, lds_stack, spill, L.count_traversal, mode, mode == kFreshOnly ? extend_grid_first : extend_grid, bt, bulk);
+        WF_TRY(hipGetLastError());      /* a launch that did not fit (LDS, registers) must not pass for an empty pass */
+        timer.end(bulk);
+        stats.n_launches++;
+        return std::string();
+    };
+    /* the film gather of the batch whose tail ran beside the current one: behind the tail, in front of everything that follows on
+       the bulk's stream (gathers stay in batch order) */
+    auto flush_pending = [&]() -> std::string {
+        if (!pend.active) return std::string();
+        WF_TRY(hipStreamWaitEvent(bulk, eng.tail_events[1], 0));
+        timer.begin(KC_FILM, bulk);
+        film_gather(sc, d_filter_table, pend.film, pend.fl, bulk);
+        if (moments) film_gather_moments(sc, d_filter_table, pend.film, *L.moments, pend.fl, bulk);
+        timer.end(bulk);
+        stats.n_launches++;
+        pend.active = false;
+        return std::string();
+    };
+
+    /* the batches, one after the other: all samples of a range of tiles, range by range */
+    WfBatch bt;
+    bt.tile_mod = L.tile_mod; bt.tile_rem = L.tile_rem; bt.tiles_x = L.tiles_x; bt.tile_w = L.tile_w;
+    bt.tile_list = L.tile_list;
+    bt.inner_repeat = plan.inner_repeat;
+    bt.flags = plan.batch_flags;
+    bt.pool = (uint32_t) pool_paths;
+    uint32_t t0 = 0, s0 = 0;      /* the next batch starts at this selected-tile ordinal and this sample of the call */
+    while (t0 < L.n_sel_tiles) {
+        bt.tile_first = t0; bt.n_tiles = std::min(tiles_b, L.n_sel_tiles - t0);
+        bt.s_first = L.spp_begin + s0; bt.n_spp = std::min(spp_b, L.spp_count - s0);
+        const uint32_t batch_samples = bt.n_tiles * 256u * bt.n_spp;
+        const bool last_batch = s0 + bt.n_spp >= L.spp_count && t0 + bt.n_tiles >= L.n_sel_tiles;
+        WF_TRY(hipMemsetAsync(b.ctr, 0, C_COUNT * sizeof(uint32_t), bulk));
+        FilmStore bfilm = film;      /* the batch's part of the sample store */
+        if (overlap) {      /* the sample store's halves alternate: the previous batch's tail and gather still use the other one */
+            const size_t half = (size_t) (stats.n_batches & 1u) * batch_max;
+            bfilm.pos += half; bfilm.L += half;
+            b.samp_pos = bfilm.pos; b.samp_L = bfilm.L;
         }
-        if (!any) break;
-        /* the path count is read back every sync_every iterations, more often once it is small
-           (the readback costs ~20 us, an iteration on a few paths ~100 us) */
-        uint32_t n_max = 0;
-        for (int k = 0; k < n_pipes; ++k) if (pipes[k].active) n_max = std::max(n_max, pipes[k].mode != kStoredOnly ? 0xffffffffu : pipes[k].h_ctr[C_N + pipes[k].cur]);
-        const int iters = n_max > (16u << 20) ? sync_every : std::min(sync_every, 2);
-        for (int it = 0; it < iters; ++it)
-            for (int k = 0; k < n_pipes; ++k) {
-                Pipe &P = pipes[k];
-                if (!P.active) continue;
-                if (split) WF_TRY(hipStreamWaitEvent(P.extend_stream, P.ev_shade, 0));
-                /* the pass's stored paths, then its new ones (pass_shape): two launches of the two pure kernels */
-                if (P.mode != kFreshOnly) {
-                    timer.begin(KC_TRACE, P.extend_stream);
-                    launch_extend_dyn(sc, P.b, P.cur, thresholds, lds_stack, spill, L.count_traversal, kStoredOnly, extend_grid, P.bt, P.extend_stream);
-                    WF_TRY(hipGetLastError());      /* a launch that did not fit (LDS, registers) must not pass for an empty pass */
-                    timer.end(P.extend_stream);
-                    stats.n_launches++;
-                }
-                if (P.mode != kStoredOnly) {
-                    timer.begin(KC_TRACE, P.extend_stream);
-                    if (first_lists) wf_first_launch_extend(*eng.first, sc, &P.b, P.cur, &P.bt, first_grid, P.extend_stream);
-                    else launch_extend_dyn(sc, P.b, P.cur, thresholds, lds_stack, spill, L.count_traversal, kFreshOnly, extend_grid_first, P.bt, P.extend_stream);
-                    WF_TRY(hipGetLastError());
-                    timer.end(P.extend_stream);
-                    stats.n_launches++;
-                }
-                if (split) { WF_TRY(hipEventRecord(P.ev_extend, P.extend_stream)); WF_TRY(hipStreamWaitEvent(P.stream, P.ev_extend, 0)); }
-                timer.begin(KC_SHADE, P.stream);
-                launch_shade(sc, P.b, P.cur, P.bt, P.mode, sh_grid, compact, P.stream);
-                timer.end(P.stream);
-                if (split) WF_TRY(hipEventRecord(P.ev_shade, P.stream));
+        stats.n_batches++;
+        int cur = 0, mode = kFreshOnly;      /* the state copy the next pass reads; the mode of its kernels */
+        bool gather_deferred = false;
+        /* rounds of passes until no path of the batch is alive.  A batch's paths die geometrically (Russian roulette from depth 3):
+           thousands of rounds on ONE batch mean the loop is stuck; the bound is per batch, however many batches the call needs */
+        uint32_t rounds = 0;
+        while (true) {
+            /* the path count is read back every sync_every iterations, more often once it is small
+               (the readback costs ~20 us, an iteration on a few paths ~100 us) */
+            const uint32_t n_max = mode != kStoredOnly ? 0xffffffffu : h_ctr[C_N + cur];
+            const int iters = n_max > (16u << 20) ? sync_every : std::min(sync_every, 2);
+            for (int it = 0; it < iters; ++it) {
+                /* the pass's stored paths, then its new ones: two launches of the two pure kernels */
+                if (mode != kFreshOnly && !(err = extend_pass(kStoredOnly, bt, cur)).empty()) return err;
+                if (mode != kStoredOnly && !(err = extend_pass(kFreshOnly, bt, cur)).empty()) return err;
+                timer.begin(KC_SHADE, bulk);
+                launch_shade(sc, b, cur, bt, mode, sh_grid, compact, bulk);
+                timer.end(bulk);
                 /* the first pass started min(pool, samples) camera samples: a batch that fits the pool has none left */
-                if (P.mode == kFreshOnly) P.mode = P.batch_samples <= P.bt.pool && !force_mixed ? kStoredOnly : kMixed;
-                P.cur ^= 1;
+                if (mode == kFreshOnly) mode = batch_samples <= bt.pool && !force_mixed ? kStoredOnly : kMixed;
+                cur ^= 1;
                 stats.n_launches++;
-                if (k == 0) stats.n_iterations++;
+                stats.n_iterations++;
             }
-        for (int k = 0; k < n_pipes; ++k)
-            if (pipes[k].active) WF_TRY(hipMemcpyAsync(pipes[k].h_ctr, pipes[k].b.ctr, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, pipes[k].stream));
-        for (int k = 0; k < n_pipes; ++k)
-            if (pipes[k].active) WF_TRY(hipStreamSynchronize(pipes[k].stream));
-        for (int k = 0; k < n_pipes; ++k) {
-            Pipe &P = pipes[k];
-            if (P.active && P.h_ctr[C_OVERFLOW] != 0) return "wavefront: path state pool overflow";
+            WF_TRY(hipMemcpyAsync(h_ctr, b.ctr, C_COUNT * sizeof(uint32_t), hipMemcpyDeviceToHost, bulk));
+            WF_TRY(hipStreamSynchronize(bulk));
+            if (h_ctr[C_OVERFLOW] != 0) return "wavefront: path state pool overflow";
             /* camera samples of the batch no pass has started yet (the counter the next pass would read) */
-            const uint32_t samples_left = P.active ? P.batch_samples - std::min(P.batch_samples, P.h_ctr[C_SAMPLE + P.cur]) : 0u;
-            if (P.active && samples_left == 0u && P.mode == kMixed && !force_mixed) P.mode = kStoredOnly;
-            if (census && P.active) fprintf(stderr, "[wavefront] pipe %d iteration %u: %u path slots, %u samples to start\n", k, stats.n_iterations, P.h_ctr[C_N + P.cur], samples_left);
-            /* the film gather of the batch whose tail ran beside this one: behind the tail, in front of everything that follows on
-               this stream (gathers stay in batch order) */
-            auto flush_pending = [&]() -> std::string {
-                if (!pend.active) return std::string();
-                WF_TRY(hipStreamWaitEvent(P.stream, eng.tail_events[1], 0));
-                timer.begin(KC_FILM, P.stream);
-                film_gather(sc, d_filter_table, pend.film, pend.fl, P.stream);
-                if (moments) film_gather_moments(sc, d_filter_table, pend.film, *L.moments, pend.fl, P.stream);
-                timer.end(P.stream);
-                stats.n_launches++;
-                pend.active = false;
-                return std::string();
-            };
-            bool gather_deferred = false;
-            if (P.active && samples_left == 0u && P.h_ctr[C_N + P.cur] != 0 && P.h_ctr[C_N + P.cur] <= (uint32_t) finish_paths && use_finish) {
-                const bool last_batch = P.s0 + P.bt.n_spp >= L.spp_count && P.t0 + P.bt.n_tiles >= P.tile_hi;
+            const uint32_t samples_left = batch_samples - std::min(batch_samples, h_ctr[C_SAMPLE + cur]);
+            if (samples_left == 0u && mode == kMixed && !force_mixed) mode = kStoredOnly;
+            if (census) fprintf(stderr, "[wavefront] iteration %u: %u path slots, %u samples to start\n", stats.n_iterations, h_ctr[C_N + cur], samples_left);
+            if (samples_left == 0u && h_ctr[C_N + cur] != 0 && h_ctr[C_N + cur] <= (uint32_t) finish_paths && use_finish) {
+                /* few live paths left: wf_finish walks them to their ends -- beside the next batch, or here */
                 if (overlap && !last_batch) {
                     err = flush_pending();      /* (also: the previous tail is done with the side copy) */
                     if (!err.empty()) return err;
-                    hipLaunchKernelGGL(wf_tail_copy, dim3(std::max(1u, (P.h_ctr[C_N + P.cur] + kB - 1) / kB)), dim3(kB), 0, P.stream, P.b, P.cur, eng.tail.st, eng.tail.ctr);
-                    WF_TRY(hipEventRecord(eng.tail_events[0], P.stream));
+                    hipLaunchKernelGGL(wf_tail_copy, dim3(std::max(1u, (h_ctr[C_N + cur] + kB - 1) / kB)), dim3(kB), 0, bulk, b, cur, eng.tail.st, eng.tail.ctr);
+                    WF_TRY(hipEventRecord(eng.tail_events[0], bulk));
                     WF_TRY(hipStreamWaitEvent(tail_stream, eng.tail_events[0], 0));
                     /* the bulk goes on once the tail is about to be dispatched: its workgroups take their CUs first */
                     WF_TRY(hipEventRecord(eng.tail_events[2], tail_stream));
-                    WF_TRY(hipStreamWaitEvent(P.stream, eng.tail_events[2], 0));
-                    WfBuf tb = P.b;
+                    WF_TRY(hipStreamWaitEvent(bulk, eng.tail_events[2], 0));
+                    WfBuf tb = b;
                     tb.st[0] = eng.tail.st; tb.ctr = eng.tail.ctr; tb.stack_spill = eng.tail.spill; tb.capacity = (uint32_t) eng.tail.capacity;
                     timer.begin(KC_TAIL, tail_stream);
-                    launch_finish(sc, tb, 0, P.bt, false, finish_grid_side, compact, tail_stream);
+                    launch_finish(sc, tb, 0, bt, false, finish_grid_side, compact, tail_stream);
                     timer.end(tail_stream);
                     WF_TRY(hipEventRecord(eng.tail_events[1], tail_stream));
-                    pend.active = true; pend.film = P.film;
-                    pend.fl = fl; pend.fl.tile_first = P.bt.tile_first; pend.fl.store_tile_first = P.bt.tile_first; pend.fl.n_tiles = P.bt.n_tiles; pend.fl.n_spp = P.bt.n_spp;
+                    pend.active = true; pend.film = bfilm;
+                    pend.fl = fl; pend.fl.tile_first = bt.tile_first; pend.fl.store_tile_first = bt.tile_first; pend.fl.n_tiles = bt.n_tiles; pend.fl.n_spp = bt.n_spp;
                     gather_deferred = true;
                     stats.n_launches += 2;
                 } else {
-                    timer.begin(KC_SHADE, P.stream);
-                    launch_finish(sc, P.b, P.cur, P.bt, L.count_traversal, finish_grid_main, compact, P.stream);
-                    timer.end(P.stream);
+                    timer.begin(KC_SHADE, bulk);
+                    launch_finish(sc, b, cur, bt, L.count_traversal, finish_grid_main, compact, bulk);
+                    timer.end(bulk);
                     stats.n_launches++;
                 }
-                P.h_ctr[C_N + P.cur] = 0;
+                break;
             }
-            if (!P.active || P.h_ctr[C_N + P.cur] != 0 || samples_left != 0u) continue;
-            /* batch done: splat its samples (each pipe owns its tiles' accumulators) */
-            if (!gather_deferred) {
-                err = flush_pending();
-                if (!err.empty()) return err;
-                fl.tile_first = P.bt.tile_first; fl.store_tile_first = P.bt.tile_first; fl.n_tiles = P.bt.n_tiles; fl.n_spp = P.bt.n_spp;
-                timer.begin(KC_FILM, P.stream);
-                if (!L.film_reference) film_gather(sc, d_filter_table, P.film, fl, P.stream);
-                if (moments) film_gather_moments(sc, d_filter_table, P.film, *L.moments, fl, P.stream);
-                timer.end(P.stream);
-                stats.n_launches++;
-            }
-            P.active = false;
-            P.s0 += P.bt.n_spp;
-            if (P.s0 >= L.spp_count) { P.s0 = 0; P.t0 += P.bt.n_tiles; }
+            if (h_ctr[C_N + cur] == 0 && samples_left == 0u) break;
+            if (++rounds > 20000) return "wavefront: path loop did not terminate";
         }
-        /* a batch's paths die geometrically (Russian roulette from depth 3): thousands of iterations on ONE
-           batch mean the loop is stuck; the bound is per batch, however many batches the call needs */
-        for (int k = 0; k < n_pipes; ++k)
-            if (pipes[k].active && ++pipes[k].batch_rounds > 20000) return "wavefront: path loop did not terminate";
+        /* batch done: splat its samples */
+        if (!gather_deferred) {
+            err = flush_pending();
+            if (!err.empty()) return err;
+            fl.tile_first = bt.tile_first; fl.store_tile_first = bt.tile_first; fl.n_tiles = bt.n_tiles; fl.n_spp = bt.n_spp;
+            timer.begin(KC_FILM, bulk);
+            if (!L.film_reference) film_gather(sc, d_filter_table, bfilm, fl, bulk);
+            if (moments) film_gather_moments(sc, d_filter_table, bfilm, *L.moments, fl, bulk);
+            timer.end(bulk);
+            stats.n_launches++;
+        }
+        s0 += bt.n_spp;
+        if (s0 >= L.spp_count) { s0 = 0; t0 += bt.n_tiles; }
     }
-    if (own_streams)        /* back to the caller's stream */
-        for (int k = 0; k < n_pipes; ++k) {
-            WF_TRY(hipEventRecord(g_events[k], pipes[k].stream));
-            WF_TRY(hipStreamWaitEvent(s, g_events[k], 0));
-        }
+    if (overlap) {      /* back to the caller's stream */
+        WF_TRY(hipEventRecord(eng.events[1], bulk));
+        WF_TRY(hipStreamWaitEvent(s, eng.events[1], 0));
+    }
     timer.begin(KC_FILM, s);
     if (L.film_reference) {
         err = film_reference_order(film_store, film, sc, d_filter_table, L.spp_count, L.tiles_x, L.film_share, d_rgbw, s);
@@ -1269,14 +1125,12 @@ std::string wavefront_render(WfEngine &eng, FilmStore &film_store, const DevScen
     timer.end(s);
     stats.n_launches++;
     WF_TRY(hipGetLastError());
-    unsigned long long h[2 * S_COUNT];
+    unsigned long long h[S_COUNT];
     WF_TRY(hipMemcpyAsync(h, g_pool.buf.stats, sizeof(h), hipMemcpyDeviceToHost, s));
     WF_TRY(hipStreamSynchronize(s));
-    for (int k = 0; k < 2; ++k) {
-        stats.n_camera += h[k * S_COUNT + S_CAM]; stats.n_closest += h[k * S_COUNT + S_CLOSEST]; stats.n_shadow += h[k * S_COUNT + S_SHADOW];
-        stats.n_nodes += h[k * S_COUNT + S_NODES]; stats.n_tris += h[k * S_COUNT + S_TRIS];
-        NORI_PROF_REPORT(h, k)
-    }
+    stats.n_camera = h[S_CAM]; stats.n_closest = h[S_CLOSEST]; stats.n_shadow = h[S_SHADOW];
+    stats.n_nodes = h[S_NODES]; stats.n_tris = h[S_TRIS];
+    NORI_PROF_REPORT(h)
     stats.n_invalid = film_invalid_count(film, s);
     timer.collect(stats.class_ms, stats.class_launches);
     if (d_census) {
@@ -1306,11 +1160,12 @@ std::string wavefront_trace(WfEngine &eng, const DevScene &sc, int stack_depth, 
     std::string err = ensure_pool(pool, state_capacity(n));
     if (!err.empty()) return err;
     ExtendPlan plan;
-    err = plan_extend(eng, pool, sc, stack_depth, count_traversal, 1, 0, plan);
+    err = plan_extend(eng, pool, sc, stack_depth, count_traversal, plan);
     if (!err.empty()) return err;
-    WfBuf b = slice(pool.buf, 0, pool.capacity, 0);
+    WfBuf b = pool.buf;
+    b.capacity = (uint32_t) pool.capacity;
     b.samp_pos = nullptr; b.samp_L = nullptr; b.census = nullptr;      /* (read by the launch of NEW paths and by counting builds under NORI_HIP_CENSUS only) */
-    if (plan.spill_ints_per_pipe != 0) b.stack_spill = pool.spill;
+    if (plan.spill_ints != 0) b.stack_spill = pool.spill;
     /* state copy 0 as wf_shade would have stored these paths (wf_records.h) */
     std::vector<P3> o(n); std::vector<f4> dA(n), dB(n);
     for (size_t i = 0; i < n; ++i) {
@@ -1326,7 +1181,7 @@ std::string wavefront_trace(WfEngine &eng, const DevScene &sc, int stack_depth, 
     uint32_t h_ctr[C_COUNT] = {0};
     h_ctr[C_N + 0] = (uint32_t) n;
     WF_TRY(hipMemcpy(b.ctr, h_ctr, sizeof(h_ctr), hipMemcpyHostToDevice));
-    WF_TRY(hipMemsetAsync(pool.buf.stats, 0, 2 * S_COUNT * sizeof(unsigned long long), s));
+    WF_TRY(hipMemsetAsync(pool.buf.stats, 0, S_COUNT * sizeof(unsigned long long), s));
     WfBatch bt;
     bt.tile_first = 0; bt.n_tiles = 0; bt.s_first = 0; bt.n_spp = 0; bt.tile_mod = 1; bt.tile_rem = 0; bt.tiles_x = 0; bt.tile_w = 0;
     bt.inner_repeat = plan.inner_repeat; bt.flags = plan.batch_flags; bt.pool = (uint32_t) n;

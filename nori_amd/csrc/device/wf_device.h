@@ -18,7 +18,7 @@
 #define NORI_PROF_DECL
 #define NORI_PROF_MARK(acc)
 #define NORI_PROF_STORE
-#define NORI_PROF_REPORT(h, k)
+#define NORI_PROF_REPORT(h)
 #define NORI_LAB_SHADE_PAD
 #define NORI_LAB_SHADE_VERTEX
 #define NORI_LAB_SHADE_STORE

@@ -44,14 +44,14 @@
 #define NORI_PROF_MARK(acc) { const unsigned long long now_ = __builtin_amdgcn_s_memrealtime(); acc += now_ - prof_t; prof_t = now_; }
 #define NORI_PROF_STORE atomicAdd(&b.stats[6], prof_refill); atomicAdd(&b.stats[S_NODES], prof_node); atomicAdd(&b.stats[S_TRIS], prof_leaf); \
     atomicAdd(&b.stats[7], __builtin_amdgcn_s_memrealtime() - prof_t0);
-#define NORI_PROF_REPORT(h, k) { const double tot = (double) h[k * S_COUNT + 7]; \
-    if (tot > 0.0) fprintf(stderr, "[wf_extend profile] wave cycles: refill %.3f, node loop %.3f, triangle step %.3f of %.4g total\n", h[k * S_COUNT + 6] / tot, \
-                           h[k * S_COUNT + S_NODES] / tot, h[k * S_COUNT + S_TRIS] / tot, tot); }
+#define NORI_PROF_REPORT(h) { const double tot = (double) h[7]; \
+    if (tot > 0.0) fprintf(stderr, "[wf_extend profile] wave cycles: refill %.3f, node loop %.3f, triangle step %.3f of %.4g total\n", h[6] / tot, \
+                           h[S_NODES] / tot, h[S_TRIS] / tot, tot); }
 #else
 #define NORI_PROF_DECL
 #define NORI_PROF_MARK(acc)
 #define NORI_PROF_STORE
-#define NORI_PROF_REPORT(h, k)
+#define NORI_PROF_REPORT(h)
 #endif
 
 /* ---- the WIDE node step (rt_trace.h, trav_wide_step): -DNORI_EXP_WIDE_SENS=1 one more load of the node's record, 3 = 32 more VALU instructions */

@@ -129,7 +129,7 @@ def _with_env(env, fn):
 
 
 def test_wavefront_schedule_knobs_do_not_change_the_frame(renderer_factory):
-    """wf_finish on/off, readback cadence, chunking, thresholds and pipes only reschedule the same
+    """wf_finish on/off, readback cadence, chunking and thresholds only reschedule the same
     per-sample work: every camera sample carries the same radiance, and the film adds the samples of a
     pixel in sample order, so the frames are bit-identical."""
     sc = scenes.cornell_box(96, 64, 9, "path_mis", sphere_bsdfs=[Bsdf("mirror"), Bsdf("dielectric")])
@@ -142,7 +142,7 @@ def test_wavefront_schedule_knobs_do_not_change_the_frame(renderer_factory):
     assert np.array_equal(refc, ref)
     for env in ({"NORI_HIP_WF_FINISH": 0}, {"NORI_HIP_WF_FINISH_PATHS": 256}, {"NORI_HIP_WF_SYNC_EVERY": 1},
                 {"NORI_HIP_WF_STATIC": 0, "NORI_HIP_WF_DYNDIV": 1}, {"NORI_HIP_WF_REFILL": 1, "NORI_HIP_WF_LEAF": 64},
-                {"NORI_HIP_WF_PIPES": 2}, {"NORI_HIP_WF_EXTEND_WGS_PER_CU": 1}):
+                {"NORI_HIP_WF_EXTEND_WGS_PER_CU": 1}):
         b, _ = _with_env(env, lambda: wf.render_host())
         assert np.array_equal(b, ref), env
         b, sb = _with_env({**env, **WALK_64B}, lambda: wf.render_host(count_traversal=True))
@@ -151,29 +151,20 @@ def test_wavefront_schedule_knobs_do_not_change_the_frame(renderer_factory):
         assert np.array_equal(b, ref), env
 
 
-def test_cus_split_between_traversal_and_shading_give_the_same_frame(renderer_factory):
-    """The device's CUs shared out between the traversal stream and the shading / film stream (wavefront_render, "split"): two
-    pipes, each half of the tiles, the kernels of the two kinds on disjoint CUs.  Same samples, same order per pixel: the frame
-    has the bits of the one-stream frame and the ray counts are equal; the stats say how many CUs the ray queries had."""
+def test_several_batches_give_the_same_frame_without_the_finish_kernel(renderer_factory):
+    """A call of several batches (a small path budget: 80 tiles x 3 samples per batch, four batches) with the tail kernel off, with
+    a readback after every pass, and with the tails on the bulk's stream: the same samples in the same order per pixel as the
+    call with no knob set, so the frame has its bits and the ray counts are equal."""
     sc = scenes.cornell_box(160, 128, 12, "path_mis", sphere_bsdfs=[Bsdf("mirror"), Bsdf("dielectric")])
     wf = renderer_factory(sc)
     wf.set_option("engine", "wavefront")
-    ref, sr = wf.render_host()
-    assert sr["trace_cus"] > 0
-    for cus in (8, 64, 128):
-        b, sb = _with_env({"NORI_HIP_WF_SPLIT_CUS": cus, "NORI_HIP_WF_SPLIT_MIN": 0}, lambda: wf.render_host())
-        assert sb["trace_cus"] == sr["trace_cus"] - cus, (cus, sb["trace_cus"], sr["trace_cus"])
-        assert np.array_equal(b, ref), cus
-        for k in ("n_camera_samples", "n_closest_rays", "n_shadow_rays"):
-            assert sr[k] == sb[k], (cus, k)
-    # several batches per pipe (a small path budget), and the tail kernel off.  (The film adds a pixel's samples batch by batch:
-    # the frame to compare with is the one of two pipes with the same budget on ONE stream.)
     _budget(wf, 1 << 16)
-    ref2, sr2 = _with_env({"NORI_HIP_WF_PIPES": 2}, lambda: wf.render_host())
-    for env in ({}, {"NORI_HIP_WF_FINISH": 0}, {"NORI_HIP_WF_SYNC_EVERY": 1}):
-        b, sb = _with_env({"NORI_HIP_WF_SPLIT_CUS": 48, "NORI_HIP_WF_SPLIT_MIN": 0, **env}, lambda: wf.render_host())
-        assert np.array_equal(b, ref2), env
-        assert sr2["n_closest_rays"] == sb["n_closest_rays"] and sr2["n_shadow_rays"] == sb["n_shadow_rays"], env
+    ref, sr = wf.render_host()
+    for env in ({"NORI_HIP_WF_FINISH": 0}, {"NORI_HIP_WF_SYNC_EVERY": 1}, {"NORI_HIP_WF_TAIL_CUS": 0}):
+        b, sb = _with_env(env, lambda: wf.render_host())
+        assert np.array_equal(b, ref), env
+        for k in ("n_camera_samples", "n_closest_rays", "n_shadow_rays"):
+            assert sr[k] == sb[k], (env, k)
 
 
 def test_tail_of_a_batch_beside_the_next_batch_gives_the_same_frame(renderer_factory):
