@@ -1218,6 +1218,70 @@ int nori_hip_phase_sample(nori_hip_ctx *ctx, const float *d, const float *xi, si
 /* nori_hip_set_medium on every device's context (the upload resets it, as on one context) */
 int nori_hip_group_set_medium(nori_hip_group *group, const nori_medium_desc *medium);
 
+/* ------------------------------------------------------------------ Delta lights
+ *
+ * Lights without geometry: point, spot and directional.  No counterpart in the reference, whose only lamp without a mesh is the one
+ * baked into the `simple` integrator.  They are a state of the context, set after the upload like the lens, the environment and
+ * the medium and reset by the next upload; no struct of the scene description grows.  Without lights every kernel is the kernel it
+ * was: path_ems and path_mis have three more sets of instantiations (rt_path.h, kDeltaLit) that only contexts with lights run --
+ * "every BSDF, textures, lights", that with an environment, that with a medium; on the wavefront engine the full path record.
+ * Every other integrator refuses lights (NORI_ERR_UNSUPPORTED): path_mats cannot reach a delta light.  A directional light and a
+ * medium exclude each other (the medium fills all space, so the transmittance from infinity is 0): nori_hip_set_lights refuses the
+ * light while a medium is set, nori_hip_set_medium refuses the medium while such a light is set.  NORI_SEED_NORI_BLOCK renders
+ * refuse lights as they refuse a medium.  The feature pass and the first-hit frames are unchanged.
+ *
+ * Everything below is float32 without FMA contraction; every / is the correctly rounded quotient, every sqrt the correctly rounded
+ * root; dot(a, b) = a.x b.x + (a.y b.y + a.z b.z); a vector / a scalar is three quotients.
+ *
+ *   The count and the pick.  nE = n_emitters + n_lights (+ 1 with an environment).  The emitter sample's first draw xiE selects
+ *                         ei = min((uint32_t) (xiE (float) nE), nE - 1): [0, n_emitters) are the area emitters,
+ *                         [n_emitters, n_emitters + n_lights) is delta light ei - n_emitters, n_emitters + n_lights is the
+ *                         environment.  pdfPick = 1 / (float) nE.  The same nE enters the density of an emitter HIT
+ *                         (inv_area / (float) nE), the environment's density on escape and the environment's own emitter sample.
+ *                         A context with lights and no area emitter is valid: "no lights at all" is nE == 0.
+ *   Draws.                A delta-light sample consumes the four draws of every emitter sample (xiE, xiT, xi); xiT and xi are unused.
+ *   Incident(light, p).   What the twin returns as (dir, maxt, radiance); "no sample" is returned as zeros in all seven.
+ *     POINT               dvec = position - p;  dist2 = dot(dvec, dvec);  dist2 == 0: no sample;  dist = sqrt(dist2);
+ *                         dir = dvec / dist;  R = intensity;  maxt = dist - kEpsilon (1e-4).
+ *     SPOT                as POINT, then c = dot(direction, -dir).  c <= cos_outer: no sample.  c >= cos_inner: R = intensity.
+ *                         Otherwise t = (c - cos_outer) / (cos_inner - cos_outer);  fall = (t t) (3 - (2 t));  R = intensity fall.
+ *                         cos_inner == cos_outer is a hard edge: one of the first two cases holds and no quotient is formed.
+ *     DIRECTIONAL         dir = -direction;  R = intensity;  maxt = infinity.  There is no distance.
+ *   At a surface vertex.  wo = toLocal(dir);  f = bsdf_eval(wi, wo);  f zero in every component: no sample.
+ *                         POINT, SPOT: Ld = (f R) (wo.z / (dist2 pdfPick));  DIRECTIONAL: Ld = (f R) (wo.z / pdfPick) -- the area
+ *                         light's expression with cosY = 1, pdfA = pdfPick and, for the directional light, dist2 = 1.  In a context
+ *                         with a medium Ld is then multiplied by Tr(dist), as for an area light.
+ *   At a medium vertex.   ph = HG(dot(d, dir));  Ld = ((ph R) (1 / (dist2 pdfPick))) Tr(dist).
+ *   MIS.                  No BSDF or phase sample reaches a delta light: under path_mis its emitter sample carries the weight
+ *                         exactly 1.0f, as under path_ems.  Nothing else in the weights changes but the count above.
+ *   The shadow ray        starts at the vertex with mint = kEpsilon, direction dir and the maxt above.
+ *
+ * nori_hip_set_lights       n = 0 or lights == NULL: no lights (the kernels and bits of before).  Else the n lights replace the
+ *                           stored ones and are used from the next launch on; directions are stored normalised (a / sqrt(dot(a, a)),
+ *                           float32), fields a type does not use are stored as 0.  NORI_ERR_NOT_READY before an upload;
+ *                           NORI_ERR_INVALID_ARGUMENT, with a message, for n above NORI_MAX_LIGHTS, an unknown type, a field in use
+ *                           that is not finite, a negative intensity, a direction of zero length, a cone that does not satisfy
+ *                           -1 <= cos_outer <= cos_inner <= 1; NORI_ERR_UNSUPPORTED, with a message, for an integrator other than
+ *                           path_ems or path_mis and for a directional light in a context with a medium.  A failed call leaves the
+ *                           stored lights as they were.
+ * nori_hip_get_lights       *n = the number of lights stored; out[0 .. min(cap, *n)) = the lights as stored.  out may be NULL.
+ * nori_hip_light_incident   Incident(light[k], p[3k ..]) of n pairs: dir (3n), maxt (n), radiance (3n).  NORI_ERR_NOT_READY while
+ *                           no lights are set, NORI_ERR_INVALID_ARGUMENT for an index that is not below the number of lights. */
+#define NORI_MAX_LIGHTS 4096
+typedef enum nori_light_type { NORI_LIGHT_POINT = 0, NORI_LIGHT_SPOT = 1, NORI_LIGHT_DIRECTIONAL = 2 } nori_light_type;
+typedef struct nori_light_desc {
+    int32_t type;
+    float position[3];     /* POINT, SPOT */
+    float direction[3];    /* SPOT: the axis the light shines along; DIRECTIONAL: the direction the light travels.  Any non-zero length */
+    float intensity[3];    /* POINT, SPOT: radiant intensity I (W/sr); DIRECTIONAL: irradiance E on a plane facing the light */
+    float cos_inner, cos_outer;   /* SPOT: full intensity where c >= cos_inner, none where c <= cos_outer */
+} nori_light_desc;
+int nori_hip_set_lights(nori_hip_ctx *ctx, uint32_t n, const nori_light_desc *lights);
+int nori_hip_get_lights(const nori_hip_ctx *ctx, uint32_t cap, nori_light_desc *out, uint32_t *n);
+int nori_hip_light_incident(nori_hip_ctx *ctx, const uint32_t *light, const float *p, size_t n, float *dir, float *maxt, float *radiance);
+/* nori_hip_set_lights on every device's context (the upload resets them, as on one context) */
+int nori_hip_group_set_lights(nori_hip_group *group, uint32_t n, const nori_light_desc *lights);
+
 #ifdef __cplusplus
 }
 #endif

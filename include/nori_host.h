@@ -47,6 +47,10 @@ int nori_host_environment(const nori_host_root *root, nori_env_desc *out);
  * Returns 1 and fills *out if the scene has one, 0 if it has none, or a negative nori_status.  Not part of nori_scene_desc: apply
  * it after the upload. */
 int nori_host_medium(const nori_host_root *root, nori_medium_desc *out);
+/* Root is a <scene>: its delta lights (<emitter type="point|spot|directional"> under the <scene>), the records nori_hip_set_lights
+ * takes, in the file's order.  *n = their number; out[0 .. min(cap, *n)) is filled (out may be NULL).  Not part of nori_scene_desc:
+ * apply them after the upload. */
+int nori_host_lights(const nori_host_root *root, uint32_t cap, nori_light_desc *out, uint32_t *n);
 
 /* Root is a <test>: kind 0 = ttest, 1 = chi2test. */
 typedef struct nori_host_test_info {

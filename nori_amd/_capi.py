@@ -168,6 +168,16 @@ class MediumDesc(C.Structure):
     _fields_ = [("sigma_t", C.c_float), ("albedo", C.c_float * 3), ("g", C.c_float)]
 
 
+class LightDesc(C.Structure):
+    """nori_light_desc"""
+    _fields_ = [("type", C.c_int32), ("position", C.c_float * 3), ("direction", C.c_float * 3), ("intensity", C.c_float * 3),
+                ("cos_inner", C.c_float), ("cos_outer", C.c_float)]
+
+
+LIGHT_TYPES = ("point", "spot", "directional")      # nori_light_type
+MAX_LIGHTS = 4096                                   # NORI_MAX_LIGHTS
+
+
 class AccelInfo(C.Structure):
     _fields_ = [("n_triangles", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32),
                 ("max_depth", C.c_uint32), ("node_bytes", C.c_uint32), ("tri_bytes", C.c_uint32),
@@ -296,6 +306,10 @@ HIP_PROTOTYPES = {
     "nori_hip_phase_eval": (C.c_int, [_P, _P, _P, C.c_size_t, _P]),
     "nori_hip_phase_sample": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P]),
     "nori_hip_group_set_medium": (C.c_int, [_P, C.POINTER(MediumDesc)]),
+    "nori_hip_set_lights": (C.c_int, [_P, C.c_uint32, C.POINTER(LightDesc)]),
+    "nori_hip_get_lights": (C.c_int, [_P, C.c_uint32, C.POINTER(LightDesc), C.POINTER(C.c_uint32)]),
+    "nori_hip_light_incident": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P]),
+    "nori_hip_group_set_lights": (C.c_int, [_P, C.c_uint32, C.POINTER(LightDesc)]),
 }
 
 

@@ -1,4 +1,4 @@
-/* ctx.h -- the context behind the C ABI and what the entry points of nori_hip.hip, frame_api.hip, env_map.hip and medium.hip (those units only) need
+/* ctx.h -- the context behind the C ABI and what the entry points of nori_hip.hip, frame_api.hip, env_map.hip, medium.hip and lights.hip (those units only) need
  * of it: the error mapping, the device guard, scratch buffers, the frame's sizes, the stats of a call. */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,6 +31,8 @@ struct nori_hip_ctx {
     std::vector<void *> allocs_env;      /* the environment map (env_map.hip): texels, tables, the record DevScene::env points at */
     uint32_t env_size = 0;               /* its N; 0 while dev.env is null */
     const float *d_env_weight = nullptr; /* its texel weights (nori_hip_debug_env_tables; the path reads the CDFs only) */
+    void *d_lights = nullptr;            /* the delta lights (lights.hip): the array DevScene::lights points at */
+    std::vector<LightRec> host_lights;   /* ... as stored (nori_hip_get_lights) */
     float *d_filter = nullptr;
     const uint32_t *d_tri_mesh = nullptr;
     unsigned long long *d_stats = nullptr;
@@ -146,6 +148,8 @@ static inline size_t env_film_samples() { const char *e = getenv("NORI_HIP_FILM_
 
 /* env_map.hip: frees the context's environment map and clears DevScene::env (an upload, nori_hip_destroy, a new map) */
 void env_release(nori_hip_ctx *ctx);
+/* lights.hip: frees the context's delta lights and clears DevScene::lights / n_lights (an upload, nori_hip_destroy, a new set) */
+void lights_release(nori_hip_ctx *ctx);
 
 /* nori_hip.hip.  What a render refuses of its parameters, in order (features: the pass of nori_hip_render_features, which shares three of the
    refusals and has one of its own among them), and of them what a render by tile list refuses.  render_impl: every render -- share: the block rows of a

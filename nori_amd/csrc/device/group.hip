@@ -449,6 +449,16 @@ int nori_hip_group_set_medium(nori_hip_group *g, const nori_medium_desc *medium)
     return NORI_OK;
 }
 
+/* the delta lights of every context (nori_hip_set_lights) */
+int nori_hip_group_set_lights(nori_hip_group *g, uint32_t n, const nori_light_desc *lights) {
+    if (!g) return NORI_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < g->ctx.size(); ++k) {
+        const int rc = nori_hip_set_lights(g->ctx[k], n, lights);
+        if (rc != NORI_OK) { g->error = "device " + std::to_string(g->devices[k]) + ": " + nori_hip_last_error(g->ctx[k]); return rc; }
+    }
+    return NORI_OK;
+}
+
 int nori_hip_group_render_host(nori_hip_group *g, const nori_render_params *params, int split, int merge, int width, int height,
                                float *rgbw, nori_render_stats *stats, float *merge_ms) {
     if (!g || !params || !rgbw) return NORI_ERR_INVALID_ARGUMENT;

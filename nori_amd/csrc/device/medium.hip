@@ -79,6 +79,12 @@ int nori_hip_set_medium(nori_hip_ctx *ctx, const nori_medium_desc *medium) {
                      "unset the environment first (nori_hip_set_environment with NULL)";
         return NORI_ERR_UNSUPPORTED;
     }
+    for (const LightRec &l : ctx->host_lights)
+        if (l.type == kLightDirectional) {
+            ctx->error = "set_medium: the context holds a directional light, and a medium that fills all space has zero transmittance from infinity; "
+                         "unset the lights first (nori_hip_set_lights with n = 0)";
+            return NORI_ERR_UNSUPPORTED;
+        }
     ctx->dev.medium = medium_record(medium->sigma_t, medium->albedo, medium->g);
     return NORI_OK;
 }

@@ -78,7 +78,8 @@ struct RenderArgs {
 
 /* MATSET = kAnyBsdf | kTextured (rt_path.h): the kernel of scenes with textured albedos; kAnyBsdf | kTextured | kEnvLit: of scenes
    with an environment map (path_mats / path_ems / path_mis; textured or not); kAnyBsdf | kTextured | kMedium: of contexts with a
-   medium (the same three; never together with an environment); kAnyBsdf: every other scene */
+   medium (the same three; never together with an environment); kAnyBsdf: every other scene.  A context with delta lights
+   (path_ems / path_mis) runs one of three more: kAnyBsdf | kTextured | kDeltaLit, and that with kEnvLit or with kMedium */
 template <int INTEG, int STACK, bool COUNT, int MATSET = kAnyBsdf>
 __global__ __launch_bounds__(kBlock, NORI_RENDER_MIN_WAVES) void render_kernel(DevScene sc, RenderArgs args, FilmStore film,
                                                         unsigned long long *stats) {
@@ -558,6 +559,7 @@ void nori_hip_destroy(nori_hip_ctx *ctx) {
     DeviceGuard g(ctx->device);
     free_pool(ctx->allocs_scene); free_pool(ctx->allocs_accel);
     env_release(ctx);
+    lights_release(ctx);
     wavefront_destroy(ctx->wf);
     film_release(ctx->film);
     film_moments_release(ctx->moments);
@@ -580,6 +582,7 @@ int nori_hip_upload_scene(nori_hip_ctx *ctx, const nori_scene_desc *scene) {
     free_pool(ctx->allocs_scene); free_pool(ctx->allocs_accel);
     env_release(ctx);      /* the environment map is set after an upload and lasts until the next (nori_hip_set_environment) */
     memset(&ctx->dev.medium, 0, sizeof(ctx->dev.medium));      /* and so is the medium (nori_hip_set_medium) */
+    lights_release(ctx);      /* and so are the delta lights (nori_hip_set_lights) */
     ctx->have_scene = ctx->have_accel = false;
     wavefront_invalidate(ctx->wf);      /* what the engine keeps per (tree, camera) */
     std::string err = prepare_scene(*scene, ctx->host);
@@ -909,11 +912,21 @@ static void launch_li(nori_hip_ctx *ctx, const nori_ray *r, size_t n, const uint
 #define LI_CASE(I) case I: hipLaunchKernelGGL((li_kernel<I, STACK>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); break;
 #define LI_TEX(I) case I: if (ctx->dev.textured) { hipLaunchKernelGGL((li_kernel<I, STACK, kAnyBsdf | kTextured>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } \
                           else { hipLaunchKernelGGL((li_kernel<I, STACK>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } break;
-#define LI_ENV(I) case I: if (ctx->dev.medium.on) { hipLaunchKernelGGL((li_kernel<I, STACK, kAnyBsdf | kTextured | kMedium>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } \
-                          else if (ctx->dev.env) { hipLaunchKernelGGL((li_kernel<I, STACK, kAnyBsdf | kTextured | kEnvLit>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } \
-                          else if (ctx->dev.textured) { hipLaunchKernelGGL((li_kernel<I, STACK, kAnyBsdf | kTextured>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } \
-                          else { hipLaunchKernelGGL((li_kernel<I, STACK>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } break;
-        LI_CASE(0) LI_CASE(1) LI_CASE(2) LI_TEX(3) LI_ENV(4) LI_ENV(5) LI_ENV(6)
+#define LI_SET(I, SET) hipLaunchKernelGGL((li_kernel<I, STACK, SET>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb)
+#define LI_ENV_(I) if (ctx->dev.medium.on) { LI_SET(I, kAnyBsdf | kTextured | kMedium); } \
+                   else if (ctx->dev.env) { LI_SET(I, kAnyBsdf | kTextured | kEnvLit); } \
+                   else if (ctx->dev.textured) { LI_SET(I, kAnyBsdf | kTextured); } \
+                   else { hipLaunchKernelGGL((li_kernel<I, STACK>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); }
+#define LI_ENV(I) case I: LI_ENV_(I) break;
+/* path_ems / path_mis: first the three sets of a context with delta lights (the lights; with a medium; with an environment) */
+#define LI_LIT(I) case I: if (!ctx->dev.n_lights) { LI_ENV_(I) } \
+                          else if (ctx->dev.medium.on) { LI_SET(I, kAnyBsdf | kTextured | kDeltaLit | kMedium); } \
+                          else if (ctx->dev.env) { LI_SET(I, kAnyBsdf | kTextured | kDeltaLit | kEnvLit); } \
+                          else { LI_SET(I, kAnyBsdf | kTextured | kDeltaLit); } break;
+        LI_CASE(0) LI_CASE(1) LI_CASE(2) LI_TEX(3) LI_ENV(4) LI_LIT(5) LI_LIT(6)
+#undef LI_LIT
+#undef LI_ENV_
+#undef LI_SET
 #undef LI_ENV
 #undef LI_TEX
 #undef LI_CASE
@@ -1199,6 +1212,15 @@ static hipError_t launch_render_one(nori_hip_ctx *ctx, const RenderArgs &a, cons
         /* and one for contexts with a medium: every BSDF, textures, the medium (kMedium; never with an environment) */
         if (ctx->dev.medium.on) kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured | kMedium>;
     }
+    /* path_ems / path_mis have three for contexts with delta lights: every BSDF, textures, the lights (kDeltaLit); that with an
+       environment; that with a medium */
+    if constexpr (INTEG == INT_EMS || INTEG == INT_MIS) {
+        if (ctx->dev.n_lights) {
+            kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured | kDeltaLit>;
+            if (ctx->dev.env) kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured | kDeltaLit | kEnvLit>;
+            if (ctx->dev.medium.on) kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured | kDeltaLit | kMedium>;
+        }
+    }
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds);
         if (e != hipSuccess) return e;
@@ -1266,6 +1288,11 @@ int check_render_params(nori_hip_ctx *ctx, const nori_render_params *params, con
     if (params->seed_mode == NORI_SEED_NORI_BLOCK && ctx->dev.medium.on) {
         ctx->error = "render: NORI_SEED_NORI_BLOCK renders no medium (the mode exists for parity with the reference's sampler, and the reference has no "
                      "medium); unset it (nori_hip_set_medium with NULL) or use NORI_SEED_PER_SAMPLE";
+        return NORI_ERR_UNSUPPORTED;
+    }
+    if (params->seed_mode == NORI_SEED_NORI_BLOCK && ctx->dev.n_lights) {
+        ctx->error = "render: NORI_SEED_NORI_BLOCK renders no delta lights (the mode exists for parity with the reference's sampler, and the reference has no "
+                     "such lights); unset them (nori_hip_set_lights with n = 0) or use NORI_SEED_PER_SAMPLE";
         return NORI_ERR_UNSUPPORTED;
     }
     if (ctx->host.filter.border > 8) { ctx->error = "render: reconstruction filter radius too large for the LDS tile"; return NORI_ERR_UNSUPPORTED; }

@@ -20,6 +20,7 @@
 #include "rt_texture.h"
 #include "env_map.h"
 #include "medium.h"
+#include "lights.h"
 #include "rt_trace.h"
 
 namespace nrt {
@@ -105,11 +106,24 @@ NORI_HD uint32_t emitter_pick(const Tab &tab, uint32_t nE, float xiE, float xiT,
    free-flight distance; a scattering event before the surface is a vertex of its own kind (`med` in path_on_closest: it runs
    through the surface vertex's code with the phase function in the BSDF's place), and an emitter sample is attenuated by the
    transmittance.  path_on_closest then needs the ORIGIN of the ray whose answer it consumes: the caller
-   leaves it in st.ray.o.  Without the bit none of that is compiled or read.  path_mats / path_ems / path_mis only. */
+   leaves it in st.ray.o.  Without the bit none of that is compiled or read.  path_mats / path_ems / path_mis only.
+   kDeltaLit (bit 7): the context has delta lights (lights.h; DevScene::lights, n_lights > 0).  They are n_lights more lights in the
+   emitter pick -- indices [n_emitters, n_emitters + n_lights), the environment moves to n_emitters + n_lights -- and the count
+   enters every density that divides by the number of lights.  A delta light is never hit: its emitter sample carries the MIS
+   weight 1.  Without the bit none of that is compiled or read.  path_ems / path_mis only. */
 constexpr int kAnyBsdf = 0xf;
 constexpr int kTextured = 0x10;
 constexpr int kEnvLit = 0x20;
 constexpr int kMedium = 0x40;
+constexpr int kDeltaLit = 0x80;
+
+/* the lights of the emitter pick: the area emitters, then the delta lights, then the environment */
+template <int MATSET> NORI_HD uint32_t light_count(const DevScene &sc) {
+    uint32_t n = sc.n_emitters;
+    if (MATSET & kDeltaLit) n += sc.n_lights;
+    if (MATSET & kEnvLit) n += 1u;
+    return n;
+}
 
 struct NeeResult {
     f3 Ld;          /* f * Le * cosX * cosY / (dist^2 * pdfA); the environment: f * Le * cosX / pdf_em */
@@ -117,6 +131,62 @@ struct NeeResult {
     float maxt;
     float pdf_em, pdf_bsdf;
 };
+
+/* sample_direct below, past the draws and the environment, of a context with delta lights (kDeltaLit): the pick is an area emitter
+ * or delta light ei - n_emitters.  A delta light is the area light's expression with cosY = 1, pdfA = pdfPick and, for a directional
+ * light, dist2 = 1, so both kinds share ONE tail: Tr, the phase function or the BSDF, Ld.  What differs after it: a BSDF or phase
+ * sample cannot reach a delta light, so its densities are (1, 0) -- the balance heuristic's weight is then exactly 1.0f. */
+template <class Tab, int MATSET>
+NORI_HD bool sample_direct_lit(const DevScene &sc, const Tab &tab, const Surface &s, const Frame &fr, const Bsdf &bsdf, f3 wi, NeeResult &out,
+                               const bool med, const f3 d, const uint32_t nE, const float xiE, const float xiT, const f2 xi) {
+    uint32_t ei = (uint32_t) (xiE * (float) nE);      /* emitter_pick's index */
+    if (ei > nE - 1) ei = nE - 1;
+    const float pdfPick = exact_rcp((float) nE);
+    const bool delta = ei >= sc.n_emitters;      /* (the environment's index never comes here) */
+    f3 dir, rad;
+    float dist2, dist, cosY, pdfA, maxt;
+    if (delta) {
+        if (!light_incident(sc.lights[ei - sc.n_emitters], s.p, dir, maxt, rad, dist2, dist)) return false;
+        cosY = 1.0f;
+        pdfA = pdfPick;
+    } else {
+        MeshRec m; uint32_t tri;
+        (void) emitter_pick(tab, nE, xiE, xiT, m, tri);
+        const f4 *rec = sc.shade_tris + (size_t) (m.tri_offset + tri) * kShadeQuads;
+        const bool hn = (m.flags & kMeshHasNormals) != 0u;
+        const f3 z = mk3(0.0f);
+        f3 p, n;
+        emitter_point(xi, xyz(rec[0]), xyz(rec[1]), xyz(rec[2]), hn, hn ? xyz(rec[3]) : z, hn ? xyz(rec[4]) : z, hn ? xyz(rec[5]) : z, p, n);
+        const f3 dvec = p - s.p;
+        dist2 = dot(dvec, dvec);
+        dist = exact_sqrt(dist2);
+        dir = dvec / dist;
+        cosY = dot(n, -dir);
+        if (!(cosY > 0.0f)) return false;
+        maxt = dist - kEpsilon;
+        pdfA = m.inv_area * pdfPick;
+        rad = mk3(m.radiance[0], m.radiance[1], m.radiance[2]);
+    }
+    float tr = 1.0f;
+    if (MATSET & kMedium) tr = medium_tr(sc.medium, dist);
+    out.dir = dir;
+    out.maxt = maxt;
+    if ((MATSET & kMedium) && med) {
+        const float ph = hg_eval(sc.medium, dot(d, dir));
+        out.pdf_em = delta ? 1.0f : exact_div(pdfA * dist2, cosY);
+        out.pdf_bsdf = delta ? 0.0f : ph;
+        out.Ld = ((ph * rad) * exact_div(cosY, dist2 * pdfA)) * tr;
+        return true;
+    }
+    const f3 wo = to_local(fr, dir);
+    const f3 f = bsdf_eval(bsdf, wi, wo);
+    if (is_zero(f)) return false;
+    out.pdf_em = delta ? 1.0f : exact_div(pdfA * dist2, cosY);
+    out.pdf_bsdf = delta ? 0.0f : bsdf_pdf(bsdf, wi, wo);
+    out.Ld = f * rad * exact_div(wo.z * cosY, dist2 * pdfA);
+    if (MATSET & kMedium) out.Ld = out.Ld * tr;      /* (the MIS weights ignore Tr in both strategies) */
+    return true;
+}
 
 /* Emitter sampling at surface `s`: uniform emitter, triangle by area, uniform
  * barycentrics (alpha = 1 - sqrt(1 - xi1), beta = xi2 sqrt(1 - xi1)).
@@ -130,12 +200,12 @@ NORI_HD bool sample_direct(const DevScene &sc, const Tab &tab, Rng &rng, const S
     const float xiE = rng_next_float(rng);
     const float xiT = rng_next_float(rng);
     const f2 xi = rng_next_2d(rng);
-    const uint32_t nE = (MATSET & kEnvLit) ? sc.n_emitters + 1u : sc.n_emitters;      /* the lights: the environment is the last */
+    const uint32_t nE = light_count<MATSET>(sc);      /* the lights: the environment is the last */
     if (nE == 0) return false;
     if (MATSET & kEnvLit) {
         uint32_t ei = (uint32_t) (xiE * (float) nE);      /* emitter_pick's index */
         if (ei > nE - 1) ei = nE - 1;
-        if (ei == sc.n_emitters) {      /* the environment: a direction from xi, xiT unused */
+        if (ei == ((MATSET & kDeltaLit) ? sc.n_emitters + sc.n_lights : sc.n_emitters)) {      /* the environment: a direction from xi, xiT unused */
             f3 dir, le; float pdfW;
             env_sample(*sc.env, xi, dir, le, pdfW);
             if (!(pdfW > 0.0f)) return false;
@@ -150,6 +220,7 @@ NORI_HD bool sample_direct(const DevScene &sc, const Tab &tab, Rng &rng, const S
             return true;
         }
     }
+    if (MATSET & kDeltaLit) return sample_direct_lit<Tab, MATSET>(sc, tab, s, fr, bsdf, wi, out, med, d, nE, xiE, xiT, xi);
     MeshRec m; uint32_t tri;
     (void) emitter_pick(tab, nE, xiE, xiT, m, tri);
     const float pdfPick = exact_rcp((float) nE);
@@ -233,7 +304,7 @@ NORI_HD bool path_on_closest(const DevScene &sc, const Tab &tab, PathState &st, 
                 float pdfW = 0.0f, wEnv = 1.0f;
                 const f3 le = env_eval(*sc.env, d, weighted ? &pdfW : nullptr);
                 if (weighted) {
-                    const float pdfEm = pdfW * exact_rcp((float) (sc.n_emitters + 1u));
+                    const float pdfEm = pdfW * exact_rcp((float) light_count<MATSET>(sc));
                     wEnv = (st.pdf_mat + pdfEm) > 0.0f ? exact_div(st.pdf_mat, st.pdf_mat + pdfEm) : 0.0f;
                 }
                 if (wEnv > 0.0f) st.L = st.L + st.T * le * wEnv;
@@ -319,7 +390,7 @@ NORI_HD bool path_on_closest(const DevScene &sc, const Tab &tab, PathState &st, 
             float pdfEm = 0.0f;
             const float cosY = dot(sf.ns, -d);
             if (cosY > 0.0f) {
-                const float pdfA = exact_div(m.inv_area, (float) ((MATSET & kEnvLit) ? sc.n_emitters + 1u : sc.n_emitters));
+                const float pdfA = exact_div(m.inv_area, (float) light_count<MATSET>(sc));
                 pdfEm = exact_div(pdfA * hit.t * hit.t, cosY);
             }
             wMat = (st.pdf_mat + pdfEm) > 0.0f ? exact_div(st.pdf_mat, st.pdf_mat + pdfEm) : 0.0f;

@@ -354,6 +354,18 @@ struct MediumRec {
     uint32_t on = 0u;
 };
 
+/* a delta light of the context (lights.h; include/nori_hip.h, "Delta lights"): 48 bytes, nori_light_desc word for word with the
+   direction normalised.  Set by nori_hip_set_lights, never by a scene description. */
+struct LightRec {
+    int32_t type;             /* kLightPoint / kLightSpot / kLightDirectional */
+    float position[3];
+    float direction[3];       /* unit length */
+    float intensity[3];
+    float cos_inner, cos_outer;
+};
+static_assert(sizeof(LightRec) == 48, "nori_light_desc, 48 bytes");
+constexpr int32_t kLightPoint = 0, kLightSpot = 1, kLightDirectional = 2;
+
 struct CameraRec {
     float sample_to_camera[16];   /* row-major */
     float camera_to_world[16];
@@ -418,6 +430,11 @@ struct DevScene {
     const EnvRec *env;
     /* the medium (above), by value; medium.on = 0: none -- and then the kernels compiled without kMedium run (rt_path.h), which never read it */
     MediumRec medium;
+    /* the delta lights (above) in device memory, set by nori_hip_set_lights; null / 0: none -- and then the kernels compiled without
+       kDeltaLit run (rt_path.h), which never read them */
+    const LightRec *lights;
+    uint32_t n_lights;
+    uint32_t lights_pad;
 };
 
 struct Hit {

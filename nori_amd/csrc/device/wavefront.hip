@@ -51,6 +51,9 @@ void wf_env_launch_finish(const DevScene &sc, const void *wf_buf, int cur, const
 /* wavefront_medium.hip: the same for contexts with a medium -- MATSET kAnyBsdf | kTextured | kMedium */
 void wf_medium_launch_shade(const DevScene &sc, const void *wf_buf, int cur, const void *batch, int mode, int grid, hipStream_t s);
 void wf_medium_launch_finish(const DevScene &sc, const void *wf_buf, int cur, const void *batch, bool count, int grid, hipStream_t s);
+/* wavefront_lights.hip: the same for contexts with delta lights -- MATSET kAnyBsdf | kTextured | kDeltaLit, and that with kEnvLit or kMedium */
+void wf_lights_launch_shade(const DevScene &sc, const void *wf_buf, int cur, const void *batch, int mode, int grid, hipStream_t s);
+void wf_lights_launch_finish(const DevScene &sc, const void *wf_buf, int cur, const void *batch, bool count, int grid, hipStream_t s);
 }
 
 namespace {
@@ -559,12 +562,14 @@ void launch_extend_dyn(const DevScene &sc, const WfBuf &b, int cur, int refill, 
    every scene with NORI_HIP_WF_RECORD=full (read once per process), the full one and the kernels of before. */
 bool record_compact(const DevScene &sc) {
     static const bool full = [] { const char *e = getenv("NORI_HIP_WF_RECORD"); return e && std::string(e) == "full"; }();
+    if (sc.n_lights) return false;      /* delta lights: the general variants, on the full record (wavefront_lights.hip) */
     if (sc.env) return false;      /* an environment map: the one general variant, on the full record (wavefront_env.hip) */
     if (sc.medium.on) return false;      /* a medium: likewise (wavefront_medium.hip) */
     return !full && sc.integrator.type >= INT_MATS && sc.bsdf_mask == 1u && !getenv("NORI_HIP_SHADE_ANY_BSDF");
 }
 
 void launch_shade(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt, int mode, int grid_, bool compact, hipStream_t s) {
+    if (sc.n_lights && sc.integrator.type >= INT_EMS) { wf_lights_launch_shade(sc, &b, cur, &bt, mode, grid_, s); return; }      /* kDeltaLit: wavefront_lights.hip */
     if (sc.env && sc.integrator.type >= INT_MATS) { wf_env_launch_shade(sc, &b, cur, &bt, mode, grid_, s); return; }      /* kEnvLit: wavefront_env.hip */
     if (sc.medium.on && sc.integrator.type >= INT_MATS) { wf_medium_launch_shade(sc, &b, cur, &bt, mode, grid_, s); return; }      /* kMedium: wavefront_medium.hip */
     const dim3 grid(grid_ * (kB / kSB)), block(kSB);
@@ -596,6 +601,7 @@ void launch_shade(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt
 }
 
 void launch_finish(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt, bool count, int grid_, bool compact, hipStream_t s) {
+    if (sc.n_lights && sc.integrator.type >= INT_EMS) { wf_lights_launch_finish(sc, &b, cur, &bt, count, grid_, s); return; }
     if (sc.env && sc.integrator.type >= INT_MATS) { wf_env_launch_finish(sc, &b, cur, &bt, count, grid_, s); return; }
     if (sc.medium.on && sc.integrator.type >= INT_MATS) { wf_medium_launch_finish(sc, &b, cur, &bt, count, grid_, s); return; }
     const dim3 grid(grid_), block(kB);

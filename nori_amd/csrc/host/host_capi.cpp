@@ -88,6 +88,14 @@ int nori_host_medium(const nori_host_root *root, nori_medium_desc *out) {
     return 1;
 }
 
+int nori_host_lights(const nori_host_root *root, uint32_t cap, nori_light_desc *out, uint32_t *n) {
+    if (!root || !n || root->root->getClassType() != NoriObject::EScene) return NORI_ERR_INVALID_ARGUMENT;
+    const std::vector<nori_light_desc> &l = static_cast<const Scene *>(root->root.get())->getLights();
+    *n = (uint32_t) l.size();
+    if (out) for (uint32_t k = 0; k < cap && k < l.size(); ++k) out[k] = l[k];
+    return NORI_OK;
+}
+
 int nori_host_test_info_get(const nori_host_root *root, nori_host_test_info *out) {
     if (!root || !out || root->root->getClassType() != NoriObject::ETest) return NORI_ERR_INVALID_ARGUMENT;
     std::memset(out, 0, sizeof(*out));

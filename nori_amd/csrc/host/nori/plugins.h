@@ -95,6 +95,9 @@ public:
        owns the texels.  Area lights are not one. */
     virtual bool isEnvironment() const { return false; }
     virtual void fillEnvironment(nori_env_desc &) const {}
+    /* a delta light (<emitter type="point|spot|directional">, a child of the <scene>): the record nori_hip_set_lights takes */
+    virtual bool isDeltaLight() const { return false; }
+    virtual void fillLight(nori_light_desc &) const {}
 };
 
 /* ------------------------------------------------- Medium, PhaseFunction */
@@ -256,6 +259,7 @@ public:
     const Camera *getCamera() const { return m_camera; }
     const Emitter *getEnvironment() const { return m_environment; }
     const Medium *getMedium() const { return m_medium; }
+    const std::vector<nori_light_desc> &getLights() const { return m_lights; }
     const Sampler *getSampler() const { return m_sampler; }
     Sampler *getSampler() { return m_sampler; }
     const std::vector<Mesh *> &getMeshes() const { return m_meshes; }
@@ -284,6 +288,8 @@ private:
     Camera *m_camera = nullptr;
     Emitter *m_environment = nullptr;      /* the environment map, if any: applied after every upload (device(), deviceGroup()) */
     Medium *m_medium = nullptr;            /* the medium, if any: likewise */
+    std::vector<nori_light_desc> m_lights; /* the delta lights, if any: likewise */
+    std::vector<Emitter *> m_lightObjects; /* ... and the objects they were read from (owned) */
     Accel *m_accel = nullptr;
     mutable nori_scene_desc m_desc;
     mutable std::vector<nori_mesh_desc> m_meshDescs;

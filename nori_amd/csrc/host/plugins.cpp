@@ -274,6 +274,69 @@ private:
 };
 NORI_REGISTER_CLASS(EnvironmentMap, "envmap");
 
+/* <emitter type="point|spot|directional"> as children of <scene>: delta lights (include/nori_hip.h, "Delta lights").
+ *   point        position (point); intensity (color, W/sr) or power (color, W): I = power (kInvPi 0.25f)
+ *   spot         position (point); direction (vector) or target (point: direction = target - position); intensity (color);
+ *                cutoffAngle (degrees from the axis where the light ends, default 20) and beamWidth (degrees within which it is
+ *                full, default 3/4 of cutoffAngle): cos_outer = cos(cutoffAngle), cos_inner = cos(beamWidth)
+ *   directional  direction (vector, the way the light travels); irradiance (color)
+ * What nori_hip_set_lights would refuse of one light is said here, before a device is asked for. */
+class DeltaLight : public Emitter {
+public:
+    DeltaLight(const PropertyList &propList, int type, const char *name) {
+        std::memset(&m_desc, 0, sizeof(m_desc));
+        m_desc.type = type;
+        if (type != NORI_LIGHT_DIRECTIONAL) {
+            const Point3f p = propList.getPoint("position");
+            for (int c = 0; c < 3; ++c) m_desc.position[c] = p[c];
+        }
+        Color3f I;
+        if (type == NORI_LIGHT_DIRECTIONAL) I = propList.getColor("irradiance");
+        else if (propList.has("power")) {
+            if (propList.has("intensity")) throw NoriException("%s light: give intensity or power, not both", name);
+            if (type == NORI_LIGHT_SPOT) throw NoriException("spot light: give its intensity (its power depends on the cone)");
+            I = propList.getColor("power") * (0.31830988618379067154f * 0.25f);
+        } else I = propList.getColor("intensity");
+        for (int c = 0; c < 3; ++c) {
+            if (!std::isfinite(I[c]) || I[c] < 0.0f) throw NoriException("%s light: every component of %s must be finite and not negative", name, type == NORI_LIGHT_DIRECTIONAL ? "irradiance" : "intensity");
+            if (!std::isfinite(m_desc.position[c])) throw NoriException("%s light: position must be finite", name);
+            m_desc.intensity[c] = I[c];
+        }
+        if (type != NORI_LIGHT_POINT) {
+            Vector3f d;
+            if (type == NORI_LIGHT_SPOT && propList.has("target")) {
+                if (propList.has("direction")) throw NoriException("spot light: give direction or target, not both");
+                const Point3f t = propList.getPoint("target");
+                d = Vector3f(t[0] - m_desc.position[0], t[1] - m_desc.position[1], t[2] - m_desc.position[2]);
+            } else d = propList.getVector("direction");
+            const float z = d[0] * d[0] + (d[1] * d[1] + d[2] * d[2]);
+            if (!(z > 0.0f) || !std::isfinite(z)) throw NoriException("%s light: direction must be finite and of non-zero length", name);
+            for (int c = 0; c < 3; ++c) m_desc.direction[c] = d[c];
+        }
+        if (type == NORI_LIGHT_SPOT) {
+            const float cutoff = propList.getFloat("cutoffAngle", 20.0f), beam = propList.getFloat("beamWidth", cutoff * 0.75f);
+            if (!(cutoff > 0.0f && cutoff <= 180.0f)) throw NoriException("spot light: cutoffAngle must lie in (0, 180] degrees (got %f)", cutoff);
+            if (!(beam >= 0.0f && beam <= cutoff)) throw NoriException("spot light: beamWidth must lie in [0, cutoffAngle] degrees (got %f)", beam);
+            m_desc.cos_outer = (float) std::cos((double) cutoff * M_PI / 180.0);
+            m_desc.cos_inner = (float) std::cos((double) beam * M_PI / 180.0);
+        }
+    }
+    Color3f getRadiance() const { return Color3f(0.0f); }
+    bool isDeltaLight() const { return true; }
+    void fillLight(nori_light_desc &d) const { d = m_desc; }
+    std::string toString() const {
+        return format("DeltaLight[\n  type = %d,\n  intensity = [%f, %f, %f]\n]", m_desc.type, m_desc.intensity[0], m_desc.intensity[1], m_desc.intensity[2]);
+    }
+private:
+    nori_light_desc m_desc;
+};
+class PointLight : public DeltaLight { public: PointLight(const PropertyList &p) : DeltaLight(p, NORI_LIGHT_POINT, "point") {} };
+class SpotLight : public DeltaLight { public: SpotLight(const PropertyList &p) : DeltaLight(p, NORI_LIGHT_SPOT, "spot") {} };
+class DirectionalLight : public DeltaLight { public: DirectionalLight(const PropertyList &p) : DeltaLight(p, NORI_LIGHT_DIRECTIONAL, "directional") {} };
+NORI_REGISTER_CLASS(PointLight, "point");
+NORI_REGISTER_CLASS(SpotLight, "spot");
+NORI_REGISTER_CLASS(DirectionalLight, "directional");
+
 /* ================================================= Medium, PhaseFunction */
 /* <phase type="isotropic"/> */
 class IsotropicPhase : public PhaseFunction {
@@ -652,6 +715,7 @@ Scene::Scene(const PropertyList &) { m_accel = new Accel(this); std::memset(&m_d
 Scene::~Scene() {
     delete m_accel; delete m_sampler; delete m_camera; delete m_integrator; delete m_environment; delete m_medium;
     for (Mesh *m : m_meshes) delete m;       /* the reference leaks these (src/scene.cpp:20-25) */
+    for (Emitter *e : m_lightObjects) delete e;
 }
 
 void Scene::activate() {
@@ -672,6 +736,17 @@ void Scene::activate() {
         if (m_environment)
             throw NoriException("A medium that fills all space cannot be lit by an environment map (its transmittance to infinity is zero)");
     }
+    if (!m_lights.empty()) {  /* what nori_hip_set_lights would refuse, likewise */
+        nori_integrator_desc id;
+        m_integrator->fill(id);
+        if (id.type != NORI_INTEGRATOR_PATH_EMS && id.type != NORI_INTEGRATOR_PATH_MIS)
+            throw NoriException("Point, spot and directional lights are rendered by path_ems and path_mis only");
+        if (m_lights.size() > NORI_MAX_LIGHTS) throw NoriException("There can be at most %d point, spot and directional lights per scene!", (int) NORI_MAX_LIGHTS);
+        if (m_medium)
+            for (const nori_light_desc &l : m_lights)
+                if (l.type == NORI_LIGHT_DIRECTIONAL)
+                    throw NoriException("A directional light cannot light a medium that fills all space (its transmittance from infinity is zero)");
+    }
     if (!m_sampler)
         m_sampler = static_cast<Sampler *>(NoriObjectFactory::createInstance("independent", PropertyList()));
     if (s_verbose) {
@@ -691,8 +766,14 @@ void Scene::addChild(NoriObject *obj) {
     case EEmitter:
         /* src/scene.cpp:55-59 throws here: the reference attaches emitters to meshes.  An environment map is the one emitter
            that belongs to the scene (a departure: INTEGRATION.md) */
+        if (static_cast<Emitter *>(obj)->isDeltaLight()) {      /* (likewise a departure: lights without geometry) */
+            m_lights.emplace_back();
+            static_cast<Emitter *>(obj)->fillLight(m_lights.back());
+            m_lightObjects.push_back(static_cast<Emitter *>(obj));
+            break;
+        }
         if (!static_cast<Emitter *>(obj)->isEnvironment())
-            throw NoriException("Scene::addChild(): emitters must be children of a <mesh> (area lights); only <emitter type=\"envmap\"> belongs to the scene");
+            throw NoriException("Scene::addChild(): emitters must be children of a <mesh> (area lights); only <emitter type=\"envmap\"> and point, spot and directional lights belong to the scene");
         if (m_environment) throw NoriException("There can only be one environment map per scene!");
         m_environment = static_cast<Emitter *>(obj);
         break;
@@ -775,6 +856,7 @@ Device &Scene::device() const {
             m_medium->fillMedium(md);
             d->check(nori_hip_set_medium(d->ctx(), &md), "nori_hip_set_medium");
         }
+        if (!m_lights.empty()) d->check(nori_hip_set_lights(d->ctx(), (uint32_t) m_lights.size(), m_lights.data()), "nori_hip_set_lights");
         m_device = std::move(d);
     }
     return *m_device;
@@ -796,6 +878,7 @@ DeviceGroup &Scene::deviceGroup(int n) const {
             m_medium->fillMedium(md);
             g->check(nori_hip_group_set_medium(g->group(), &md), "nori_hip_group_set_medium");
         }
+        if (!m_lights.empty()) g->check(nori_hip_group_set_lights(g->group(), (uint32_t) m_lights.size(), m_lights.data()), "nori_hip_group_set_lights");
         m_group = std::move(g);
     }
     return *m_group;

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _capi as capi
 from ._capi import NoriError
-from .scene import Bsdf, Camera, Environment, Integrator, Medium, Mesh, RFilter, Scene, Texture
+from .scene import Bsdf, Camera, Environment, Integrator, Light, Medium, Mesh, RFilter, Scene, Texture
 
 DEFER_TESTS, QUIET = 1, 2
 _P = C.c_void_p
@@ -35,6 +35,7 @@ HOST_PROTOTYPES = {
     "nori_host_lens": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "nori_host_environment": (C.c_int, [_P, C.POINTER(capi.EnvDesc)]),
     "nori_host_medium": (C.c_int, [_P, C.POINTER(capi.MediumDesc)]),
+    "nori_host_lights": (C.c_int, [_P, C.c_uint32, C.POINTER(capi.LightDesc), C.POINTER(C.c_uint32)]),
     "nori_host_test_info_get": (C.c_int, [_P, C.POINTER(TestInfo)]),
     "nori_host_test_bsdf": (C.c_int, [_P, C.c_uint32, C.POINTER(capi.BsdfDesc)]),
     "nori_host_test_scene_desc": (C.c_int, [_P, C.c_uint32, C.POINTER(capi.SceneDesc)]),
@@ -157,7 +158,19 @@ class HostRoot:
         sc.camera.aperture_radius, sc.camera.focus_distance = self.lens()      # (not part of the description: Renderer.upload applies them)
         sc.environment = self.environment()                                    # (nor is this)
         sc.medium = self.medium()                                              # (nor this)
+        sc.lights = self.lights()                                              # (nor these)
         return sc
+
+    def lights(self):
+        """The scene's delta lights (<emitter type="point|spot|directional"> under the <scene>) as a list of scene.Light."""
+        n = C.c_uint32(0)
+        if self._lib.nori_host_lights(self._h, 0, None, C.byref(n)) != 0:
+            raise NoriError("root is not a <scene>")
+        if n.value == 0:
+            return []
+        arr = (capi.LightDesc * n.value)()
+        self._lib.nori_host_lights(self._h, n.value, arr, C.byref(n))
+        return [Light.from_desc(arr[k]) for k in range(n.value)]
 
     def medium(self):
         """The scene's medium (<medium type="homogeneous">) as a scene.Medium; None without one."""

@@ -103,9 +103,43 @@ class Renderer:
             self.set_environment(scene.environment)
         if getattr(scene, "medium", None) is not None:
             self.set_medium(scene.medium)
+        if getattr(scene, "lights", None):
+            self.set_lights(scene.lights)
         if build:
             self.build_accel(builder)
         return self
+
+    # ------------------------------------------------------------ delta lights
+    def set_lights(self, lights):
+        """The delta lights of the uploaded scene (include/nori_hip.h, "Delta lights"): a list of scene.Light, or None / an empty
+        list for none -- the kernels and the bits of a context that never had lights.  Holds until the next upload."""
+        from .scene import light_array
+        lights = list(lights) if lights is not None else []
+        self._check(self._lib.nori_hip_set_lights(self._h, len(lights), light_array(lights)), "set_lights")
+        return self
+
+    @property
+    def lights(self):
+        """The lights set, as the context stores them (directions normalised, unused fields zero): a list of scene.Light."""
+        from .scene import Light
+        n = C.c_uint32(0)
+        self._check(self._lib.nori_hip_get_lights(self._h, 0, None, C.byref(n)), "get_lights")
+        if n.value == 0:
+            return []
+        arr = (capi.LightDesc * n.value)()
+        self._check(self._lib.nori_hip_get_lights(self._h, n.value, arr, C.byref(n)), "get_lights")
+        return [Light.from_desc(arr[k]) for k in range(n.value)]
+
+    def light_incident(self, light, p):
+        """(dir (n, 3), maxt (n,), radiance (n, 3)): what the lights of the (n,) indices send towards the (n, 3) points, as the
+        emitter sample computes it; zeros where there is no sample."""
+        li = np.ascontiguousarray(light, dtype=np.uint32).reshape(-1)
+        pts = _f32(p, 3)
+        assert li.shape[0] == pts.shape[0]
+        n = li.shape[0]
+        d, hi, rad = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
+        self._check(self._lib.nori_hip_light_incident(self._h, ptr(li), ptr(pts), n, ptr(d), ptr(hi), ptr(rad)), "light_incident")
+        return d, hi, rad
 
     # ------------------------------------------------------------ homogeneous medium
     def set_medium(self, medium):
@@ -988,6 +1022,15 @@ class DeviceGroup:
             self.set_environment(scene.environment)
         if getattr(scene, "medium", None) is not None:
             self.set_medium(scene.medium)
+        if getattr(scene, "lights", None):
+            self.set_lights(scene.lights)
+        return self
+
+    def set_lights(self, lights):
+        """Renderer.set_lights on every device of the group."""
+        from .scene import light_array
+        lights = list(lights) if lights is not None else []
+        self._check(self._lib.nori_hip_group_set_lights(self._h, len(lights), light_array(lights)), "group_set_lights")
         return self
 
     def set_medium(self, medium):

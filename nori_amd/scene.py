@@ -117,6 +117,42 @@ class Medium:
 
 
 @dataclass
+class Light:
+    """A delta light (nori_light_desc in include/nori_hip.h, which states every operation): "point", "spot" or "directional".
+    Not part of nori_scene_desc: Renderer.upload applies Scene.lights with nori_hip_set_lights."""
+    type: str
+    position: tuple = (0.0, 0.0, 0.0)       # point, spot
+    direction: tuple = (0.0, 0.0, 0.0)      # spot: the axis it shines along; directional: the direction the light travels
+    intensity: tuple = (1.0, 1.0, 1.0)      # point, spot: radiant intensity (W/sr); directional: irradiance
+    cos_inner: float = 0.0                  # spot: full intensity where the cosine to the axis is >= cos_inner,
+    cos_outer: float = 0.0                  # none where it is <= cos_outer
+
+    def desc(self) -> capi.LightDesc:
+        d = capi.LightDesc()
+        d.type = capi.LIGHT_TYPES.index(self.type)
+        d.position[:] = [float(x) for x in self.position]
+        d.direction[:] = [float(x) for x in self.direction]
+        d.intensity[:] = [float(x) for x in self.intensity]
+        d.cos_inner, d.cos_outer = float(self.cos_inner), float(self.cos_outer)
+        return d
+
+    @staticmethod
+    def from_desc(d: capi.LightDesc) -> "Light":
+        return Light(capi.LIGHT_TYPES[d.type], tuple(float(x) for x in d.position), tuple(float(x) for x in d.direction),
+                     tuple(float(x) for x in d.intensity), float(d.cos_inner), float(d.cos_outer))
+
+
+def light_array(lights):
+    """the nori_light_desc array of a list of Light (None for an empty list)"""
+    if not lights:
+        return None
+    arr = (capi.LightDesc * len(lights))()
+    for k, l in enumerate(lights):
+        arr[k] = l.desc()
+    return arr
+
+
+@dataclass
 class Mesh:
     positions: np.ndarray                   # (nV, 3) float32, world space
     indices: np.ndarray                     # (nF, 3) uint32
@@ -176,6 +212,7 @@ class Scene:
     textures: List[Texture] = field(default_factory=list)
     environment: Optional[Environment] = None      # path_mats / path_ems / path_mis; applied after the upload
     medium: Optional[Medium] = None                # likewise; never together with an environment
+    lights: List[Light] = field(default_factory=list)      # delta lights (path_ems / path_mis); applied after the upload
 
     # ------------------------------------------------------------ C view
     def c_desc(self):
@@ -273,6 +310,10 @@ class Scene:
             meta["environment"] = {"scale": list(map(float, self.environment.scale))}
         if self.medium is not None:           # (likewise)
             meta["medium"] = {"sigma_t": float(self.medium.sigma_t), "albedo": list(map(float, self.medium.albedo)), "g": float(self.medium.g)}
+        if self.lights:                       # (likewise)
+            meta["lights"] = [{"type": l.type, "position": list(map(float, l.position)), "direction": list(map(float, l.direction)),
+                               "intensity": list(map(float, l.intensity)), "cos_inner": float(l.cos_inner), "cos_outer": float(l.cos_outer)}
+                              for l in self.lights]
         if base is not None:
             assert self.environment is None, "a variant fixture (base=...) stores no arrays: save a scene with an environment whole"
             assert not self.textures, "a variant fixture (base=...) stores no arrays: save a textured scene whole"
@@ -339,4 +380,6 @@ class Scene:
             sc.environment = Environment(z["env_texels"], tuple(meta["environment"]["scale"]), z["env_to_world"])
         if "medium" in meta:
             sc.medium = Medium(meta["medium"]["sigma_t"], tuple(meta["medium"]["albedo"]), meta["medium"]["g"])
+        for l in meta.get("lights", []):
+            sc.lights.append(Light(l["type"], tuple(l["position"]), tuple(l["direction"]), tuple(l["intensity"]), l["cos_inner"], l["cos_outer"]))
         return sc
