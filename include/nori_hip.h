@@ -1254,7 +1254,11 @@ int nori_hip_group_set_medium(nori_hip_group *group, const nori_medium_desc *med
  *   At a medium vertex.   ph = HG(dot(d, dir));  Ld = ((ph R) (1 / (dist2 pdfPick))) Tr(dist).
  *   MIS.                  No BSDF or phase sample reaches a delta light: under path_mis its emitter sample carries the weight
  *                         exactly 1.0f, as under path_ems.  Nothing else in the weights changes but the count above.
- *   The shadow ray        starts at the vertex with mint = kEpsilon, direction dir and the maxt above.
+ *   The shadow ray        starts at the vertex with mint = kEpsilon, direction dir and the maxt above.  It is traced, and counted in
+ *                         n_shadow_rays, for every sample -- also where R or Ld is zero in every component (a black light, a
+ *                         transmittance that underflowed).  A light nearer than 2 kEpsilon leaves maxt < mint (maxt < 0 for one
+ *                         nearer than kEpsilon): the query is the query of every ray, a hit is a t with mint <= t <= maxt, there is
+ *                         none, and the sample is added unoccluded.  The ray is still traced and counted.
  *
  * nori_hip_set_lights       n = 0 or lights == NULL: no lights (the kernels and bits of before).  Else the n lights replace the
  *                           stored ones and are used from the next launch on; directions are stored normalised (a / sqrt(dot(a, a)),

@@ -40,8 +40,10 @@ __global__ __launch_bounds__(kFeatBlock, kFeatMinWaves) void feature_pass_kernel
     const uint32_t sel = blockIdx.x / fl.n_chunks, chunk = blockIdx.x % fl.n_chunks;
     const uint32_t tile_id = fl.tile_rem + sel * fl.tile_mod;
     const int x0 = (int) (tile_id % fl.tiles_x) * kTile, y0 = (int) (tile_id / fl.tiles_x) * kTile;
-    const uint32_t s_end = fl.spp_begin + fl.spp_count;
-    const uint32_t s0 = min(fl.spp_begin + chunk * fl.chunk_spp, s_end), s1 = min(s0 + fl.chunk_spp, s_end);
+    /* the chunk's samples RELATIVE to spp_begin, [r0, r1), as render_kernel counts them: spp_begin + spp_count itself may be 2^32
+       (the frame of sample 2^32 - 1) */
+    const uint32_t r0 = min(chunk * fl.chunk_spp, fl.spp_count);
+    const uint32_t r1 = r0 + min(fl.chunk_spp, fl.spp_count - r0);
     int px, py; film_tile_pixel(tid, x0, y0, px, py);
     const bool live = px < sc.camera.width && py < sc.camera.height;
 
@@ -50,7 +52,8 @@ __global__ __launch_bounds__(kFeatBlock, kFeatMinWaves) void feature_pass_kernel
     TraversalCounters tc; tc.nodes = tc.tris = 0;
     const uint32_t mask = fl.mask;
     if (live) {
-        for (uint32_t s = s0; s < s1; ++s) {
+        for (uint32_t r = r0; r < r1; ++r) {
+            const uint32_t s = fl.spp_begin + r;
             /* renderBlock, src/main.cpp:41-46: jitter, aperture draw, sampleRay -- the camera sample of render_kernel / first_vertex */
             Rng rng;
             rng_seed(rng, (uint64_t) py * (uint64_t) sc.camera.width + (uint64_t) px, (uint64_t) s);
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(kFeatBlock, kFeatMinWaves) void feature_pass_kernel
             const bool found = hit.tri != kNoHit;
             P3 a, n, d;
             first_hit_features(sc, hit, found, mask, a, n, d);
-            const size_t idx = ((size_t) sel * fl.spp_count + (size_t) (s - fl.spp_begin)) * 256u + (size_t) tid;
+            const size_t idx = ((size_t) sel * fl.spp_count + (size_t) r) * 256u + (size_t) tid;
             pos[idx] = pixelSample;
             if (mask & kFeatureAlbedo) albedo[idx] = a;
             if (mask & kFeatureNormal) normal[idx] = n;
@@ -86,8 +89,8 @@ __global__ __launch_bounds__(kFeatBlock, kFeatMinWaves) void feature_pass_kernel
     }
     /* one camera sample = one closest-hit ray; counted per wave, no LDS beside the stack */
     const unsigned long long n_lanes = (unsigned long long) __popcll(__ballot(live));
-    if ((tid & 63) == 0 && n_lanes != 0ull && s1 > s0) {
-        const unsigned long long n = n_lanes * (unsigned long long) (s1 - s0);
+    if ((tid & 63) == 0 && n_lanes != 0ull && r1 > r0) {
+        const unsigned long long n = n_lanes * (unsigned long long) (r1 - r0);
         atomicAdd(&stats[0], n); atomicAdd(&stats[1], n);
     }
 }

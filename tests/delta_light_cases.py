@@ -1,6 +1,7 @@
 """The scenes, light sets and inputs on which tests/test_gpu_delta_lights.py holds the device to tests/delta_lights_ref.py, and on
 which tests/test_delta_lights_cpu.py shows -- without a GPU -- that these inputs reach every new branch (delta_lights_ref.EVENTS)
-and that a wrong branch would change their radiance (delta_lights_ref.MUTATIONS).  Everything here is computed on the CPU, once."""
+and that a wrong branch would change their radiance (delta_lights_ref.MUTATIONS).  Everything here is computed on the CPU, once.
+The box's cases are 48 x 32; the OUTSIDE_LDS cases are path_cases.lights' 32 x 32 (size_of)."""
 from __future__ import annotations
 
 import functools
@@ -8,11 +9,11 @@ import functools
 import numpy as np
 
 from nori_amd.scene import Bsdf, Camera, Integrator, Light, Mesh, RFilter, Scene
-from tests import delta_lights_ref as dl, path_cases as pc, scenes
+from tests import delta_lights_ref as dl, light_cases as lc, path_cases as pc, scenes
 from tests.backends import Oracle
 
 F = np.float32
-W, H = 48, 32
+W, H = 48, 32                     # the box's frame; the OUTSIDE_LDS cases keep path_cases.lights' own 32 x 32: size_of(case)
 SAMPLES = (0, 1, 2, 3)            # the frames: four single-sample frames under the box filter -- a pixel is Li of its path
 N_LI = 4096                       # paths of nori_hip_li: the first 1024 pixels of each of the four samples
 INTEGRATORS = ("path_ems", "path_mis")
@@ -78,6 +79,16 @@ def scenes_resized(sc):
     return sc
 
 
+def outside_lds(name, integrator, lights, medium=None, env=None):
+    """path_cases.lights(name) -- many area lights, grown so that sampled rays hit them, whose tables do NOT fit the LDS -- with the
+    delta lights `lights`: wf_shade<..., LDSTAB = false, ...> of the three delta-light sets, and the megakernel and li_kernel on
+    unredirected table pointers.  emitter_pick reads a table of emitters + lights (+ 1) entries from global memory there."""
+    sc = pc.lights(name, integrator, medium=medium, env=env)
+    assert not lc.fits(lc.table_counts(sc))
+    sc.lights = list(lights)
+    return sc
+
+
 CASES = {
     "a_each_type": lambda i: box(i, [POINT, SPOT, SUN]),
     "b_257": lambda i: box(i, many()),
@@ -85,7 +96,11 @@ CASES = {
     "d_fog": lambda i: box(i, [INSIDE, SPOT], medium=pc.FOG),
     "e_lights_only": lambda i: box(i, [INSIDE, SPOT, SUN], area=False),
     "f_lights_only_sky": lambda i: box(i, [INSIDE, SPOT, SUN], env=pc._sky(), area=False),
+    "g_fog_r3": lambda i: outside_lds("R3", i, [INSIDE, SPOT], medium=pc.THIN_FOG),
+    "h_sky_r4": lambda i: outside_lds("R4", i, [POINT, SPOT, SUN], env=pc._sky(3)),
+    "i_r3": lambda i: outside_lds("R3", i, [POINT, SPOT, SUN]),
 }
+OUTSIDE_LDS = ("g_fog_r3", "h_sky_r4", "i_r3")      # one per delta-light set (with a medium, with an environment, alone)
 # the light sets of (a) and (c) on the box whose area emitter has its geometric normal: what path_ems and path_mis are compared on
 STAT_CASES = {
     "a_each_type": lambda i: box(i, [POINT, SPOT, SUN], light_normals=False),
@@ -93,11 +108,11 @@ STAT_CASES = {
 }
 # mutation -> the cases on which tests/test_delta_lights_cpu.py requires it to change at least 8 paths under path_mis
 SHOWN_ON = {
-    "emitter_hit_pdf_without_lights_in_count": ("a_each_type", "b_257"),
-    "env_at_unshifted_index": ("c_each_type_sky", "f_lights_only_sky"),
+    "emitter_hit_pdf_without_lights_in_count": ("a_each_type", "b_257") + OUTSIDE_LDS,
+    "env_at_unshifted_index": ("c_each_type_sky", "f_lights_only_sky", "h_sky_r4"),
     "mis_weight_from_quotient": ("a_each_type", "e_lights_only"),
     "no_falloff": ("a_each_type", "d_fog"),
-    "no_tr_on_delta": ("d_fog",),
+    "no_tr_on_delta": ("d_fog", "g_fog_r3"),
     "maxt_is_dist": ("a_each_type",),
 }
 
@@ -124,6 +139,12 @@ def applicable(sc, integrator):
 @functools.lru_cache(maxsize=None)
 def scene_of(case, integrator):
     return CASES[case](integrator)
+
+
+def size_of(case):
+    """(width, height) of the case's frame"""
+    cam = scene_of(case, "path_mis").camera
+    return cam.width, cam.height
 
 
 @functools.lru_cache(maxsize=None)

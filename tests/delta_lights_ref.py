@@ -30,6 +30,18 @@ EVENTS = (
     "delta_shadow",                                      # a delta sample's shadow ray (point / spot: it has a distance)
     "delta_tr",                                          # a delta sample in a medium: Tr enters
 )
+# what the drawn lights of tests/path_fuzz.py's lit rounds are there to reach (the hand-made cases of tests/delta_light_cases.py are
+# not asked for them): counted like EVENTS, never part of the contract of delta_light_cases.applicable
+FUZZ_EVENTS = (
+    "delta_outside_cone",                                # a delta pick without a sample: the point lies outside a spot's cone
+    "delta_bsdf_zero",                                   # a delta pick rejected because the BSDF is zero (the light behind the surface)
+    "delta_black_shadow",                                # a delta sample whose radiance is zero in every channel: its shadow ray is traced
+    "delta_occluded",                                    # a delta sample whose shadow ray is occluded
+    "hard_edge_lit",                                     # a sample of a spot with cos_inner == cos_outer
+    "delta_medium_lens",                                 # a delta sample at a medium vertex of a path that began on a lens
+)
+# counted as well, asked of no drawn round (a vertex within 2e-4 of a light is not drawn; tests/test_gpu_delta_lights.py aims rays at one)
+RARE_EVENTS = ("delta_empty_interval",)                  # a delta sample nearer than 2 kEpsilon: maxt < mint, traced, never occluded
 MUTATIONS = {      # name -> the counter that is non-zero on every path the departure can change
     "emitter_hit_pdf_without_lights_in_count": "emitter_hit_lights_count",
     "env_at_unshifted_index": ("env_pick_shifted", "pick_point", "pick_spot", "pick_directional"),      # (the pick that index n_emitters was)
@@ -152,7 +164,10 @@ def walk(backend, scene, integrator, rays, floats, lights=None, medium=None, env
     depth, cur = np.zeros(n, np.int64), np.zeros(n, np.int64)
     alive = np.ones(n, bool)
     n_closest = n_shadow = 0
-    events = {k: np.zeros(n, np.int64) for k in EVENTS + ("vertices",)}
+    events = {k: np.zeros(n, np.int64) for k in EVENTS + FUZZ_EVENTS + RARE_EVENTS + ("vertices",)}
+    LENS = scene.camera.aperture_radius > 0
+    hard = (LT.type == SPOT) & (LT.cos_inner == LT.cos_outer)
+    from_delta = np.zeros(n, bool)                 # the path's last emitter sample came from a delta light (and asks for a shadow ray)
 
     def draw(idx):
         v = floats[idx, cur[idx]]
@@ -191,6 +206,7 @@ def walk(backend, scene, integrator, rays, floats, lights=None, medium=None, env
         k = idx.shape[0]
         xs = np.stack([draw(idx), draw(idx), draw(idx), draw(idx)], -1)
         ok = np.zeros(k, bool)
+        from_delta[idx] = False
         dirs, hi, Ld = np.zeros((k, 3), F), np.zeros(k, F), np.zeros((k, 3), F)
         pdf_em, pdf_bsdf = np.zeros(k, F), np.zeros(k, F)
         ei = np.minimum((xs[:, 0] * F(nL)).astype(np.int64), nL - 1)
@@ -228,6 +244,7 @@ def walk(backend, scene, integrator, rays, floats, lights=None, medium=None, env
                 for t_, name in ((POINT, "pick_point"), (SPOT, "pick_spot"), (DIRECTIONAL, "pick_directional")):
                     events[name][gq[LT.type[li] == t_]] += 1
                 events["spot_in_band"][gq[band]] += 1
+                events["delta_outside_cone"][gq[~g_ & (LT.type[li] == SPOT) & (dist2[q] != 0)]] += 1
                 if med:
                     events["delta_at_medium_vertex"][gq] += 1
             q = np.nonzero(~delta)[0]
@@ -269,6 +286,7 @@ def walk(backend, scene, integrator, rays, floats, lights=None, medium=None, env
                 else:
                     wo = _to_local(frame[0][a], frame[1][a], frame[2][a], dr)
                     f, pb = surface_bsdf(mesh[a], alb[a], wi[a], wo)
+                    events["delta_bsdf_zero"][idx[a[delta & good & _is_zero(f)]]] += 1
                     good = good & ~_is_zero(f)
                     if mutate == "mis_weight_from_quotient":      # the densities a light with an area would have: pdfPick dist2, the BSDF's
                         pe = np.where(delta, pdfA * dist2, pe).astype(F)
@@ -282,6 +300,12 @@ def walk(backend, scene, integrator, rays, floats, lights=None, medium=None, env
                     ld = np.where(use_tr[:, None], ld * tr[:, None], ld)
                     events["delta_tr"][idx[a[delta & good]]] += 1
             gd = idx[a[delta & good]]
+            from_delta[gd] = True
+            events["delta_black_shadow"][idx[a[delta & good & _is_zero(rad)]]] += 1
+            events["hard_edge_lit"][idx[a[delta & good & hard[np.clip(ei[a] - nE, 0, nD - 1)]]]] += 1
+            events["delta_empty_interval"][idx[a[delta & good & (mx < KEPS)]]] += 1
+            if med and LENS:
+                events["delta_medium_lens"][gd] += 1
             if MIS:
                 events["delta_sample_mis"][gd] += 1
             events["delta_shadow"][idx[a[delta & good & np.isfinite(mx)]]] += 1
@@ -439,6 +463,8 @@ def walk(backend, scene, integrator, rays, floats, lights=None, medium=None, env
             ans = query(idx[sh], origin[sh], sh_dir[sh], np.full(sh.size, KEPS, F), sh_maxt[sh], True)
             n_shadow += sh.size
             lit = ans["mesh"] == NO_HIT
+            dark = idx[sh[~lit]]
+            events["delta_occluded"][dark[from_delta[dark]]] += 1
             g = idx[sh[lit]]
             L[g] = (L[g] + Ld[sh[lit]]).astype(F)
         T[idx], pdf_mat[idx] = Tn, pm

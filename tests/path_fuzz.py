@@ -5,7 +5,7 @@ soup, area lights (leaning normals, a reflecting BSDF, facing away from the came
 parameters, textures with and without per-vertex texcoords, a fog or a sky or neither, a thin lens, a camera inside a glass body,
 the tree builder, a ragged frame, the sample index and the wavefront knobs.
 
-    python tests/path_fuzz.py [--seconds 60] [--seed 1000]
+    python tests/path_fuzz.py [--seconds 60] [--seed 1000] [--lit]
 
 runs rounds from any seed on a GPU (a long manual run; not part of the suite).
 
@@ -15,7 +15,12 @@ a 1 -- ends only with probability 0.01 per vertex.  The generator therefore boun
 and texels stay <= 0.8; at most one wall is a mirror; a fog with a 1 in its albedo fills a CLOSED box and has a mean free path of
 at least the box's size, so that most of its paths' vertices are on surfaces (outside a half-open box such a fog has no surface
 to end a path at).  It bounds nothing per path: a round whose longest path still exceeds
-LONGEST is listed in SKIPPED with that length, whole."""
+LONGEST is listed in SKIPPED with that length, whole.
+
+A LIT round (LIT_SEEDS, lit_scene_of) is the round of its seed with drawn delta lights under path_ems or path_mis, held to
+tests/delta_lights_ref.py: 1 to 4096 point, spot and directional lights -- in a wall's plane, half a kEpsilon off a wall on either
+side, at a mesh vertex, inside a body, at the eye, behind the ceiling; black ones; hard-edged, full-sphere and hair-thin cones.
+The draws of the plain rounds are untouched: the lights come from a generator of their own."""
 from __future__ import annotations
 
 import argparse
@@ -53,6 +58,16 @@ BRIGHTEST = 0.8                          # of a diffuse albedo, a kd, a texel
 LONGEST = 128
 SKIPPED = {}
 SEEDS = tuple(s for s in range(0, 36) if s not in SKIPPED)
+
+# The lit rounds: scene_of(seed) with drawn delta lights (point, spot, directional; lit_scene_of) under path_ems or path_mis, held to
+# tests/delta_lights_ref.py -- a run of consecutive seeds of their own, skipped for the same one reason.
+LIT_SKIPPED = {}
+LIT_SEEDS = tuple(s for s in range(36, 60) if s not in LIT_SKIPPED)
+LIGHT_COUNTS = (1, 2, 3, 17, 256, 4096)      # (4096 is NORI_MAX_LIGHTS)
+POSITION_CLASSES = ("anywhere", "in_a_wall_plane", "just_inside_a_wall", "just_outside_a_wall", "at_a_sphere_vertex", "at_a_sphere_centroid",
+                    "at_the_eye", "above_the_box")
+OFF_THE_WALL = 5e-5                          # half of kEpsilon: a shadow ray's maxt = dist - kEpsilon ends before or after the wall
+CONES = ((20.0, 35.0), (30.0, 30.0), (0.0, 180.0), (10.0, 10.01), (60.0, 89.0))      # (inner, outer) in degrees; (0, 180) is cos 1 / -1
 
 
 # ------------------------------------------------------------------ the draws (tests/fuzz_engines.py --features calls them too)
@@ -230,9 +245,104 @@ def scene_of(seed):
     return sc, builder, knobs
 
 
-def describe(seed):
-    """the drawn configuration in one line"""
+def light_count_of(seed):
+    """the number of delta lights of lit round `seed`: LIGHT_COUNTS in turn, shifted by two per kind, so that any 18 consecutive
+    seeds hold every count under every kind (seed // 3 advances once per fog / sky / neither triple)"""
+    return LIGHT_COUNTS[(seed // 3 + 2 * (seed % 3)) % len(LIGHT_COUNTS)]
+
+
+def cone_cosines(inner, outer):
+    return (1.0, -1.0) if (inner, outer) == (0.0, 180.0) else (float(np.cos(np.radians(inner))), float(np.cos(np.radians(outer))))
+
+
+def draw_lights(rng, sc, closed, n, seed):
+    """(lights, classes, cones): n delta lights for the scene sc of scene_of(seed), from a generator of their own.
+    Types: every fifth light is directional, never in a fog (the setter refuses it); the others are points or spots by a draw.
+    Positions: POSITION_CLASSES in turn over the lights that have a position, beginning at class `seed`; classes[k] is the
+    class' index, -1 for a directional light.  cones[k] is the index into CONES of a spot, -1 otherwise."""
+    from nori_amd.scene import Light
+    eye = sc.camera.to_world[:3, 3].astype(np.float64)
+    spheres = [m for m in sc.meshes if m.name.startswith("sphere")]
+    walls = [("floor", 1, 0.0, 1.0), ("ceiling", 1, 2.0, -1.0), ("back", 2, -1.0, 1.0), ("left", 0, -1.0, 1.0), ("right", 0, 1.0, -1.0)]      # (name, axis, plane, inward)
+    if closed:
+        walls.append(("front", 2, 1.0, -1.0))
+    in_box = lambda: np.array([rng.uniform(-0.95, 0.95), rng.uniform(0.05, 1.95), rng.uniform(-0.95, 0.95)])
+    lights, classes, cones = [], [], []
+    placed = 0
+    for k in range(n):
+        u = rng.random()
+        inten = rng.uniform(0.2, 6.0, 3)
+        if u < 0.1:                                   # a tenth are black: no radiance, and the shadow ray is traced all the same
+            inten[:] = 0.0
+        elif u < 0.1 + 1.0 / 7.0:                     # a further seventh have one channel at zero
+            inten[int(rng.integers(3))] = 0.0
+        inten = tuple(float(x) for x in inten)
+        target = in_box()
+        if sc.medium is None and (k + seed) % 5 == 4:
+            d = target - np.array([rng.uniform(-3, 3), rng.uniform(2.5, 6.0), rng.uniform(-1.0, 5.0)])      # from above and mostly from the front
+            lights.append(Light("directional", direction=tuple(float(x) for x in d), intensity=inten))
+            classes.append(-1)
+            cones.append(-1)
+            continue
+        c = (placed + seed) % len(POSITION_CLASSES)
+        placed += 1
+        name = POSITION_CLASSES[c]
+        if name == "anywhere":
+            pos = in_box()
+        elif name == "in_a_wall_plane":               # the ceiling's or a side wall's plane, exactly
+            _, axis, plane, _ = walls[(1, 3, 4)[int(rng.integers(3))]]
+            pos = in_box()
+            pos[axis] = plane
+        elif name in ("just_inside_a_wall", "just_outside_a_wall"):
+            _, axis, plane, inward = walls[int(rng.integers(len(walls)))]
+            pos = in_box()
+            pos[axis] = plane + (OFF_THE_WALL if name == "just_inside_a_wall" else -OFF_THE_WALL) * inward
+        elif name == "at_a_sphere_vertex":            # the float32 coordinates themselves
+            m = spheres[int(rng.integers(len(spheres)))]
+            pos = m.positions[int(rng.integers(m.positions.shape[0]))].astype(np.float64)
+        elif name == "at_a_sphere_centroid":          # inside the body: lit through glass, dark inside an opaque one
+            m = spheres[int(rng.integers(len(spheres)))]
+            pos = m.positions.astype(np.float64).mean(axis=0)
+        elif name == "at_the_eye":
+            pos = eye.copy()
+        else:                                         # 3 units above the box: behind the ceiling from everywhere inside
+            pos = np.array([rng.uniform(-0.95, 0.95), 5.0, rng.uniform(-0.95, 0.95)])
+        pos = tuple(float(x) for x in np.asarray(pos, F))
+        classes.append(c)
+        if rng.random() < 0.5:
+            lights.append(Light("point", pos, intensity=inten))
+            cones.append(-1)
+        else:
+            ci = int(rng.integers(len(CONES)))
+            axis_ = target - np.asarray(pos, np.float64)
+            if not np.abs(axis_).max() > 1e-3:
+                axis_ = np.array([0.0, -1.0, 0.0])
+            cin, cout = cone_cosines(*CONES[ci])
+            lights.append(Light("spot", pos, tuple(float(x) for x in axis_), inten, cin, cout))
+            cones.append(ci)
+    return lights, classes, cones
+
+
+@functools.lru_cache(maxsize=None)
+def lit_scene_of(seed):
+    """(Scene, builder, knobs) of LIT round `seed`: scene_of(seed) -- its geometry, materials, textures, kind, lens, camera, builder, S
+    and knobs -- with path_ems (even seeds) or path_mis (odd) for its integrator and light_count_of(seed) delta lights drawn from
+    np.random.default_rng([BASE, seed, 1]); knobs gains light_classes and light_cones (draw_lights)."""
+    import dataclasses
     sc, builder, kn = scene_of(seed)
+    rng = np.random.default_rng([BASE, seed, 1])
+    lights, classes, cones = draw_lights(rng, sc, kn["closed"], light_count_of(seed), seed)
+    lit = dataclasses.replace(sc, integrator=Integrator(("path_ems", "path_mis")[seed % 2]), lights=lights)
+    return lit, builder, dict(kn, light_classes=tuple(classes), light_cones=tuple(cones))
+
+
+def round_of(seed, lit=False):
+    return lit_scene_of(seed) if lit else scene_of(seed)
+
+
+def describe(seed, lit=False):
+    """the drawn configuration in one line"""
+    sc, builder, kn = round_of(seed, lit)
     cam = sc.camera
     what = [f"seed {seed}: {sc.integrator.type} {cam.width}x{cam.height} S={kn['S']} builder {builder}", "closed" if kn["closed"] else "half-open"]
     if sc.medium is not None:
@@ -252,6 +362,12 @@ def describe(seed):
         if m.radiance is not None:
             tag += "*" + ("n" if m.normals is not None else "") + ("r" if any(x > 0 for x in b.albedo) else "")
         what.append(f"{m.name}:{tag}:{m.indices.shape[0]}")
+    if sc.lights:
+        types = [l.type for l in sc.lights]
+        held = sorted(set(kn["light_classes"]) - {-1})
+        what.append(f"{len(sc.lights)} delta lights: " + " ".join(f"{types.count(t)} {t}" for t in ("point", "spot", "directional") if t in types)
+                    + "; positions " + (" ".join(POSITION_CLASSES[c] for c in held) if len(held) < len(POSITION_CLASSES) else "of every class")
+                    + "; cones " + " ".join("%g/%g" % CONES[c] for c in sorted(set(kn["light_cones"]) - {-1})))
     what.append(f"pool {kn['wavefront_paths']} batch {kn['wavefront_samples']} {' '.join(kn['env'].values())}")
     return ", ".join(what)
 
@@ -269,24 +385,29 @@ def oracle_of(seed):
     return Oracle(scene_of(seed)[0], use_bvh=True)
 
 
-def walk(seed, from_start=False, mutate=None):
-    """path_ref.walk of the round's frame under the round's integrator (from_start: of nori_hip_li's stream)"""
-    sc = scene_of(seed)[0]
-    return pc.walk_scene(sc, oracle_of(seed), inputs(seed), sc.integrator.type, from_start, mutate)
+def walk(seed, from_start=False, mutate=None, lit=False):
+    """path_ref.walk of the round's frame under the round's integrator (from_start: of nori_hip_li's stream); of a lit round
+    delta_lights_ref.walk -- on the same inputs and oracle: neither the integrator nor the lights enter them"""
+    sc = round_of(seed, lit)[0]
+    if not lit:
+        return pc.walk_scene(sc, oracle_of(seed), inputs(seed), sc.integrator.type, from_start, mutate)
+    from tests import delta_lights_ref as dl
+    _, _, f, rays = inputs(seed)
+    return dl.walk(oracle_of(seed), sc, sc.integrator.type, rays, f if from_start else f[:, 4:], medium=sc.medium, env=sc.environment, max_vertices=pc.CAP, mutate=mutate)
 
 
 @functools.lru_cache(maxsize=None)
-def reference(seed, from_start=False):
+def reference(seed, from_start=False, lit=False):
     """walk(), computed once and shared read-only"""
-    L, nc, ns, ev = walk(seed, from_start)
+    L, nc, ns, ev = walk(seed, from_start, lit=lit)
     L.setflags(write=False)
     return L, nc, ns, ev
 
 
-def longest_path(seed):
+def longest_path(seed, lit=False):
     """the vertices of the round's longest path: of the frame's stream and, for a pinhole round, of nori_hip_li's"""
     streams = (False,) if scene_of(seed)[0].camera.aperture_radius > 0 else (False, True)
-    return max(int(reference(seed, fs)[3]["vertices"].max()) for fs in streams)
+    return max(int(reference(seed, fs, lit)[3]["vertices"].max()) for fs in streams)
 
 
 # ------------------------------------------------------------------ one round on a GPU
@@ -294,12 +415,12 @@ def differing(a, b):
     return int((np.ascontiguousarray(a).view(np.uint32) != np.ascontiguousarray(b).view(np.uint32)).any(axis=1).sum())
 
 
-def one_round(seed, make_renderer):
-    """The three parts of tests/test_gpu_paths.py on round `seed`, every comparison an equality of bytes; make_renderer(scene,
-    builder=...) gives the uploaded renderer.  Prints the seed, the configuration and the differing paths of every part before it
-    asserts.  Returns the rays traced."""
-    sc, builder, kn = scene_of(seed)
-    what = describe(seed)
+def one_round(seed, make_renderer, lit=False):
+    """The three parts of tests/test_gpu_paths.py on round `seed` (lit: on lit round `seed`), every comparison an equality of bytes;
+    make_renderer(scene, builder=...) gives the uploaded renderer.  Prints the seed, the configuration and the differing paths of
+    every part before it asserts.  Returns the rays traced."""
+    sc, builder, kn = round_of(seed, lit)
+    what = describe(seed, lit)
     print(what)
     r = make_renderer(sc, builder=builder)
     if builder == 1:      # (the radix tree, which assert_built_where_asked does not know)
@@ -308,6 +429,7 @@ def one_round(seed, make_renderer):
         from tests.test_gpu_parity import assert_built_where_asked
         assert_built_where_asked(r, builder)
     assert (r.medium is not None) == (sc.medium is not None) and (r.environment_size > 0) == (sc.environment is not None), what
+    assert len(r.lights) == len(sc.lights) and bool(sc.lights) == lit, what
     idx, seq, f, rays = inputs(seed)
     cam = sc.camera
     w, h, n = cam.width, cam.height, cam.width * cam.height
@@ -319,12 +441,12 @@ def one_round(seed, make_renderer):
         print(f"seed {seed} lens rays:", int((got.view(np.uint32).reshape(n, -1) != rays.view(np.uint32).reshape(n, -1)).any(axis=1).sum()), "of", n, "differ")
         assert got.tobytes() == rays.tobytes(), what
     else:
-        want_li = reference(seed, True)[0]
+        want_li = reference(seed, True, lit)[0]
         got_li = r.li(rays, idx, seq)
         print(f"seed {seed} li:", differing(got_li, want_li), "of", n, "paths differ")
         assert got_li.tobytes() == want_li.tobytes(), (what, differing(got_li, want_li))
     # 2. both engines' frames of sample S under the box filter: a pixel is Li of its path
-    want, nc, ns, _ = reference(seed)
+    want, nc, ns, _ = reference(seed, False, lit)
     frames = {}
     for e, engine in enumerate(("megakernel", "wavefront")):
         r.set_option("engine", engine)
@@ -336,8 +458,8 @@ def one_round(seed, make_renderer):
         assert got.tobytes() == want.tobytes(), (what, engine, differing(got, want))
         assert (st["n_closest_rays"], st["n_shadow_rays"]) == (nc, ns), (what, engine)
         assert st["n_invalid"] == 0, what
-        if engine == "wavefront" and (sc.medium is not None or sc.environment is not None):
-            assert st["wf_record"] == "full", what      # a fog or a sky: the one general variant, on the full record
+        if engine == "wavefront" and (lit or sc.medium is not None or sc.environment is not None):
+            assert st["wf_record"] == "full", what      # a fog, a sky or delta lights: a general variant, on the full record
         frames[engine] = frame
     # 3. the drawn pool, batch and finish knobs: regeneration, many passes, wf_finish early or never
     r.set_option("wavefront_paths", kn["wavefront_paths"])
@@ -362,6 +484,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--seed", type=int, default=1000)
+    ap.add_argument("--lit", action="store_true", help="the rounds with drawn delta lights")
     a = ap.parse_args()
     from nori_amd.render import Renderer
     t0, n, rays, skipped = time.time(), 0, 0, []
@@ -369,7 +492,7 @@ def main():
         seed = a.seed + n
         n += 1
         try:
-            longest = longest_path(seed)
+            longest = longest_path(seed, a.lit)
         except AssertionError:      # (the walker's: a path alive at path_cases.CAP)
             longest = pc.CAP + 1
         if longest > LONGEST:      # (the walker has ended every path within path_cases.CAP; the suite's rounds stay under half of it)
@@ -381,7 +504,7 @@ def main():
             made.append(Renderer(0).upload(scene, **kw))
             return made[-1]
         try:
-            rays += one_round(seed, make)
+            rays += one_round(seed, make, a.lit)
         finally:
             for r in made:
                 r.close()

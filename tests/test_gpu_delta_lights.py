@@ -1,7 +1,8 @@
 """Delta lights (point, spot, directional) on the device, against tests/delta_lights_ref.py: the twin bit for bit, one diffuse quad
 under one point light against the closed form, whole paths byte for byte -- nori_hip_li, the megakernel's and the wavefront
 engine's frames, with equal ray counts -- on a box with mirror, glass, microfacet, a textured wall and an area emitter, with an
-environment, in fog, and with the delta lights as the only lights; path_ems against path_mis statistically; unsetting, the upload
+environment, in fog, and with the delta lights as the only lights, and on three scenes of many area lights whose emitter tables lie
+outside the LDS (one per delta-light set); a light nearer than 2 kEpsilon; path_ems against path_mis statistically; unsetting, the upload
 and every refusal.  tests/test_delta_lights_cpu.py shows without a GPU that the inputs used here (tests/delta_light_cases.py) reach
 every new branch and that a branch taken wrongly changes their radiance."""
 from __future__ import annotations
@@ -12,7 +13,7 @@ import pytest
 from nori_amd import NoriError, _capi
 from nori_amd.render import DeviceGroup, Renderer
 from nori_amd.scene import Light, Medium
-from tests import delta_light_cases as dc, delta_lights_ref as dl, path_cases as pc, stat_harness as sh
+from tests import delta_light_cases as dc, delta_lights_ref as dl, light_cases as lc, path_cases as pc, stat_harness as sh
 from tests.backends import Oracle
 
 pytestmark = pytest.mark.gpu
@@ -141,6 +142,33 @@ def test_the_umbra_of_an_occluder_is_exactly_zero_with_equal_ray_counts(renderer
         assert not got[inside].any() and (got[on_quad & ~inside] > 0).any()
 
 
+def test_a_light_nearer_than_two_epsilon_leaves_an_empty_shadow_interval(renderer_factory):
+    """The header's rule for dist < 2 kEpsilon: maxt = dist - kEpsilon lies below the shadow ray's mint (below 0 for dist < kEpsilon),
+    no t satisfies mint <= t <= maxt, the ray is traced and counted and the sample is added.  256 rays aimed at the quad around the
+    foot of a point light 3e-5 above it, at 0 to 4e-4 from the foot: both sides of dist = kEpsilon and of dist = 2 kEpsilon."""
+    near = Light("point", position=(0.3, 3e-5, -0.2), intensity=(1e-8, 2e-8, 3e-8))
+    k = np.arange(256)
+    rad, ang = 4e-4 * k / 256, 2.399963 * k
+    target = np.stack([0.3 + rad * np.cos(ang), np.zeros(256), -0.2 + rad * np.sin(ang)], 1)
+    idx, seq = k.astype(np.uint64), np.full(256, 7, np.uint64)
+    f = Oracle.pcg32_floats(idx, seq, 4 + dc.CAP * dl.DRAWS_PER_VERTEX)
+    for integ in dc.INTEGRATORS:
+        sc = dc.quad_scene(integ)
+        sc.lights = [near]
+        oracle = Oracle(sc, use_bvh=True)
+        rays = oracle.sample_rays(np.full((256, 2), 32.0, F)).copy()
+        d = target - rays["o"].astype(np.float64)
+        rays["d"] = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(F)
+        want, nc, ns, ev = dl.walk(oracle, sc, integ, rays, f, max_vertices=dc.CAP)
+        below_eps = int(((ev["delta_empty_interval"] > 0) & (np.linalg.norm(target - near.position, axis=1) < 1e-4)).sum())
+        print(integ, "paths with maxt < mint:", int((ev["delta_empty_interval"] > 0).sum()), "of them with maxt < 0:", below_eps, "shadow rays", ns)
+        assert (ev["delta_empty_interval"] > 0).sum() >= 64 and below_eps >= 16 and (ev["delta_shadow"] > ev["delta_empty_interval"]).sum() >= 64
+        assert (want[ev["delta_empty_interval"] > 0] > 0).all()      # lit: nothing lies in an empty interval
+        got = renderer_factory(sc).li(rays, idx, seq)
+        print(integ, differing(got, want), "of 256 paths differ")
+        assert got.tobytes() == want.tobytes(), (integ, differing(got, want))
+
+
 # ------------------------------------------------------------------ 3., 4. whole paths, byte for byte
 @pytest.mark.parametrize("integrator", dc.INTEGRATORS)
 @pytest.mark.parametrize("case", list(dc.CASES))
@@ -149,6 +177,11 @@ def test_paths_equal_the_reference_bit_for_bit(renderer_factory, case, integrato
     r = renderer_factory(sc)
     assert len(r.lights) == len(sc.lights) and (r.medium is not None) == (sc.medium is not None) and (r.environment_size > 0) == (sc.environment is not None)
     assert (r.emitter_tables()["n_emitters"] == 0) == case.endswith(("lights_only", "lights_only_sky"))
+    # the emitter tables: in the LDS, or -- the OUTSIDE_LDS cases -- read from global memory (wf_shade's LDSTAB = false variants)
+    assert lc.fits(lc.table_counts(sc)) == (case not in dc.OUTSIDE_LDS)
+    if case in dc.OUTSIDE_LDS:
+        assert not lc.fits(lc.table_counts(sc))
+    w, h = dc.size_of(case)
     # 1. Li of the stated rays, its stream seeded like the render's and drawn from the start: 1024 paths of each of four samples
     per = dc.N_LI // len(dc.SAMPLES)
     for s in dc.SAMPLES:
@@ -160,11 +193,11 @@ def test_paths_equal_the_reference_bit_for_bit(renderer_factory, case, integrato
     frames = {}
     for s in dc.SAMPLES:
         want, nc, ns, _ = dc.reference(case, integrator, s)
-        assert (want > 0).any() and nc > dc.W * dc.H and ns > 0
+        assert (want > 0).any() and nc > w * h and ns > 0
         for engine in ENGINES:
             r.set_option("engine", engine)
             frame, st = r.render_host(spp_count=1, spp_begin=s)
-            assert st["engine"] == ENGINES.index(engine) and st["n_camera_samples"] == dc.W * dc.H
+            assert st["engine"] == ENGINES.index(engine) and st["n_camera_samples"] == w * h and frame.shape == (h, w, 4)
             got = frame[..., :3].reshape(-1, 3)
             print(case, integrator, engine, s, ":", differing(got, want), "paths differ; rays", st["n_closest_rays"], st["n_shadow_rays"], "want", nc, ns)
             assert got.tobytes() == want.tobytes(), (case, integrator, engine, s, differing(got, want))
@@ -174,7 +207,7 @@ def test_paths_equal_the_reference_bit_for_bit(renderer_factory, case, integrato
                 assert st["wf_record"] == "full"
             frames[engine, s] = frame
     # 3. a quarter of the samples in flight: regeneration, many passes, wf_finish
-    r.set_option("wavefront_paths", dc.W * dc.H // 4)
+    r.set_option("wavefront_paths", w * h // 4)
     small, st = r.render_host(spp_count=1, spp_begin=dc.SAMPLES[-1])
     assert st["engine"] == 1 and st["n_invalid"] == 0
     assert small.tobytes() == frames["wavefront", dc.SAMPLES[-1]].tobytes()

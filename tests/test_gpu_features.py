@@ -111,6 +111,42 @@ def test_every_sample_bit_for_bit_on_wide_nodes(renderer_factory):
     _per_sample(r, "A")
 
 
+TOP = 2 ** 32 - 1      # the last sample index: spp_begin + spp_count is 2^32 there, one past uint32
+
+
+def test_the_top_of_the_sample_range(renderer_factory):
+    """The pass counts a chunk's samples relative to spp_begin, as render_kernel does: the sample 2^32 - 1 is rendered (an end formed
+    in uint32 wraps to 0 and the pass renders nothing, with success), alone bit for bit and as the last of three in one call."""
+    r = renderer_factory(scene_a("box"))
+    frames, st = r.render_features_host(spp_begin=TOP, spp_count=1)
+    _, vals = ref_samples("A", TOP, 1)
+    assert st["n_invalid"] == 0
+    print("sample 2^32 - 1: camera samples", st["n_camera_samples"], "of", W * H)
+    for n in NAMES:
+        f, want = frames[n], vals[n].reshape(H, W, 3)
+        print("sample 2^32 - 1", n, int((f[..., :3] != want).any(axis=-1).sum()), "pixels differ, weight", float(f[..., 3].sum()))
+    assert st["n_camera_samples"] == st["n_closest_rays"] == W * H
+    for n in NAMES:
+        f, want = frames[n], vals[n].reshape(H, W, 3)
+        assert f.shape == (H, W, 4) and (f[..., 3] == 1).all(), n
+        assert np.array_equal(f[..., :3], want), (n, int((f[..., :3] != want).any(axis=-1).sum()))
+    # [2^32 - 3, 2^32) in one call: the binary64 film of the three samples, and the three single-sample frames combined
+    singles = []
+    for s in (TOP - 2, TOP - 1, TOP):
+        one, s1 = r.render_features_host(spp_begin=s, spp_count=1)
+        _, v1 = ref_samples("A", s, 1)
+        assert s1["n_camera_samples"] == W * H and all(np.array_equal(one[n][..., :3], v1[n].reshape(H, W, 3)) for n in NAMES), s
+        singles.append(one)
+    three, st = r.render_features_host(spp_begin=TOP - 2, spp_count=3)
+    print("samples 2^32 - 3 .. 2^32 - 1: camera samples", st["n_camera_samples"], "of", 3 * W * H)
+    assert st["n_camera_samples"] == st["n_closest_rays"] == 3 * W * H and st["n_invalid"] == 0
+    check_films(three, "A", "box", TOP - 2, 3, "[2^32 - 3, 2^32)")
+    for n in NAMES:
+        total = sum(one[n].astype(np.float64) for one in singles)      # (the values are not negative: the sum of magnitudes is the sum)
+        assert (three[n][..., 3] == 3).all(), n
+        assert_within_summation_bound(three[n], total, total, np.full((H, W), 3, np.uint32), what=f"three single frames combined, {n}")
+
+
 # ------------------------------------------------------------------ 2. filtered frames
 @pytest.mark.parametrize("rf", ["gaussian", "tent", "gaussian5"])
 def test_filtered_frames_within_the_summation_bound(renderer_factory, rf):

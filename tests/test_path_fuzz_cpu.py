@@ -1,7 +1,8 @@
 """What the committed rounds of tests/path_fuzz.py (SEEDS) are worth, shown without a GPU: every path of every round ends well under
 the walker's cap, the rounds between them reach every counter of path_ref.EVENTS and show every departure of path_ref.MUTATIONS,
 they hold every kind of draw the generator has, and in the rounds with neither fog nor sky the CPU oracle's Li is a second witness
-of the walker.  tests/test_gpu_path_fuzz.py renders these very rounds and compares bytes."""
+of the walker.  The same for the lit rounds (LIT_SEEDS: the round of the seed with drawn delta lights) against
+tests/delta_lights_ref.py's counters and departures.  tests/test_gpu_path_fuzz.py renders these very rounds and compares bytes."""
 from __future__ import annotations
 
 import dataclasses
@@ -9,7 +10,7 @@ import dataclasses
 import numpy as np
 import pytest
 
-from tests import path_cases as pc, path_fuzz as pf, path_ref as pr
+from tests import delta_lights_ref as dl, path_cases as pc, path_fuzz as pf, path_ref as pr
 
 SEEDS = pf.SEEDS
 
@@ -135,3 +136,132 @@ def test_the_oracle_is_a_second_witness_where_there_is_neither_fog_nor_sky():
         want = o.li(rays, idx, seq)
         assert got.tobytes() == want.tobytes(), (pf.describe(seed), int((got != want).any(axis=1).sum()))
     print("plain rounds", plain, "of them without a texture", as_is)
+
+
+# ------------------------------------------------------------------ the lit rounds: scene_of(seed) with drawn delta lights
+LIT = pf.LIT_SEEDS
+
+
+def test_lit_seed_list():
+    run = sorted(LIT + tuple(pf.LIT_SKIPPED))
+    assert run == list(range(36, 60)) and not set(LIT) & set(pf.LIT_SKIPPED) and not set(run) & set(SEEDS + tuple(pf.SKIPPED))
+    assert 8 * len(pf.LIT_SKIPPED) <= len(run)      # at most one round in eight
+    for seed, longest in pf.LIT_SKIPPED.items():      # a seed is skipped for one reason only, and the reason is measured
+        assert pf.longest_path(seed, lit=True) == longest > pf.LONGEST, (seed, pf.longest_path(seed, lit=True))
+    print("LIT_SKIPPED", pf.LIT_SKIPPED, "LONGEST", pf.LONGEST)
+
+
+def test_a_lit_round_is_its_plain_round_with_lights():
+    """geometry, materials, textures, kind, lens, camera, builder, S and knobs are scene_of(seed)'s; the inputs and the oracle are shared"""
+    for seed in LIT:
+        (sc, b, kn), (lit, lb, lkn) = pf.scene_of(seed), pf.lit_scene_of(seed)
+        assert lit.meshes is sc.meshes and lit.textures is sc.textures and lit.camera is sc.camera and lit.medium is sc.medium and lit.environment is sc.environment
+        assert lb == b and {k: lkn[k] for k in kn} == kn and not sc.lights
+        assert lit.integrator.type == ("path_ems", "path_mis")[seed % 2] and len(lit.lights) == pf.light_count_of(seed) == len(lkn["light_classes"])
+        assert not (lit.medium is not None and any(l.type == "directional" for l in lit.lights))      # (the setter refuses it)
+
+
+def test_every_path_of_every_lit_round_ends():
+    longest = {seed: pf.longest_path(seed, lit=True) for seed in LIT}
+    print("longest path per lit seed", longest, "of all", max(longest.values()), "LONGEST", pf.LONGEST)
+    assert max(longest.values()) <= pf.LONGEST, longest
+    brightest = {}
+    for seed in LIT:
+        L, nc, ns, ev = pf.reference(seed, lit=True)
+        sc = pf.lit_scene_of(seed)[0]
+        assert L.shape == (sc.camera.width * sc.camera.height, 3) and int(ev["vertices"].sum()) == nc and ns > 0
+        assert np.isfinite(L).all()
+        brightest[seed] = float(L.max())
+    print("largest L per lit seed", brightest)
+
+
+def test_every_light_counter_is_reached_in_two_lit_rounds():
+    names = dl.EVENTS + dl.FUZZ_EVENTS
+    rounds = {k: [seed for seed in LIT if _paths(pf.reference(seed, lit=True)[3], k) >= 8] for k in names}
+    for seed in LIT:
+        print(seed, {k: _paths(pf.reference(seed, lit=True)[3], k) for k in names})
+    print("lit rounds with at least 8 paths", rounds)
+    for k in names:
+        assert len(rounds[k]) >= 2, (k, rounds[k])
+
+
+@pytest.mark.parametrize("name", list(dl.MUTATIONS))
+def test_every_light_departure_changes_paths_of_the_lit_rounds(name):
+    """the loop of test_every_departure_changes_paths_of_the_rounds over the lit rounds and delta_lights_ref.MUTATIONS"""
+    counters = dl.MUTATIONS[name]
+    counters = (counters,) if isinstance(counters, str) else counters
+    shown = {}
+    for seed in LIT:
+        L, _, _, ev = pf.reference(seed, lit=True)
+        reached = sum(ev[k] for k in counters) > 0
+        if not reached.any() or (name == "env_at_unshifted_index" and pf.lit_scene_of(seed)[0].environment is None):
+            continue
+        M = pf.walk(seed, mutate=name, lit=True)[0]
+        differs = (L.view(np.uint32) != M.view(np.uint32)).any(axis=1)
+        assert not (differs & ~reached).any(), (name, seed)
+        shown[seed] = int(differs.sum())
+        if sum(shown.values()) >= 16:
+            break
+    print(name, "paths changed per lit round", shown)
+    assert sum(shown.values()) >= 8, (name, shown)
+
+
+def test_the_lit_rounds_hold_every_kind_of_light_draw():
+    rounds = [pf.lit_scene_of(seed) for seed in LIT]
+    kinds_of = {}
+    for sc, _, kn in rounds:
+        kinds_of.setdefault(len(sc.lights), []).append(kn["kind"])
+    print("light counts -> kinds", kinds_of)
+    assert set(kinds_of) == set(pf.LIGHT_COUNTS)
+    assert all(len(set(v)) >= 2 for v in kinds_of.values())                               # every count under at least two kinds
+    assert len(kinds_of[4096]) >= 2
+    assert sum(kn["kind"] == "fog" and len(sc.lights) >= 17 for sc, _, kn in rounds) >= 2
+    assert {l.type for sc, _, _ in rounds for l in sc.lights} == {"point", "spot", "directional"}
+    for seed, (sc, _, kn) in zip(LIT, rounds):
+        classes, cones = kn["light_classes"], kn["light_cones"]
+        assert len(classes) == len(cones) == len(sc.lights)
+        for l, c, k in zip(sc.lights, classes, cones):
+            assert (c == -1) == (l.type == "directional") and (k != -1) == (l.type == "spot")
+            assert all(0.0 == x or 0.2 <= x <= 6.0 for x in l.intensity)
+            if l.type == "spot":
+                assert (l.cos_inner, l.cos_outer) == pf.cone_cosines(*pf.CONES[k]) and np.float32(l.cos_outer) <= np.float32(l.cos_inner)
+        if len(sc.lights) >= 8:                                                            # in turn: all of them
+            assert set(classes) - {-1} == set(range(len(pf.POSITION_CLASSES))), pf.describe(seed, True)
+        # the positions are what their class says
+        eye = sc.camera.to_world[:3, 3]
+        verts = np.concatenate([m.positions for m in sc.meshes if m.name.startswith("sphere")])
+        for l, c in zip(sc.lights, classes):
+            p = np.array(l.position, np.float32)
+            name = pf.POSITION_CLASSES[c] if c >= 0 else None
+            if name == "in_a_wall_plane":
+                assert p[1] == 2.0 or abs(p[0]) == 1.0
+            elif name in ("just_inside_a_wall", "just_outside_a_wall"):
+                off = np.concatenate([np.abs(np.abs(p[[0, 2]]) - 1.0), np.abs(p[1:2]), np.abs(p[1:2] - 2.0)]).min()
+                outside = (np.abs(p[[0, 2]]) > 1.0).any() or p[1] < 0.0 or p[1] > 2.0
+                assert 4e-5 < off < 6e-5 and outside == (name == "just_outside_a_wall")
+            elif name == "at_a_sphere_vertex":
+                assert (verts == p).all(axis=1).any()
+            elif name == "at_the_eye":
+                assert (p == eye).all()
+            elif name == "above_the_box":
+                assert p[1] == 5.0
+    every = [l for sc, _, _ in rounds for l in sc.lights]
+    assert {(l.cos_inner, l.cos_outer) for l in every if l.type == "spot"} == {pf.cone_cosines(*c) for c in pf.CONES}
+    black = sum(not any(l.intensity) for l in every) / len(every)
+    one_zero = sum(sorted(x == 0 for x in l.intensity) == [False, False, True] for l in every) / len(every)
+    print("black lights", black, "one channel at zero", one_zero)
+    assert 0.07 < black < 0.13 and 0.10 < one_zero < 0.18                                   # a tenth; a further seventh of all
+    # a light at the centroid of a glass body, and of an opaque one
+    inside = {m.bsdf.type for sc, _, kn in rounds for l, c in zip(sc.lights, kn["light_classes"]) if c == 5
+              for m in sc.meshes if m.name.startswith("sphere") and np.abs(m.positions.astype(np.float64).mean(axis=0) - l.position).max() < 1e-6}
+    assert "dielectric" in inside and inside - {"dielectric"}, inside
+    # the combinations: the device's builders, a lens, the last sample index, fog, a sky as the only other light
+    assert {b for _, b, _ in rounds} == {0, 1, 2}
+    assert any(sc.camera.aperture_radius > 0 for sc, _, _ in rounds) and any(kn["S"] == (1 << 32) - 1 for _, _, kn in rounds)
+    assert any(kn["S"] == 1 << 31 for _, _, kn in rounds) and any(kn["inside_glass"] for _, _, kn in rounds)
+    assert any(sc.medium is not None for sc, _, _ in rounds)
+    assert any(sc.environment is not None and not any(m.radiance is not None for m in sc.meshes) for sc, _, _ in rounds)
+    assert {sc.integrator.type for sc, _, _ in rounds} == {"path_ems", "path_mis"}
+    for sc, _, _ in rounds:
+        w, h = sc.camera.width, sc.camera.height
+        assert w <= 40 and h <= 40 and sc.n_triangles <= 800 and sc.sample_count == 1 and len(sc.lights) <= 4096
