@@ -535,6 +535,19 @@ int nori_hip_debug_emitter_tables(nori_hip_ctx *ctx, uint32_t counts[3], uint32_
  * Needs a built tree: NORI_ERR_INVALID_ARGUMENT before nori_hip_build_accel succeeded; the context stays usable. */
 int nori_hip_debug_tree(nori_hip_ctx *ctx, int32_t *root, uint32_t counts[4], float *nodes, uint32_t *nodes32, float grid[6], float *pairs);
 
+/* The per-tile candidate lists of the wavefront engine's first pass (first_lists.h), built on the device and read back: one launch
+ * of wf_first_build -- the kernel a render launches, unchanged -- over the 16 x 16 tile grid a render of the context's camera uses
+ * (tiles_x = ceil(width / 16), tiles_y = ceil(height / 16), tile = ty tiles_x + tx), with the cap K, into buffers of this call's
+ * own, which are copied out and freed.  The lists the engine keeps for its renders are neither read nor touched, and the
+ * NORI_HIP_WF_FIRST* switches are not read: the call answers for any K whatever a render of this process would do.
+ * count[tile] (tiles_x tiles_y words) is the kernel's own encoding: the number of pair records in the tile's list, or 0xffffffff
+ * for an overflow tile (more than K pairs, or no pyramid); pairs[tile max(K, 1) + k], k < count[tile], are the indices of those pair
+ * records in the tree's pair array (nori_hip_debug_tree), in the order the walk found them; the other slots are 0.
+ * K > 64 (the most a list may hold) and a context without a built tree are NORI_ERR_INVALID_ARGUMENT with a message; the context
+ * stays usable.  A lens, a wide tree and a root that is a leaf are not refused: first_camera gives such a scene ok = 0, so every
+ * tile comes back as overflow -- as K = 0 does.  Synchronous, on the default stream, after a device synchronise. */
+int nori_hip_debug_first_lists(nori_hip_ctx *ctx, uint32_t K, uint32_t *count, uint32_t *pairs);
+
 /* wf_extend -- the traversal kernel of the wavefront engine -- on n rays of the caller's choosing, all arrays in HOST memory.
  * Slot k is a stored path vertex as wf_shade would have left it: origin origins[3 k ..] (both rays start there, with the mint every
  * stored ray has, 1e-4), a continuation ray dir_a[3 k ..] (slot A: closest hit, maxt = inf) and / or a shadow ray dir_b[4 k ..] =

@@ -234,6 +234,7 @@ HIP_PROTOTYPES = {
     "nori_hip_debug_emitter_sample": (C.c_int, [_P, C.c_int, _P, C.c_size_t, _P, _P, _P]),
     "nori_hip_debug_emitter_tables": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
     "nori_hip_debug_tree": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "nori_hip_debug_first_lists": (C.c_int, [_P, C.c_uint32, _P, _P]),
     "nori_hip_debug_extend": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_int, _P, _P]),
     "nori_hip_pcg32_floats": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_uint32, _P]),
     "nori_hip_pcg32_floats_at": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_size_t, C.c_uint32, _P]),

@@ -86,7 +86,10 @@ NORI_HD double first_root_diagonal(const DevScene &sc) {
     double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
     bool any = false;
     for (int k = 0; k < 2; ++k) {
-        if (!(h[k][0] < 1e37 && h[k][1] < 1e37 && h[k][2] < 1e37)) continue;      /* unbounded (kBoxHalfInf) */
+        /* unbounded: box_centre_half (rt_types.h) stores such an axis as h = kBoxHalfInf -- 2^59, a finite number: a test against
+           1e37 here took the subtree of the collinear triangles for a box 1e18 wide, and the pad that came of it culled nothing */
+        const double inf = (double) kBoxHalfInf;
+        if (!(h[k][0] < inf && h[k][1] < inf && h[k][2] < inf)) continue;
         any = true;
         for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], c[k][a] - h[k][a]); hi[a] = fmax(hi[a], c[k][a] + h[k][a]); }
     }

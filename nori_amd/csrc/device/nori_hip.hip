@@ -1122,6 +1122,21 @@ int nori_hip_debug_tree(nori_hip_ctx *ctx, int32_t *root, uint32_t counts[4], fl
     return NORI_OK;
 }
 
+int nori_hip_debug_first_lists(nori_hip_ctx *ctx, uint32_t K, uint32_t *count, uint32_t *pairs) {
+    if (!ctx) return NORI_ERR_INVALID_ARGUMENT;
+    if (!ctx->have_accel) { ctx->error = "debug_first_lists: no acceleration structure built"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (!count || !pairs) { ctx->error = "debug_first_lists: count and pairs must not be NULL"; return NORI_ERR_INVALID_ARGUMENT; }
+    if (K > 64u) { ctx->error = "debug_first_lists: K = " + std::to_string(K) + ", a list holds at most 64 pairs"; return NORI_ERR_INVALID_ARGUMENT; }
+    DeviceGuard g(ctx->device);
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    const std::string err = wf_first_debug_lists(ctx->dev, K, count, pairs);
+    if (!err.empty()) {
+        ctx->error = "debug_first_lists: " + err;
+        return err.find("out of memory") != std::string::npos ? NORI_ERR_OUT_OF_MEMORY : NORI_ERR_INTERNAL;
+    }
+    return NORI_OK;
+}
+
 int nori_hip_debug_extend(nori_hip_ctx *ctx, const float *origins, const float *dir_a, const float *dir_b, const uint32_t *flags, size_t n,
                           int count_traversal, float *hits, unsigned long long counts[4]) {
     REQUIRE_ACCEL(ctx);

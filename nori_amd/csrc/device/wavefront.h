@@ -92,6 +92,9 @@ void wf_first_selected(const WfFirstLists &lists, uint32_t tile_mod, uint32_t ti
    as many lanes as the traversal-stack spill buffer was sized for */
 void wf_first_launch_extend(const WfFirstLists &lists, const DevScene &sc, const void *wf_buf, int cur, const void *batch, int grid, void *stream);
 void wavefront_invalidate(WfEngine *engine);
+/* nori_hip_debug_first_lists (include/nori_hip.h): wf_first_build for the 16 x 16 tiles of sc's frame at cap K into buffers of the
+   call's own; count[n_tiles] and pairs[n_tiles][max(K, 1)] in HOST memory.  Synchronous on the default stream; touches no engine. */
+std::string wf_first_debug_lists(const DevScene &sc, uint32_t K, uint32_t *count, uint32_t *pairs);
 
 /* -DNORI_COUNT_EXCURSIONS builds: adds this translation unit's excursion counters (rt_types.h) to out[4], optionally
    resetting them; false in the product build */

@@ -226,6 +226,30 @@ void wf_first_selected(const WfFirstLists &f, uint32_t tile_mod, uint32_t tile_r
     }
 }
 
+/* nori_hip_debug_first_lists: wf_first_build over the frame's tiles into buffers of this call's own, copied out.  Neither the
+   engine's lists nor the switches above are looked at. */
+std::string wf_first_debug_lists(const DevScene &sc, uint32_t K, uint32_t *count, uint32_t *pairs) {
+    if (K > kFirstListMaxK) return "K = " + std::to_string(K) + " is more than a list may hold (" + std::to_string(kFirstListMaxK) + ")";
+    if (sc.camera.width <= 0 || sc.camera.height <= 0) return "the camera has no pixels";
+    const uint32_t tiles_x = (uint32_t) (sc.camera.width + kTile - 1) / kTile, tiles_y = (uint32_t) (sc.camera.height + kTile - 1) / kTile;
+    const uint32_t n_tiles = tiles_x * tiles_y;
+    const size_t pair_bytes = (size_t) n_tiles * std::max(1u, K) * sizeof(uint32_t), count_bytes = (size_t) n_tiles * sizeof(uint32_t);
+    uint32_t *d_pairs = nullptr, *d_count = nullptr;
+    hipError_t rc = hipMalloc((void **) &d_pairs, pair_bytes);
+    if (rc == hipSuccess) rc = hipMalloc((void **) &d_count, count_bytes);
+    if (rc == hipSuccess) rc = hipMemset(d_pairs, 0, pair_bytes);      /* (slots past a tile's count read as 0) */
+    if (rc == hipSuccess) rc = hipMemset(d_count, 0, count_bytes);
+    if (rc == hipSuccess) {
+        hipLaunchKernelGGL(wf_first_build, dim3((n_tiles + 63u) / 64u), dim3(64), 0, (hipStream_t) nullptr, sc, tiles_x, n_tiles, K, d_pairs, d_count);
+        rc = hipGetLastError();
+    }
+    if (rc == hipSuccess) rc = hipMemcpy(count, d_count, count_bytes, hipMemcpyDeviceToHost);
+    if (rc == hipSuccess) rc = hipMemcpy(pairs, d_pairs, pair_bytes, hipMemcpyDeviceToHost);
+    if (d_pairs) (void) hipFree(d_pairs);
+    if (d_count) (void) hipFree(d_count);
+    return rc == hipSuccess ? std::string() : std::string("wf_first_build: ") + hipGetErrorString(rc);
+}
+
 void wf_first_launch_extend(const WfFirstLists &f, const DevScene &sc, const void *wf_buf, int cur, const void *batch, int grid, void *stream) {
     hipStream_t s = (hipStream_t) stream;
     const WfBuf &b = *static_cast<const WfBuf *>(wf_buf);

@@ -386,6 +386,15 @@ class Renderer:
         [n_nodes, 8] uint32, grid_mn [3], grid_scale [3] float32."""
         return read_tree(lambda *a: self._check(self._lib.nori_hip_debug_tree(self._h, *a), "debug_tree"))
 
+    def first_lists(self, K: int):
+        """(count [n_tiles] uint32, pairs [n_tiles, max(K, 1)] uint32): the per-tile candidate lists of the first pass as the device
+        builds them for the context's camera at cap K (include/nori_hip.h: nori_hip_debug_first_lists).  count is the number of
+        pair records of a tile's list or 0xffffffff (an overflow tile); pairs[tile, :count] index Renderer.tree()["pairs"]."""
+        ty, tx = self.tile_grid()
+        count, pairs = np.zeros(ty * tx, np.uint32), np.zeros((ty * tx, max(int(K), 1)), np.uint32)
+        self._check(self._lib.nori_hip_debug_first_lists(self._h, int(K), ptr(count), ptr(pairs)), "debug_first_lists")
+        return count, pairs
+
     def extend(self, origins, dir_a=None, dir_b=None, maxt_b=None, flags=None, count_traversal=False):
         """wf_extend, the wavefront engine's traversal kernel, on rays of the caller's (include/nori_hip.h: nori_hip_debug_extend).
         Slot k starts at origins[k]; dir_a [n, 3]: its continuation ray (closest hit), dir_b [n, 3] with maxt_b [n] (default inf): its

@@ -16,8 +16,8 @@ import pytest
 
 from nori_amd import _capi as capi
 from nori_amd import workloads
-from nori_amd.scene import Bsdf, Camera, Integrator, Mesh, RFilter, Scene
 from tests import scenes
+from tests.first_list_cases import case, filler, only_clipped, tiny_scene, tri_mesh      # noqa: F401 (the helpers keep their names here)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -171,24 +171,7 @@ def test_cornell_box_small_frames(lib, size):
 
 
 # ------------------------------------------------------------------------------------------------ adversarial cases, tiny frames
-def tri_mesh(tris, name="t"):
-    v = np.asarray(tris, dtype=np.float32).reshape(-1, 3)
-    f = np.arange(v.shape[0], dtype=np.uint32).reshape(-1, 3)
-    return Mesh(v, f, bsdf=Bsdf("diffuse"), name=name)
-
-
-def tiny_scene(meshes, origin=(0, 0, 4), target=(0, 0, 0), size=(32, 32), fov=45.0, near=1e-4, far=1e4):
-    cam = Camera(size[0], size[1], fov, near_clip=near, far_clip=far, to_world=scenes.lookat(origin, target, (0, 1, 0)))
-    return Scene(meshes, cam, RFilter(), Integrator("normals"), 1)
-
-
-def filler(n=40, seed=3):
-    """small triangles spread over the view, so that the tree has inner nodes to cull"""
-    rng = np.random.default_rng(seed)
-    c = rng.uniform(-1.5, 1.5, (n, 1, 3))
-    return tri_mesh((c + rng.uniform(-0.2, 0.2, (n, 3, 3))).astype(np.float32), "filler")
-
-
+# (the scenes live in tests/first_list_cases.py, which the GPU tests share)
 def check_tiny(lib, sc, what, builders=(0, 1), expect_hits=True):
     for builder in builders:
         h = Harness(lib, sc, builder=builder)
@@ -205,39 +188,27 @@ def check_tiny(lib, sc, what, builders=(0, 1), expect_hits=True):
 def test_edge_in_a_frustum_side_plane(lib):
     """a triangle edge on the plane x = 0, which for this camera (on the z axis, 32 pixels wide) is the side plane between the two
     tile columns -- and one on y = 0, between the rows"""
-    a = [[0, -1, 0], [0, 1, 0], [1.5, 0, 0]]
-    b = [[0, -1, -1], [0, 1, -1], [-1.5, 0, -1]]
-    c = [[-1, 0, 0.5], [1, 0, 0.5], [0, 1.2, 0.5]]
-    check_tiny(lib, tiny_scene([tri_mesh([a, b, c]), filler()]), "edge in a side plane")
+    check_tiny(lib, case("edge-in-a-side-plane"), "edge in a side plane")
 
 
 def test_triangle_spanning_the_camera_plane(lib):
-    big = [[-0.5, -0.6, -3], [0.5, -0.6, -3], [0, 0.4, 9]]      # from in front of the camera (z = 4) to behind it
-    check_tiny(lib, tiny_scene([tri_mesh([big]), filler()]), "triangle through the camera plane")
+    check_tiny(lib, case("through-the-camera-plane"), "triangle through the camera plane")
 
 
 def test_camera_inside_a_box(lib):
     """the camera inside the scene's box and inside leaf boxes: a shell of triangles around it"""
-    p, f, _ = scenes.icosphere(1, 1.0, (0, 0, 4))
-    shell = Mesh(p, f, bsdf=Bsdf("diffuse"), name="shell")
-    near_tri = [[-0.3, -0.3, 3.9], [0.3, -0.3, 3.9], [0, 0.3, 4.3]]      # its box holds the camera
-    check_tiny(lib, tiny_scene([shell, tri_mesh([near_tri]), filler()]), "camera inside boxes")
+    check_tiny(lib, case("camera-inside-boxes"), "camera inside boxes")
 
 
 def test_flat_boxes(lib):
     """axis-aligned triangles: zero-thickness boxes in x, y and z"""
-    t = [[[-1, -1, 0], [1, -1, 0], [0, 1, 0]], [[0.25, -1, -1], [0.25, 1, -1], [0.25, 0, 1]], [[-1, -0.25, -1], [1, -0.25, -1], [0, -0.25, 1]]]
-    check_tiny(lib, tiny_scene([tri_mesh(t), filler()]), "flat boxes")      # (the filler gives the tree inner nodes: a root that is a leaf gets no lists)
+    check_tiny(lib, case("flat-boxes"), "flat boxes")      # (the filler gives the tree inner nodes: a root that is a leaf gets no lists)
 
 
 def test_near_and_far_clip(lib):
     """one triangle in front of the near clip, one beyond the far clip, one between: only the last is ever hit, and the lists agree"""
-    t = [[[-0.05, -0.05, 3.95], [0.05, -0.05, 3.95], [0, 0.05, 3.95]],      # 0.05 from the camera, near = 0.5
-         [[-9, -9, -8], [9, -9, -8], [0, 9, -8]],                            # 12 away, far = 10
-         [[-1, -1, 0], [1, -1, 0], [0, 1, 0]]]
-    sc = tiny_scene([tri_mesh(t), filler(12)], near=0.5, far=10.0)
-    check_tiny(lib, sc, "near / far clip")
-    h = Harness(lib, tiny_scene([tri_mesh(t[:2])], near=0.5, far=10.0))
+    check_tiny(lib, case("near-and-far-clip"), "near / far clip")
+    h = Harness(lib, only_clipped())
     try:
         r = h.check(MAX_K, per_pixel=8, scan_every=1)
         assert_superset(r)
@@ -249,8 +220,7 @@ def test_near_and_far_clip(lib):
 def test_spatial_split_duplicates(lib):
     """long thin diagonal triangles among small ones: the device builders split them, so leaves hold duplicated references (more
     pair slots than triangles); duplicates give identical candidates"""
-    long_ones = [[[-1.8, -1.8, -1], [-1.7, -1.8, -1], [1.8, 1.8, 1]], [[-1.8, 1.8, 0.5], [-1.8, 1.7, 0.5], [1.8, -1.8, -0.5]]]
-    sc = tiny_scene([tri_mesh(long_ones, "long"), filler(200, seed=9)])
+    sc = case("split-duplicates")
     h = Harness(lib, sc, builder=1)
     try:
         n_tris = sum(m.indices.shape[0] for m in sc.meshes)
@@ -264,9 +234,7 @@ def test_axis_aligned_case_at_margin_zero(lib):
     """The exactly representable case: camera at (0, 0, 4) looking down -z with fov 90 (the tile borders of a 32 x 32 frame are the
     planes x = 0 and y = 0, slopes 0 and +-1), triangles with small-integer coordinates.  With margin 0 the lists must still hold
     every hit: the margin is not what makes the signs right."""
-    t = [[[-8, -8, 0], [8, -8, 0], [-8, 8, 0]], [[8, 8, 0], [-8, 8, 0], [8, -8, 0]],
-         [[0, 0, 1], [1, 0, 1], [0, 1, 1]], [[0, 0, 2], [-1, 0, 2], [0, -1, 2]], [[-1, 1, 1], [0, 1, 1], [-1, 0, 1]]]
-    sc = tiny_scene([tri_mesh(t)], fov=90.0)
+    sc = case("axis-aligned")
     for builder in (0, 1):
         h = Harness(lib, sc, builder=builder)
         try:
