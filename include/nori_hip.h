@@ -1299,6 +1299,91 @@ int nori_hip_light_incident(nori_hip_ctx *ctx, const uint32_t *light, const floa
 /* nori_hip_set_lights on every device's context (the upload resets them, as on one context) */
 int nori_hip_group_set_lights(nori_hip_group *group, uint32_t n, const nori_light_desc *lights);
 
+/* ------------------------------------------------------------------ Grid medium
+ *
+ * A heterogeneous medium: ONE per context, as an alternative to the homogeneous one -- setting either replaces the other, and
+ * nori_hip_set_medium with NULL unsets whichever is set.  An axis-aligned box [bmin, bmax] in world space holds nx ny nz voxels of
+ * float32 density rho, x fastest (voxel (x, y, z) is rho[(z ny + y) nx + x]); a voxel's extinction is sigma = sigma_scale rho.  The
+ * density is PIECEWISE CONSTANT (nearest voxel) and outside the box there is vacuum, so the optical depth along a ray is an exact
+ * finite sum over the voxels a 3-D DDA visits: the free flight is sampled by analytic inversion (regular tracking) and the
+ * transmittance is exp(-tau), deterministic.  Albedo and the Henyey-Greenstein g are the homogeneous medium's, and so is everything
+ * after the distance and the transmittance: every closest-hit answer still draws exactly one number xi_d and every emitter sample
+ * four, a medium vertex multiplies T by albedo and by nothing else, and its steps 1 - 5 are those of "Homogeneous participating
+ * medium".  It is a state of the context set after the upload and reset by the next; path_mats, path_ems and path_mis render it
+ * through sets of instantiations of their own (rt_path.h, kGridMedium: with and without delta lights), every other kernel is the
+ * kernel it was.  A DIRECTIONAL light and a grid medium are allowed together (the box bounds the walk, the transmittance from
+ * infinity is finite); an environment map is still refused -- no kernel set combines the two yet.
+ *
+ * Everything below is float32 without FMA contraction; 1 / x and a / b are the correctly rounded ones, log and exp the pinned ones
+ * (DESIGN.md section 5).  min, max and clamps are selects on ONE comparison, written out here, so signed zeros take one way.
+ *
+ *   Derived once, on the host.  per axis a:  cell_a = (bmax_a - bmin_a) / (float) n_a;  inv_cell_a = (float) n_a / (bmax_a - bmin_a).
+ *   walk(o, d, tmax, tau_stop).  t0 = 0;  t1 = tmax.  Per axis a, in the order x, y, z:
+ *       PARALLEL iff |d_a| < 2^-40.  A parallel axis never steps (step_a = 0); the ray MISSES unless bmin_a <= o_a < bmax_a -- a
+ *       point exactly on a plane belongs to the voxel ABOVE it, so o_a = bmax_a is outside.
+ *       Otherwise inv_a = 1 / d_a;  step_a = d_a > 0 ? 1 : -1;  ta = (bmin_a - o_a) inv_a;  tb = (bmax_a - o_a) inv_a;
+ *       tn = ta < tb ? ta : tb;  tf = ta < tb ? tb : ta;  t0 = tn > t0 ? tn : t0;  t1 = tf < t1 ? tf : t1.
+ *     The ray misses, too, if all three axes are parallel or unless t0 < t1.  A miss: tau = 0, no event, 0 voxels.
+ *     Entry voxel, per axis: p = o_a + d_a t0 (a parallel axis: p = o_a);  c = floor((p - bmin_a) inv_cell_a);
+ *       c = c >= 0 ? c : 0;  c = c <= n_a - 1 ? c : n_a - 1;  i_a = (int) c.  Again a point on a plane belongs to the voxel above it,
+ *       whichever way the ray travels: travelling down, its first segment is empty.
+ *     t_cur = t0;  tau = 0.  Then at most nx + ny + nz trips (by construction: every trip but the last moves ONE index by one
+ *     towards the face its axis leaves the box through, and the walk ends when an index leaves 0 .. n_a - 1):
+ *       Plane crossings come from the INTEGER plane index, never from an accumulated step:  k_a = i_a + (step_a > 0 ? 1 : 0);
+ *         t_a = ((bmin_a + (float) k_a cell_a) - o_a) inv_a;  a parallel axis: t_a = +inf.
+ *       Ties step x, then y, then z:  sx = t_x <= t_y && t_x <= t_z;  sy = !sx && t_y <= t_z;  t_next = sx ? t_x : sy ? t_y : t_z.
+ *       t_end = t_next < t1 ? t_next : t1;  sigma = sigma_scale rho[i];  len = t_end - t_cur;
+ *       tau_new = tau + sigma (len > 0 ? len : 0).  The voxel counts as visited.
+ *       EVENT iff sigma > 0 && tau_new >= tau_stop:  s = (t_cur + (tau_stop - tau) / sigma) + 0, and the walk ends (tau is the sum
+ *         BEFORE this voxel).
+ *       Else tau = tau_new;  the walk ends unless t_next < t1;  t_cur = t_next > t_cur ? t_next : t_cur;  the index of the stepping
+ *       axis moves by its step;  the walk ends if it left its range.
+ *   Distance(o, d, tmax, xi).     walk with tau_stop = -log(1 - xi):  s, or "no event" -- none before tmax or the box's far side.
+ *   Transmittance(o, d, dist).    exp(-tau) of walk(o, d, dist, +inf).  dist may be +inf.
+ *   In Li.                The closest-hit answer for the ray (o, d): xi_d is drawn as always;  walk with tmax = hit.t if something was
+ *                         hit, else +inf.  MEDIUM vertex iff there is an event && (nothing was hit || s < hit.t), at p = o + d s.
+ *                         No event and nothing hit: the path ends, like a miss without an environment.  An emitter sample's Ld is
+ *                         multiplied by Transmittance(p, dir, dist) -- p the vertex, dist as for the homogeneous medium, +inf for a
+ *                         directional light -- at surface and medium vertices alike; the MIS weights ignore it.
+ *   Coincidence.          A 1 x 1 x 1 grid with rho = 1 whose box holds the origin and every hit of a closed scene gives the BITS of the
+ *                         homogeneous medium with sigma_t = sigma_scale: t0 = 0, so s = (0 + q) + 0 with q = -log(1 - xi) / sigma_t,
+ *                         the event test sigma hit.t >= tau_stop holds whenever q < hit.t, and tau = 0 + sigma_t dist.
+ *   Domains.              Every divisor is a d_a with 2^-40 <= |d_a| (d is finite, |d_a| < 2^126) or a sigma in [1e-4, 1e4]: inside
+ *                         the verified domain of the device's reciprocal.  o and tmax are finite or, tmax, +inf.
+ *
+ * nori_hip_set_grid_medium      medium == NULL: unsets a grid medium (a homogeneous one stays).  Else the voxels are copied to the
+ *                               device and the medium is used from the next launch on, in place of any medium set before.
+ *                               NORI_ERR_NOT_READY before an upload; NORI_ERR_INVALID_ARGUMENT, with a message, for nx, ny or nz
+ *                               outside 1 .. 256, a box that is not finite with bmin < bmax on every axis, a sigma_scale that is not
+ *                               finite or negative, albedo or g outside the homogeneous medium's bounds, and for the first voxel --
+ *                               NAMED BY ITS INDEX -- whose rho is not finite or negative or whose sigma_scale rho is neither 0 nor
+ *                               within [1e-4, 1e4]; NORI_ERR_UNSUPPORTED, with a message, for an integrator other than the three
+ *                               path integrators and for a context with an environment map.  NORI_SEED_NORI_BLOCK renders refuse
+ *                               it as they refuse the homogeneous medium.  A failed call leaves the context's medium as it was.
+ * nori_hip_get_grid_medium      1 and the record as stored (rho NULL: the voxels are not read back; g: 0 where |g| < 1e-3) if a grid
+ *                               medium is set, 0 if none, or a negative status.  nori_hip_get_medium returns 0 while a grid medium is
+ *                               set, and this returns 0 while a homogeneous one is.
+ * nori_hip_grid_medium_distance       Distance of n queries (o, d: 3n; tmax, xi: n); "no event" is returned as +inf.
+ * nori_hip_grid_medium_transmittance  Transmittance of n queries.
+ * nori_hip_grid_medium_optical_depth  tau and the number of voxels visited of walk(o, d, tmax, +inf), so a failing walk can be read.
+ * The last three return NORI_ERR_NOT_READY, with a message, while no grid medium is set; nori_hip_medium_distance and
+ * nori_hip_medium_transmittance do while one is (the phase twins serve both kinds of medium). */
+typedef struct nori_grid_medium_desc {
+    const float *rho;      /* nx ny nz densities, x fastest; each finite and >= 0 */
+    int32_t nx, ny, nz;    /* each 1 .. 256 */
+    float bmin[3], bmax[3];/* the box, world space; bmin < bmax per axis */
+    float sigma_scale;     /* sigma = sigma_scale rho: 0, or 1e-4 .. 1e4 */
+    float albedo[3];       /* single-scattering albedo, each 0 .. 1 */
+    float g;               /* Henyey-Greenstein asymmetry, |g| <= 0.99; 0: isotropic */
+} nori_grid_medium_desc;
+int nori_hip_set_grid_medium(nori_hip_ctx *ctx, const nori_grid_medium_desc *medium);
+int nori_hip_get_grid_medium(const nori_hip_ctx *ctx, nori_grid_medium_desc *medium);
+int nori_hip_grid_medium_distance(nori_hip_ctx *ctx, const float *o, const float *d, const float *tmax, const float *xi, size_t n, float *s);
+int nori_hip_grid_medium_transmittance(nori_hip_ctx *ctx, const float *o, const float *d, const float *dist, size_t n, float *tr);
+int nori_hip_grid_medium_optical_depth(nori_hip_ctx *ctx, const float *o, const float *d, const float *tmax, size_t n, float *tau, int32_t *steps);
+/* nori_hip_set_grid_medium on every device's context (the upload resets it, as on one context) */
+int nori_hip_group_set_grid_medium(nori_hip_group *group, const nori_grid_medium_desc *medium);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,10 @@ int nori_host_environment(const nori_host_root *root, nori_env_desc *out);
  * Returns 1 and fills *out if the scene has one, 0 if it has none, or a negative nori_status.  Not part of nori_scene_desc: apply
  * it after the upload. */
 int nori_host_medium(const nori_host_root *root, nori_medium_desc *out);
+/* Root is a <scene>: its grid medium (<medium type="grid">: a VOL file, sigmaScale, albedo, its <phase> child's g, boxMin / boxMax), the
+ * record nori_hip_set_grid_medium takes; the voxels are borrowed (valid until free).  Returns 1 and fills *out if the scene has one,
+ * 0 if it has none -- nori_host_medium returns 0 for a scene whose medium is a grid --, or a negative nori_status. */
+int nori_host_grid_medium(const nori_host_root *root, nori_grid_medium_desc *out);
 /* Root is a <scene>: its delta lights (<emitter type="point|spot|directional"> under the <scene>), the records nori_hip_set_lights
  * takes, in the file's order.  *n = their number; out[0 .. min(cap, *n)) is filled (out may be NULL).  Not part of nori_scene_desc:
  * apply them after the upload. */

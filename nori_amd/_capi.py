@@ -168,6 +168,12 @@ class MediumDesc(C.Structure):
     _fields_ = [("sigma_t", C.c_float), ("albedo", C.c_float * 3), ("g", C.c_float)]
 
 
+class GridMediumDesc(C.Structure):
+    """nori_grid_medium_desc"""
+    _fields_ = [("rho", C.c_void_p), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("bmin", C.c_float * 3), ("bmax", C.c_float * 3),
+                ("sigma_scale", C.c_float), ("albedo", C.c_float * 3), ("g", C.c_float)]
+
+
 class LightDesc(C.Structure):
     """nori_light_desc"""
     _fields_ = [("type", C.c_int32), ("position", C.c_float * 3), ("direction", C.c_float * 3), ("intensity", C.c_float * 3),
@@ -311,6 +317,12 @@ HIP_PROTOTYPES = {
     "nori_hip_get_lights": (C.c_int, [_P, C.c_uint32, C.POINTER(LightDesc), C.POINTER(C.c_uint32)]),
     "nori_hip_light_incident": (C.c_int, [_P, _P, _P, C.c_size_t, _P, _P, _P]),
     "nori_hip_group_set_lights": (C.c_int, [_P, C.c_uint32, C.POINTER(LightDesc)]),
+    "nori_hip_set_grid_medium": (C.c_int, [_P, C.POINTER(GridMediumDesc)]),
+    "nori_hip_get_grid_medium": (C.c_int, [_P, C.POINTER(GridMediumDesc)]),
+    "nori_hip_grid_medium_distance": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "nori_hip_grid_medium_transmittance": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P]),
+    "nori_hip_grid_medium_optical_depth": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, _P]),
+    "nori_hip_group_set_grid_medium": (C.c_int, [_P, C.POINTER(GridMediumDesc)]),
 }
 
 

@@ -1,4 +1,4 @@
-/* ctx.h -- the context behind the C ABI and what the entry points of nori_hip.hip, frame_api.hip, env_map.hip, medium.hip and lights.hip (those units only) need
+/* ctx.h -- the context behind the C ABI and what the entry points of nori_hip.hip, frame_api.hip, env_map.hip, medium.hip, grid_medium.hip and lights.hip (those units only) need
  * of it: the error mapping, the device guard, scratch buffers, the frame's sizes, the stats of a call. */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +33,8 @@ struct nori_hip_ctx {
     const float *d_env_weight = nullptr; /* its texel weights (nori_hip_debug_env_tables; the path reads the CDFs only) */
     void *d_lights = nullptr;            /* the delta lights (lights.hip): the array DevScene::lights points at */
     std::vector<LightRec> host_lights;   /* ... as stored (nori_hip_get_lights) */
+    void *d_grid_rho = nullptr;          /* the grid medium's voxels (grid_medium.hip): the array DevScene::gmed.rho points at */
+    nori_grid_medium_desc grid_desc = {};/* ... its record as stored, rho null (nori_hip_get_grid_medium) */
     float *d_filter = nullptr;
     const uint32_t *d_tri_mesh = nullptr;
     unsigned long long *d_stats = nullptr;
@@ -150,6 +152,9 @@ static inline size_t env_film_samples() { const char *e = getenv("NORI_HIP_FILM_
 void env_release(nori_hip_ctx *ctx);
 /* lights.hip: frees the context's delta lights and clears DevScene::lights / n_lights (an upload, nori_hip_destroy, a new set) */
 void lights_release(nori_hip_ctx *ctx);
+/* grid_medium.hip: frees the context's grid medium and clears DevScene::gmed and, if it was the grid's, DevScene::medium (an upload,
+   nori_hip_destroy, a new grid, a homogeneous medium set in its place) */
+void grid_medium_release(nori_hip_ctx *ctx);
 
 /* nori_hip.hip.  What a render refuses of its parameters, in order (features: the pass of nori_hip_render_features, which shares three of the
    refusals and has one of its own among them), and of them what a render by tile list refuses.  render_impl: every render -- share: the block rows of a

@@ -156,6 +156,11 @@ int nori_hip_set_environment(nori_hip_ctx *ctx, const nori_env_desc *env) {
         ctx->error = "set_environment: the whitted integrator has no environment variant (it samples emitters and would need kernels of its own); use path_mats, path_ems or path_mis";
         return NORI_ERR_UNSUPPORTED;
     }
+    if (ctx->dev.gmed.rho) {
+        ctx->error = "set_environment: the context has a grid medium, and no kernel set combines a grid medium with an environment map yet; "
+                     "unset the medium first (nori_hip_set_grid_medium with NULL)";
+        return NORI_ERR_UNSUPPORTED;
+    }
     if (ctx->dev.medium.on) {
         ctx->error = "set_environment: the context has a medium, and a medium that fills all space has zero transmittance to infinity; "
                      "unset the medium first (nori_hip_set_medium with NULL)";

@@ -439,6 +439,16 @@ int nori_hip_group_set_environment(nori_hip_group *g, const nori_env_desc *env) 
     return NORI_OK;
 }
 
+/* the grid medium of every context (nori_hip_set_grid_medium): all devices render one scene */
+int nori_hip_group_set_grid_medium(nori_hip_group *g, const nori_grid_medium_desc *medium) {
+    if (!g) return NORI_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < g->ctx.size(); ++k) {
+        const int rc = nori_hip_set_grid_medium(g->ctx[k], medium);
+        if (rc != NORI_OK) { g->error = "device " + std::to_string(g->devices[k]) + ": " + nori_hip_last_error(g->ctx[k]); return rc; }
+    }
+    return NORI_OK;
+}
+
 /* the medium of every context (nori_hip_set_medium): all devices render one scene */
 int nori_hip_group_set_medium(nori_hip_group *g, const nori_medium_desc *medium) {
     if (!g) return NORI_ERR_INVALID_ARGUMENT;

@@ -96,7 +96,7 @@ int nori_hip_set_lights(nori_hip_ctx *ctx, uint32_t n, const nori_light_desc *li
         ctx->error = "set_lights: only path_ems and path_mis render delta lights (path_mats cannot reach one; the other integrators have no variant for them)";
         return NORI_ERR_UNSUPPORTED;
     }
-    if (directional && ctx->dev.medium.on) {
+    if (directional && ctx->dev.medium.on && !ctx->dev.gmed.rho) {      /* (a grid medium is bounded by its box: the transmittance from infinity is finite) */
         ctx->error = "set_lights: a directional light in a context with a medium: the medium fills all space, so the transmittance from infinity is 0; "
                      "unset the medium first (nori_hip_set_medium with NULL)";
         return NORI_ERR_UNSUPPORTED;

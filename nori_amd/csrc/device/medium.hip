@@ -53,6 +53,8 @@ int nori_hip_set_medium(nori_hip_ctx *ctx, const nori_medium_desc *medium) {
     if (!ctx) return NORI_ERR_INVALID_ARGUMENT;
     if (!ctx->have_scene) { ctx->error = "set_medium: no scene uploaded"; return NORI_ERR_NOT_READY; }
     if (!medium) {      /* (a render still running has its own copy of the record: kernel arguments) */
+        DeviceGuard g(ctx->device);
+        grid_medium_release(ctx);      /* no medium of either kind */
         ctx->dev.medium = MediumRec();
         return NORI_OK;
     }
@@ -85,6 +87,10 @@ int nori_hip_set_medium(nori_hip_ctx *ctx, const nori_medium_desc *medium) {
                          "unset the lights first (nori_hip_set_lights with n = 0)";
             return NORI_ERR_UNSUPPORTED;
         }
+    {
+        DeviceGuard g(ctx->device);
+        grid_medium_release(ctx);      /* one medium per context: the homogeneous one replaces a grid (nori_hip_set_grid_medium) */
+    }
     ctx->dev.medium = medium_record(medium->sigma_t, medium->albedo, medium->g);
     return NORI_OK;
 }
@@ -92,6 +98,10 @@ int nori_hip_set_medium(nori_hip_ctx *ctx, const nori_medium_desc *medium) {
 int nori_hip_get_medium(const nori_hip_ctx *ctx, nori_medium_desc *medium) {
     if (!ctx) return NORI_ERR_INVALID_ARGUMENT;
     if (!ctx->have_scene) return NORI_ERR_NOT_READY;      /* (the context is const: no message) */
+    if (ctx->dev.gmed.rho) {      /* a grid medium is set (nori_hip_get_grid_medium reads it): none here */
+        if (medium) *medium = nori_medium_desc();
+        return 0;
+    }
     const MediumRec &m = ctx->dev.medium;
     if (medium) {
         medium->sigma_t = m.sigma_t; medium->g = m.g;
@@ -103,6 +113,7 @@ int nori_hip_get_medium(const nori_hip_ctx *ctx, nori_medium_desc *medium) {
 int nori_hip_medium_distance(nori_hip_ctx *ctx, const float *xi, size_t n, float *s) {
     const int ready = medium_ready(ctx, "medium_distance");
     if (ready != NORI_OK) return ready;
+    if (ctx->dev.gmed.rho) { ctx->error = "medium_distance: the context's medium is a grid (nori_hip_grid_medium_distance)"; return NORI_ERR_NOT_READY; }
     if (n == 0) return NORI_OK;
     if (!xi || !s) { ctx->error = "medium_distance: null array"; return NORI_ERR_INVALID_ARGUMENT; }
     DeviceGuard g(ctx->device);
@@ -117,6 +128,7 @@ int nori_hip_medium_distance(nori_hip_ctx *ctx, const float *xi, size_t n, float
 int nori_hip_medium_transmittance(nori_hip_ctx *ctx, const float *dist, size_t n, float *tr) {
     const int ready = medium_ready(ctx, "medium_transmittance");
     if (ready != NORI_OK) return ready;
+    if (ctx->dev.gmed.rho) { ctx->error = "medium_transmittance: the context's medium is a grid (nori_hip_grid_medium_transmittance)"; return NORI_ERR_NOT_READY; }
     if (n == 0) return NORI_OK;
     if (!dist || !tr) { ctx->error = "medium_transmittance: null array"; return NORI_ERR_INVALID_ARGUMENT; }
     DeviceGuard g(ctx->device);

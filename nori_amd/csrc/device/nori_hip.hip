@@ -560,6 +560,7 @@ void nori_hip_destroy(nori_hip_ctx *ctx) {
     free_pool(ctx->allocs_scene); free_pool(ctx->allocs_accel);
     env_release(ctx);
     lights_release(ctx);
+    grid_medium_release(ctx);
     wavefront_destroy(ctx->wf);
     film_release(ctx->film);
     film_moments_release(ctx->moments);
@@ -581,6 +582,7 @@ int nori_hip_upload_scene(nori_hip_ctx *ctx, const nori_scene_desc *scene) {
     DeviceGuard g(ctx->device);
     free_pool(ctx->allocs_scene); free_pool(ctx->allocs_accel);
     env_release(ctx);      /* the environment map is set after an upload and lasts until the next (nori_hip_set_environment) */
+    grid_medium_release(ctx);      /* and so is the grid medium (nori_hip_set_grid_medium) */
     memset(&ctx->dev.medium, 0, sizeof(ctx->dev.medium));      /* and so is the medium (nori_hip_set_medium) */
     lights_release(ctx);      /* and so are the delta lights (nori_hip_set_lights) */
     ctx->have_scene = ctx->have_accel = false;
@@ -913,13 +915,15 @@ static void launch_li(nori_hip_ctx *ctx, const nori_ray *r, size_t n, const uint
 #define LI_TEX(I) case I: if (ctx->dev.textured) { hipLaunchKernelGGL((li_kernel<I, STACK, kAnyBsdf | kTextured>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } \
                           else { hipLaunchKernelGGL((li_kernel<I, STACK>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); } break;
 #define LI_SET(I, SET) hipLaunchKernelGGL((li_kernel<I, STACK, SET>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb)
-#define LI_ENV_(I) if (ctx->dev.medium.on) { LI_SET(I, kAnyBsdf | kTextured | kMedium); } \
+#define LI_ENV_(I) if (ctx->dev.gmed.rho) { LI_SET(I, kAnyBsdf | kTextured | kMedium | kGridMedium); } \
+                   else if (ctx->dev.medium.on) { LI_SET(I, kAnyBsdf | kTextured | kMedium); } \
                    else if (ctx->dev.env) { LI_SET(I, kAnyBsdf | kTextured | kEnvLit); } \
                    else if (ctx->dev.textured) { LI_SET(I, kAnyBsdf | kTextured); } \
                    else { hipLaunchKernelGGL((li_kernel<I, STACK>), grid, block, lds, 0, ctx->dev, r, n, ss, sq, rgb); }
 #define LI_ENV(I) case I: LI_ENV_(I) break;
 /* path_ems / path_mis: first the three sets of a context with delta lights (the lights; with a medium; with an environment) */
 #define LI_LIT(I) case I: if (!ctx->dev.n_lights) { LI_ENV_(I) } \
+                          else if (ctx->dev.gmed.rho) { LI_SET(I, kAnyBsdf | kTextured | kDeltaLit | kMedium | kGridMedium); } \
                           else if (ctx->dev.medium.on) { LI_SET(I, kAnyBsdf | kTextured | kDeltaLit | kMedium); } \
                           else if (ctx->dev.env) { LI_SET(I, kAnyBsdf | kTextured | kDeltaLit | kEnvLit); } \
                           else { LI_SET(I, kAnyBsdf | kTextured | kDeltaLit); } break;
@@ -1226,6 +1230,8 @@ static hipError_t launch_render_one(nori_hip_ctx *ctx, const RenderArgs &a, cons
         if (ctx->dev.env) kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured | kEnvLit>;
         /* and one for contexts with a medium: every BSDF, textures, the medium (kMedium; never with an environment) */
         if (ctx->dev.medium.on) kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured | kMedium>;
+        /* and one for contexts with a grid medium: that with the grid's walk (kGridMedium) */
+        if (ctx->dev.gmed.rho) kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured | kMedium | kGridMedium>;
     }
     /* path_ems / path_mis have three for contexts with delta lights: every BSDF, textures, the lights (kDeltaLit); that with an
        environment; that with a medium */
@@ -1234,6 +1240,7 @@ static hipError_t launch_render_one(nori_hip_ctx *ctx, const RenderArgs &a, cons
             kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured | kDeltaLit>;
             if (ctx->dev.env) kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured | kDeltaLit | kEnvLit>;
             if (ctx->dev.medium.on) kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured | kDeltaLit | kMedium>;
+            if (ctx->dev.gmed.rho) kern = render_kernel<INTEG, STACK, COUNT, kAnyBsdf | kTextured | kDeltaLit | kMedium | kGridMedium>;
         }
     }
     if (lds > 64 * 1024) {

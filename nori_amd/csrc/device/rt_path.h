@@ -20,6 +20,7 @@
 #include "rt_texture.h"
 #include "env_map.h"
 #include "medium.h"
+#include "grid_medium.h"
 #include "lights.h"
 #include "rt_trace.h"
 
@@ -110,12 +111,17 @@ NORI_HD uint32_t emitter_pick(const Tab &tab, uint32_t nE, float xiE, float xiT,
    kDeltaLit (bit 7): the context has delta lights (lights.h; DevScene::lights, n_lights > 0).  They are n_lights more lights in the
    emitter pick -- indices [n_emitters, n_emitters + n_lights), the environment moves to n_emitters + n_lights -- and the count
    enters every density that divides by the number of lights.  A delta light is never hit: its emitter sample carries the MIS
-   weight 1.  Without the bit none of that is compiled or read.  path_ems / path_mis only. */
+   weight 1.  Without the bit none of that is compiled or read.  path_ems / path_mis only.
+   kGridMedium (bit 8, only together with kMedium): the medium is the voxel grid of grid_medium.h (DevScene::gmed) instead of the
+   homogeneous one.  The free flight and the transmittance come from its walk; everything after them -- the medium vertex, Russian
+   roulette, the emitter sample through the phase function, the phase sample -- is kMedium's code.  A ray that leaves the box
+   without an event and hits nothing ends the path.  Without the bit none of that is compiled or read. */
 constexpr int kAnyBsdf = 0xf;
 constexpr int kTextured = 0x10;
 constexpr int kEnvLit = 0x20;
 constexpr int kMedium = 0x40;
 constexpr int kDeltaLit = 0x80;
+constexpr int kGridMedium = 0x100;
 
 /* the lights of the emitter pick: the area emitters, then the delta lights, then the environment */
 template <int MATSET> NORI_HD uint32_t light_count(const DevScene &sc) {
@@ -168,7 +174,8 @@ NORI_HD bool sample_direct_lit(const DevScene &sc, const Tab &tab, const Surface
         rad = mk3(m.radiance[0], m.radiance[1], m.radiance[2]);
     }
     float tr = 1.0f;
-    if (MATSET & kMedium) tr = medium_tr(sc.medium, dist);
+    if (MATSET & kGridMedium) tr = grid_tr(sc.gmed, s.p, dir, dist);      /* (a directional light: dist is infinite, the box bounds the walk) */
+    else if (MATSET & kMedium) tr = medium_tr(sc.medium, dist);
     out.dir = dir;
     out.maxt = maxt;
     if ((MATSET & kMedium) && med) {
@@ -236,7 +243,8 @@ NORI_HD bool sample_direct(const DevScene &sc, const Tab &tab, Rng &rng, const S
     const float cosY = dot(n, -dir);
     if (!(cosY > 0.0f)) return false;
     float tr = 1.0f;      /* (evaluated here, where the fewest values are alive: it runs in binary64) */
-    if (MATSET & kMedium) tr = medium_tr(sc.medium, dist);
+    if (MATSET & kGridMedium) tr = grid_tr(sc.gmed, s.p, dir, dist);
+    else if (MATSET & kMedium) tr = medium_tr(sc.medium, dist);
     if ((MATSET & kMedium) && med) {
         const float ph = hg_eval(sc.medium, dot(d, dir));
         const float pdfA = m.inv_area * pdfPick;
@@ -291,7 +299,12 @@ NORI_HD bool path_on_closest(const DevScene &sc, const Tab &tab, PathState &st, 
        shares the surface vertex's Russian roulette, emitter sample and tail below; what only a surface has is skipped */
     bool med = false;
     f3 pm = mk3(0.0f);
-    if ((MATSET & kMedium) && INTEG >= INT_MATS) {
+    if ((MATSET & kGridMedium) && INTEG >= INT_MATS) {      /* the grid: an event only where the walk finds one before the surface */
+        float s;
+        const bool ev = grid_distance(sc.gmed, st.ray.o, d, found ? hit.t : kInf, rng_next_float(st.rng), s);
+        med = ev && (!found || s < hit.t);
+        pm = st.ray.o + d * s;
+    } else if ((MATSET & kMedium) && INTEG >= INT_MATS) {
         const float s = medium_distance(sc.medium, rng_next_float(st.rng));
         med = !found || s < hit.t;
         pm = st.ray.o + d * s;

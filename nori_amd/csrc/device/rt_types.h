@@ -354,6 +354,18 @@ struct MediumRec {
     uint32_t on = 0u;
 };
 
+/* the grid medium of the context (grid_medium.h; include/nori_hip.h, "Grid medium"): a box [bmin, bmax] of nx ny nz voxels of float32
+   density, x fastest, in device memory; the extinction of a voxel is sigma_scale rho.  Set by nori_hip_set_grid_medium, never by a
+   scene description.  cell = (bmax - bmin) / n and inv_cell = n / (bmax - bmin) are made once on the host, in float32.  While a grid
+   medium is set, DevScene::medium holds its albedo and phase function (on = 1, sigma_t = sigma_scale) and rho is not null. */
+struct GridMediumRec {
+    const float *rho = nullptr;
+    int32_t n[3] = {0, 0, 0};
+    float bmin[3] = {0.0f, 0.0f, 0.0f}, bmax[3] = {0.0f, 0.0f, 0.0f};
+    float cell[3] = {0.0f, 0.0f, 0.0f}, inv_cell[3] = {0.0f, 0.0f, 0.0f};
+    float sigma_scale = 0.0f;
+};
+
 /* a delta light of the context (lights.h; include/nori_hip.h, "Delta lights"): 48 bytes, nori_light_desc word for word with the
    direction normalised.  Set by nori_hip_set_lights, never by a scene description. */
 struct LightRec {
@@ -435,6 +447,8 @@ struct DevScene {
     const LightRec *lights;
     uint32_t n_lights;
     uint32_t lights_pad;
+    /* the grid medium (above); rho null: none -- and then the kernels compiled without kGridMedium run (rt_path.h), which never read it */
+    GridMediumRec gmed;
 };
 
 struct Hit {

@@ -54,6 +54,9 @@ void wf_medium_launch_finish(const DevScene &sc, const void *wf_buf, int cur, co
 /* wavefront_lights.hip: the same for contexts with delta lights -- MATSET kAnyBsdf | kTextured | kDeltaLit, and that with kEnvLit or kMedium */
 void wf_lights_launch_shade(const DevScene &sc, const void *wf_buf, int cur, const void *batch, int mode, int grid, hipStream_t s);
 void wf_lights_launch_finish(const DevScene &sc, const void *wf_buf, int cur, const void *batch, bool count, int grid, hipStream_t s);
+/* wavefront_grid_medium.hip: the same for contexts with a grid medium -- MATSET kAnyBsdf | kTextured | kMedium | kGridMedium, and that with kDeltaLit */
+void wf_grid_medium_launch_shade(const DevScene &sc, const void *wf_buf, int cur, const void *batch, int mode, int grid, hipStream_t s);
+void wf_grid_medium_launch_finish(const DevScene &sc, const void *wf_buf, int cur, const void *batch, bool count, int grid, hipStream_t s);
 }
 
 namespace {
@@ -569,6 +572,7 @@ bool record_compact(const DevScene &sc) {
 }
 
 void launch_shade(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt, int mode, int grid_, bool compact, hipStream_t s) {
+    if (sc.gmed.rho && sc.integrator.type >= INT_MATS) { wf_grid_medium_launch_shade(sc, &b, cur, &bt, mode, grid_, s); return; }      /* kGridMedium: wavefront_grid_medium.hip */
     if (sc.n_lights && sc.integrator.type >= INT_EMS) { wf_lights_launch_shade(sc, &b, cur, &bt, mode, grid_, s); return; }      /* kDeltaLit: wavefront_lights.hip */
     if (sc.env && sc.integrator.type >= INT_MATS) { wf_env_launch_shade(sc, &b, cur, &bt, mode, grid_, s); return; }      /* kEnvLit: wavefront_env.hip */
     if (sc.medium.on && sc.integrator.type >= INT_MATS) { wf_medium_launch_shade(sc, &b, cur, &bt, mode, grid_, s); return; }      /* kMedium: wavefront_medium.hip */
@@ -601,6 +605,7 @@ void launch_shade(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt
 }
 
 void launch_finish(const DevScene &sc, const WfBuf &b, int cur, const WfBatch &bt, bool count, int grid_, bool compact, hipStream_t s) {
+    if (sc.gmed.rho && sc.integrator.type >= INT_MATS) { wf_grid_medium_launch_finish(sc, &b, cur, &bt, count, grid_, s); return; }
     if (sc.n_lights && sc.integrator.type >= INT_EMS) { wf_lights_launch_finish(sc, &b, cur, &bt, count, grid_, s); return; }
     if (sc.env && sc.integrator.type >= INT_MATS) { wf_env_launch_finish(sc, &b, cur, &bt, count, grid_, s); return; }
     if (sc.medium.on && sc.integrator.type >= INT_MATS) { wf_medium_launch_finish(sc, &b, cur, &bt, count, grid_, s); return; }

@@ -83,8 +83,17 @@ int nori_host_medium(const nori_host_root *root, nori_medium_desc *out) {
     if (!root || !out || root->root->getClassType() != NoriObject::EScene) return NORI_ERR_INVALID_ARGUMENT;
     std::memset(out, 0, sizeof(*out));
     const Medium *m = static_cast<const Scene *>(root->root.get())->getMedium();
-    if (!m) return 0;
+    if (!m || m->isGrid()) return 0;      /* (a grid medium: nori_host_grid_medium) */
     m->fillMedium(*out);
+    return 1;
+}
+
+int nori_host_grid_medium(const nori_host_root *root, nori_grid_medium_desc *out) {
+    if (!root || !out || root->root->getClassType() != NoriObject::EScene) return NORI_ERR_INVALID_ARGUMENT;
+    std::memset(out, 0, sizeof(*out));
+    const Medium *m = static_cast<const Scene *>(root->root.get())->getMedium();
+    if (!m || !m->isGrid()) return 0;
+    m->fillGridMedium(*out);
     return 1;
 }
 

@@ -109,11 +109,14 @@ public:
     virtual float getAsymmetry() const = 0;      /* Henyey-Greenstein g; 0: isotropic */
 };
 
-/* <medium type="homogeneous"> as a child of <scene>: it fills all space */
+/* <medium type="homogeneous"> as a child of <scene>: it fills all space; or <medium type="grid">: a box of voxels (include/nori_hip.h,
+   "Grid medium") */
 class Medium : public NoriObject {
 public:
     EClassType getClassType() const { return EMedium; }
-    virtual void fillMedium(nori_medium_desc &) const = 0;      /* the record nori_hip_set_medium takes */
+    virtual void fillMedium(nori_medium_desc &) const = 0;      /* the record nori_hip_set_medium takes (a grid: zeros) */
+    virtual bool isGrid() const { return false; }
+    virtual void fillGridMedium(nori_grid_medium_desc &) const {}      /* a grid: the record nori_hip_set_grid_medium takes; rho is borrowed */
 };
 
 /* ---------------------------------------------------------------- Sampler */

@@ -396,6 +396,84 @@ private:
 };
 NORI_REGISTER_CLASS(HomogeneousMedium, "homogeneous");
 
+/* <medium type="grid"> as a child of <scene> (include/nori_hip.h, "Grid medium"): a box of voxels of piecewise-constant density.
+ *   filename     string, a VOL file, little-endian: the bytes 'V' 'O' 'L', a version byte 3, int32 encoding 1 (float32), int32 nx, ny, nz,
+ *                int32 channels 1, six float32 xmin ymin zmin xmax ymax zmax, then nx ny nz float32 with x fastest
+ *   sigmaScale   float, a voxel's extinction is sigmaScale rho: 0, or 1e-4 .. 1e4 (default 1)
+ *   albedo       color, the single-scattering albedo, each component 0 .. 1 (default 1)
+ *   boxMin, boxMax   points, optional: they override the file's box
+ *   <phase>      an optional child: isotropic (the default) or hg
+ * What nori_hip_set_grid_medium would refuse of the grid is said here, before a device is asked for. */
+class GridMedium : public Medium {
+public:
+    GridMedium(const PropertyList &propList) {
+        m_filename = getFileResolver()->resolve(propList.getString("filename"));
+        std::ifstream is(m_filename, std::ios::binary);
+        if (!is) throw NoriException("medium grid: cannot open \"%s\"", m_filename);
+        char magic[4] = {0, 0, 0, 0};
+        int32_t head[5] = {0, 0, 0, 0, 0};
+        float box[6];
+        is.read(magic, 4);
+        is.read(reinterpret_cast<char *>(head), sizeof(head));
+        is.read(reinterpret_cast<char *>(box), sizeof(box));
+        if (!is || magic[0] != 'V' || magic[1] != 'O' || magic[2] != 'L' || magic[3] != 3)
+            throw NoriException("medium grid: \"%s\" is not a VOL file of version 3", m_filename);
+        if (head[0] != 1) throw NoriException("medium grid: \"%s\": encoding %d, only 1 (float32) is read", m_filename, head[0]);
+        if (head[4] != 1) throw NoriException("medium grid: \"%s\": %d channels, only 1 is read", m_filename, head[4]);
+        for (int a = 0; a < 3; ++a) {
+            m_n[a] = head[1 + a];
+            if (m_n[a] < 1 || m_n[a] > 256) throw NoriException("medium grid: nx, ny and nz must each lie in 1 .. 256 (got %d x %d x %d)", head[1], head[2], head[3]);
+            m_bmin[a] = box[a]; m_bmax[a] = box[3 + a];
+        }
+        if (propList.has("boxMin")) { const Point3f p = propList.getPoint("boxMin"); for (int a = 0; a < 3; ++a) m_bmin[a] = p[a]; }
+        if (propList.has("boxMax")) { const Point3f p = propList.getPoint("boxMax"); for (int a = 0; a < 3; ++a) m_bmax[a] = p[a]; }
+        for (int a = 0; a < 3; ++a)
+            if (!(std::isfinite(m_bmin[a]) && std::isfinite(m_bmax[a]) && m_bmin[a] < m_bmax[a] && std::isfinite(m_bmax[a] - m_bmin[a])))
+                throw NoriException("medium grid: the box needs finite boxMin < boxMax on every axis (axis %d: %f, %f)", a, m_bmin[a], m_bmax[a]);
+        m_sigmaScale = propList.getFloat("sigmaScale", 1.0f);
+        if (!std::isfinite(m_sigmaScale) || !(m_sigmaScale >= 0.0f)) throw NoriException("medium grid: sigmaScale must be finite and not negative (got %f)", m_sigmaScale);
+        m_albedo = propList.getColor("albedo", Color3f(1.0f));
+        for (int c = 0; c < 3; ++c)
+            if (!(std::isfinite(m_albedo[c]) && m_albedo[c] >= 0.0f && m_albedo[c] <= 1.0f)) throw NoriException("medium: every albedo component must lie in [0, 1]");
+        const size_t n = (size_t) m_n[0] * (size_t) m_n[1] * (size_t) m_n[2];
+        m_rho.resize(n);
+        is.read(reinterpret_cast<char *>(m_rho.data()), (std::streamsize) (n * sizeof(float)));
+        if (!is) throw NoriException("medium grid: \"%s\" ends before its %d x %d x %d voxels", m_filename, m_n[0], m_n[1], m_n[2]);
+        for (size_t k = 0; k < n; ++k) {
+            const float rho = m_rho[k], sigma = m_sigmaScale * rho;
+            if (!(std::isfinite(rho) && rho >= 0.0f && (sigma == 0.0f || (sigma >= 1e-4f && sigma <= 1e4f))))
+                throw NoriException("medium grid: voxel %d: rho must be finite and not negative, and sigmaScale * rho 0 or in [1e-4, 1e4] (rho %f)", (int) k, rho);
+        }
+    }
+    ~GridMedium() { delete m_phase; }
+    void addChild(NoriObject *obj) {
+        if (obj->getClassType() != EPhaseFunction) throw NoriException("Medium::addChild(<%s>) is not supported!", classTypeName(obj->getClassType()));
+        if (m_phase) throw NoriException("There can only be one phase function per medium!");
+        m_phase = static_cast<PhaseFunction *>(obj);
+    }
+    void fillMedium(nori_medium_desc &d) const { std::memset(&d, 0, sizeof(d)); }
+    bool isGrid() const { return true; }
+    void fillGridMedium(nori_grid_medium_desc &d) const {
+        d.rho = m_rho.data();
+        d.nx = m_n[0]; d.ny = m_n[1]; d.nz = m_n[2];
+        for (int a = 0; a < 3; ++a) { d.bmin[a] = m_bmin[a]; d.bmax[a] = m_bmax[a]; d.albedo[a] = m_albedo[a]; }
+        d.sigma_scale = m_sigmaScale;
+        d.g = m_phase ? m_phase->getAsymmetry() : 0.0f;
+    }
+    std::string toString() const {
+        return format("GridMedium[\n  filename = \"%s\",\n  voxels = %d x %d x %d,\n  sigmaScale = %f,\n  albedo = %s,\n  phase = %s\n]", m_filename, m_n[0], m_n[1], m_n[2],
+                      m_sigmaScale, m_albedo.toString(), m_phase ? indent(m_phase->toString()) : std::string("Isotropic[]"));
+    }
+private:
+    std::string m_filename;
+    int32_t m_n[3];
+    float m_bmin[3], m_bmax[3], m_sigmaScale;
+    Color3f m_albedo;
+    std::vector<float> m_rho;
+    PhaseFunction *m_phase = nullptr;
+};
+NORI_REGISTER_CLASS(GridMedium, "grid");
+
 /* ================================================================ Sampler */
 /* src/independent.cpp:21-67.  The pcg32 arithmetic runs on the device
    (nori_hip_pcg32_floats_at); the host keeps the stream key, how many numbers of the stream it has
@@ -733,6 +811,8 @@ void Scene::activate() {
         m_integrator->fill(id);
         if (id.type != NORI_INTEGRATOR_PATH_MATS && id.type != NORI_INTEGRATOR_PATH_EMS && id.type != NORI_INTEGRATOR_PATH_MIS)
             throw NoriException("A medium is rendered by path_mats, path_ems and path_mis only");
+        if (m_environment && m_medium->isGrid())
+            throw NoriException("A grid medium cannot be lit by an environment map yet (no kernel set combines the two)");
         if (m_environment)
             throw NoriException("A medium that fills all space cannot be lit by an environment map (its transmittance to infinity is zero)");
     }
@@ -742,7 +822,7 @@ void Scene::activate() {
         if (id.type != NORI_INTEGRATOR_PATH_EMS && id.type != NORI_INTEGRATOR_PATH_MIS)
             throw NoriException("Point, spot and directional lights are rendered by path_ems and path_mis only");
         if (m_lights.size() > NORI_MAX_LIGHTS) throw NoriException("There can be at most %d point, spot and directional lights per scene!", (int) NORI_MAX_LIGHTS);
-        if (m_medium)
+        if (m_medium && !m_medium->isGrid())      /* (a grid medium is bounded by its box: a directional light may light it) */
             for (const nori_light_desc &l : m_lights)
                 if (l.type == NORI_LIGHT_DIRECTIONAL)
                     throw NoriException("A directional light cannot light a medium that fills all space (its transmittance from infinity is zero)");
@@ -851,7 +931,11 @@ Device &Scene::device() const {
             m_environment->fillEnvironment(env);
             d->check(nori_hip_set_environment(d->ctx(), &env), "nori_hip_set_environment");
         }
-        if (m_medium) {
+        if (m_medium && m_medium->isGrid()) {
+            nori_grid_medium_desc gd;
+            m_medium->fillGridMedium(gd);
+            d->check(nori_hip_set_grid_medium(d->ctx(), &gd), "nori_hip_set_grid_medium");
+        } else if (m_medium) {
             nori_medium_desc md;
             m_medium->fillMedium(md);
             d->check(nori_hip_set_medium(d->ctx(), &md), "nori_hip_set_medium");
@@ -873,7 +957,11 @@ DeviceGroup &Scene::deviceGroup(int n) const {
             m_environment->fillEnvironment(env);
             g->check(nori_hip_group_set_environment(g->group(), &env), "nori_hip_group_set_environment");
         }
-        if (m_medium) {
+        if (m_medium && m_medium->isGrid()) {
+            nori_grid_medium_desc gd;
+            m_medium->fillGridMedium(gd);
+            g->check(nori_hip_group_set_grid_medium(g->group(), &gd), "nori_hip_group_set_grid_medium");
+        } else if (m_medium) {
             nori_medium_desc md;
             m_medium->fillMedium(md);
             g->check(nori_hip_group_set_medium(g->group(), &md), "nori_hip_group_set_medium");

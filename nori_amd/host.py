@@ -35,6 +35,7 @@ HOST_PROTOTYPES = {
     "nori_host_lens": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "nori_host_environment": (C.c_int, [_P, C.POINTER(capi.EnvDesc)]),
     "nori_host_medium": (C.c_int, [_P, C.POINTER(capi.MediumDesc)]),
+    "nori_host_grid_medium": (C.c_int, [_P, C.POINTER(capi.GridMediumDesc)]),
     "nori_host_lights": (C.c_int, [_P, C.c_uint32, C.POINTER(capi.LightDesc), C.POINTER(C.c_uint32)]),
     "nori_host_test_info_get": (C.c_int, [_P, C.POINTER(TestInfo)]),
     "nori_host_test_bsdf": (C.c_int, [_P, C.c_uint32, C.POINTER(capi.BsdfDesc)]),
@@ -173,7 +174,18 @@ class HostRoot:
         return [Light.from_desc(arr[k]) for k in range(n.value)]
 
     def medium(self):
-        """The scene's medium (<medium type="homogeneous">) as a scene.Medium; None without one."""
+        """The scene's medium: <medium type="homogeneous"> as a scene.Medium, <medium type="grid"> as a scene.GridMedium (the voxels
+        copied); None without one."""
+        from .scene import GridMedium
+        gd = capi.GridMediumDesc()
+        rc = self._lib.nori_host_grid_medium(self._h, C.byref(gd))
+        if rc < 0:
+            raise NoriError("root is not a <scene>")
+        if rc == 1:
+            n = int(gd.nx) * int(gd.ny) * int(gd.nz)
+            rho = np.ctypeslib.as_array(C.cast(gd.rho, C.POINTER(C.c_float)), shape=(n,)).copy().reshape(int(gd.nz), int(gd.ny), int(gd.nx))
+            return GridMedium(rho, tuple(float(x) for x in gd.bmin), tuple(float(x) for x in gd.bmax), float(gd.sigma_scale),
+                              tuple(float(x) for x in gd.albedo), float(gd.g))
         d = capi.MediumDesc()
         rc = self._lib.nori_host_medium(self._h, C.byref(d))
         if rc < 0:

@@ -144,7 +144,11 @@ class Renderer:
     # ------------------------------------------------------------ homogeneous medium
     def set_medium(self, medium):
         """The homogeneous medium of the uploaded scene (include/nori_hip.h, "Homogeneous participating medium"): a scene.Medium, or
-        None for no medium -- the kernels and the bits of a context that never had one.  Holds until the next upload."""
+        None for no medium of either kind -- the kernels and the bits of a context that never had one.  Holds until the next upload.
+        (A scene.GridMedium, which Scene.medium may hold instead, goes to set_grid_medium.)"""
+        from .scene import GridMedium
+        if isinstance(medium, GridMedium):
+            return self.set_grid_medium(medium)
         d = medium.desc() if medium is not None else None
         self._check(self._lib.nori_hip_set_medium(self._h, C.byref(d) if d is not None else None), "set_medium")
         return self
@@ -188,6 +192,55 @@ class Renderer:
         wo, p = np.zeros((a.shape[0], 3), np.float32), np.zeros(a.shape[0], np.float32)
         self._check(self._lib.nori_hip_phase_sample(self._h, ptr(a), ptr(x), a.shape[0], ptr(wo), ptr(p)), "phase_sample")
         return wo, p
+
+    # ------------------------------------------------------------ grid medium
+    def set_grid_medium(self, medium):
+        """The grid medium of the uploaded scene (include/nori_hip.h, "Grid medium"): a scene.GridMedium, which replaces any medium
+        set before, or None to unset a grid medium.  Holds until the next upload."""
+        d = medium.desc() if medium is not None else None
+        self._check(self._lib.nori_hip_set_grid_medium(self._h, C.byref(d) if d is not None else None), "set_grid_medium")
+        return self
+
+    @property
+    def grid_medium(self):
+        """The record of the grid medium set, as the context stores it, without the voxels: a dict, or None."""
+        d = capi.GridMediumDesc()
+        rc = self._lib.nori_hip_get_grid_medium(self._h, C.byref(d))
+        if rc < 0:
+            self._check(rc, "get_grid_medium")
+        if rc != 1:
+            return None
+        return {"shape": (int(d.nz), int(d.ny), int(d.nx)), "bmin": tuple(float(x) for x in d.bmin), "bmax": tuple(float(x) for x in d.bmax),
+                "sigma_scale": float(d.sigma_scale), "albedo": tuple(float(x) for x in d.albedo), "g": float(d.g)}
+
+    def _grid_rays(self, o, d, t):
+        a, b = _f32(o, 3), _f32(d, 3)
+        x = np.ascontiguousarray(t, dtype=np.float32).reshape(-1)
+        assert a.shape == b.shape and a.shape[0] == x.shape[0]
+        return a, b, x
+
+    def grid_medium_distance(self, o, d, tmax, xi):
+        """The free flights the (n,) samples xi select on the rays (o, d: (n, 3)) over [0, tmax], as Li draws them; +inf: no event."""
+        a, b, t = self._grid_rays(o, d, tmax)
+        x = np.ascontiguousarray(xi, dtype=np.float32).reshape(-1)
+        assert x.shape[0] == t.shape[0]
+        s = np.zeros(t.shape[0], np.float32)
+        self._check(self._lib.nori_hip_grid_medium_distance(self._h, ptr(a), ptr(b), ptr(t), ptr(x), t.shape[0], ptr(s)), "grid_medium_distance")
+        return s
+
+    def grid_medium_transmittance(self, o, d, dist):
+        """Tr = exp(-tau) of the rays (o, d: (n, 3)) over [0, dist]; dist may be infinite."""
+        a, b, t = self._grid_rays(o, d, dist)
+        tr = np.zeros(t.shape[0], np.float32)
+        self._check(self._lib.nori_hip_grid_medium_transmittance(self._h, ptr(a), ptr(b), ptr(t), t.shape[0], ptr(tr)), "grid_medium_transmittance")
+        return tr
+
+    def grid_medium_optical_depth(self, o, d, tmax):
+        """(tau (n,), voxels visited (n,) int32) of the rays (o, d: (n, 3)) over [0, tmax]."""
+        a, b, t = self._grid_rays(o, d, tmax)
+        tau, steps = np.zeros(t.shape[0], np.float32), np.zeros(t.shape[0], np.int32)
+        self._check(self._lib.nori_hip_grid_medium_optical_depth(self._h, ptr(a), ptr(b), ptr(t), t.shape[0], ptr(tau), ptr(steps)), "grid_medium_optical_depth")
+        return tau, steps
 
     # ------------------------------------------------------------ environment map
     def set_environment(self, env):
@@ -1044,8 +1097,17 @@ class DeviceGroup:
 
     def set_medium(self, medium):
         """Renderer.set_medium on every device of the group."""
+        from .scene import GridMedium
+        if isinstance(medium, GridMedium):
+            return self.set_grid_medium(medium)
         d = medium.desc() if medium is not None else None
         self._check(self._lib.nori_hip_group_set_medium(self._h, C.byref(d) if d is not None else None), "group_set_medium")
+        return self
+
+    def set_grid_medium(self, medium):
+        """Renderer.set_grid_medium on every device of the group."""
+        d = medium.desc() if medium is not None else None
+        self._check(self._lib.nori_hip_group_set_grid_medium(self._h, C.byref(d) if d is not None else None), "group_set_grid_medium")
         return self
 
     def set_environment(self, env):

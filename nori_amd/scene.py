@@ -116,6 +116,39 @@ class Medium:
         return d
 
 
+@dataclass(eq=False)
+class GridMedium:
+    """The grid medium of a scene (nori_grid_medium_desc in include/nori_hip.h, which states every operation): a box of voxels of
+    piecewise-constant density, vacuum outside it.  Accepted as Scene.medium in place of a Medium: Renderer.upload applies it with
+    nori_hip_set_grid_medium."""
+    rho: np.ndarray                         # (nz, ny, nx) float32 densities, each finite and >= 0: x fastest in memory
+    bmin: tuple = (0.0, 0.0, 0.0)           # the box, world space
+    bmax: tuple = (1.0, 1.0, 1.0)
+    sigma_scale: float = 1.0                # a voxel's extinction is sigma_scale rho: 0, or 1e-4 .. 1e4
+    albedo: tuple = (1.0, 1.0, 1.0)         # single-scattering albedo, each 0 .. 1
+    g: float = 0.0                          # Henyey-Greenstein asymmetry, |g| <= 0.99; > 0 scatters forward
+
+    def __post_init__(self):
+        self.rho = np.ascontiguousarray(self.rho, dtype=np.float32)
+        assert self.rho.ndim == 3, "rho: (nz, ny, nx)"
+        self.bmin, self.bmax, self.albedo = tuple(map(float, self.bmin)), tuple(map(float, self.bmax)), tuple(map(float, self.albedo))
+
+    def __eq__(self, other):
+        return (isinstance(other, GridMedium) and self.rho.shape == other.rho.shape and self.rho.tobytes() == other.rho.tobytes() and
+                (self.bmin, self.bmax, self.sigma_scale, self.albedo, self.g) == (other.bmin, other.bmax, other.sigma_scale, other.albedo, other.g))
+
+    def desc(self) -> capi.GridMediumDesc:
+        """The ctypes struct; it borrows self.rho."""
+        d = capi.GridMediumDesc()
+        d.rho = self.rho.ctypes.data
+        d.nz, d.ny, d.nx = (int(x) for x in self.rho.shape)
+        d.bmin[:], d.bmax[:] = self.bmin, self.bmax
+        d.sigma_scale = float(self.sigma_scale)
+        d.albedo[:] = self.albedo
+        d.g = float(self.g)
+        return d
+
+
 @dataclass
 class Light:
     """A delta light (nori_light_desc in include/nori_hip.h, which states every operation): "point", "spot" or "directional".
@@ -308,7 +341,11 @@ class Scene:
             meta["textures"] = [dict(t.params(), texels=t.texels is not None) for t in self.textures]
         if self.environment is not None:      # (scenes without one: the file of before, key for key)
             meta["environment"] = {"scale": list(map(float, self.environment.scale))}
-        if self.medium is not None:           # (likewise)
+        if isinstance(self.medium, GridMedium):      # (likewise; the voxels are an array of their own)
+            assert base is None, "a variant fixture (base=...) stores no arrays: save a scene with a grid medium whole"
+            m = self.medium
+            meta["grid_medium"] = {"bmin": list(m.bmin), "bmax": list(m.bmax), "sigma_scale": float(m.sigma_scale), "albedo": list(m.albedo), "g": float(m.g)}
+        elif self.medium is not None:           # (likewise)
             meta["medium"] = {"sigma_t": float(self.medium.sigma_t), "albedo": list(map(float, self.medium.albedo)), "g": float(self.medium.g)}
         if self.lights:                       # (likewise)
             meta["lights"] = [{"type": l.type, "position": list(map(float, l.position)), "direction": list(map(float, l.direction)),
@@ -333,6 +370,8 @@ class Scene:
                 arrays[f"t{k}_texels"] = t.texels
         if self.environment is not None:
             arrays["env_texels"], arrays["env_to_world"] = self.environment.texels, self.environment.to_world
+        if isinstance(self.medium, GridMedium):
+            arrays["grid_medium_rho"] = self.medium.rho
         arrays["meta"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
         np.savez_compressed(path, **arrays)
 
@@ -380,6 +419,9 @@ class Scene:
             sc.environment = Environment(z["env_texels"], tuple(meta["environment"]["scale"]), z["env_to_world"])
         if "medium" in meta:
             sc.medium = Medium(meta["medium"]["sigma_t"], tuple(meta["medium"]["albedo"]), meta["medium"]["g"])
+        if "grid_medium" in meta:
+            gm = meta["grid_medium"]
+            sc.medium = GridMedium(z["grid_medium_rho"], tuple(gm["bmin"]), tuple(gm["bmax"]), gm["sigma_scale"], tuple(gm["albedo"]), gm["g"])
         for l in meta.get("lights", []):
             sc.lights.append(Light(l["type"], tuple(l["position"]), tuple(l["direction"]), tuple(l["intensity"]), l["cos_inner"], l["cos_outer"]))
         return sc
